@@ -253,6 +253,43 @@ class Watchdog(threading.Thread):
                 self.fail(f"no progress: phase '{self.phase}' exceeded its deadline -- a rank is missing or a collective hangs", 5)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, plan, alg, update_out):
+    """--dump-outputs: what the LAST timed step handed its caller, one DIR/<name>.npy per array -- the planner's outputs, the
+    storage's returns and advantages (compute_returns), the update's mean losses, learning rate and per-mini-batch statistics, and
+    the trained parameters (state_dict order, flattened).  Integers (foothold indices) as float64, everything else float32 /
+    float64 as computed.  Inputs are seeded, so two builds run with the same arguments can be compared array for array.  An array
+    that would take the total past 64 MB is replaced by a fixed, seeded sample of its flattened elements."""
+    import numpy as np
+    st = alg.storage
+    arrays = {f"plan_{k}": v for k, v in sorted(plan.items())}
+    arrays.update(returns=st.returns, advantages=st.advantages,
+                  update_losses=torch.tensor([float(x) for x in update_out], dtype=torch.float64),
+                  learning_rate=torch.tensor([float(alg.learning_rate)], dtype=torch.float64),
+                  parameters=torch.cat([v.detach().reshape(-1).float() for v in alg.actor_critic.state_dict().values()
+                                        if v.is_floating_point()]))
+    stats = getattr(alg, "last_update_stats", None)
+    if stats is not None:
+        arrays["update_stats"] = stats
+    host = {}
+    for name, t in arrays.items():
+        x = t.detach().cpu()
+        host[name] = (x.double() if not x.is_floating_point() or x.dtype == torch.float64 else x.float()).numpy()
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_LIMIT_BYTES
+    for i, name in enumerate(sorted(host, key=lambda k: host[k].nbytes)):       # smallest first: each gets an equal share of what is left
+        x = host[name]
+        share = left // (len(host) - i)
+        if x.nbytes > share:
+            pick = np.random.default_rng(0).choice(x.size, size=share // x.itemsize, replace=False)
+            x = x.reshape(-1)[np.sort(pick)]
+        np.save(os.path.join(path, name + ".npy"), x)
+        left -= x.nbytes
+    return sorted(host)
+
+
 def self_launch(n: int) -> int:
     """Re-execute this script as `n` ranks (one per GPU of this node) under torch.distributed.run and return its exit code.
     The children inherit stdout / stderr, so rank 0's single JSON line is what the caller of `python bench.py --gpus N`
@@ -311,7 +348,11 @@ def main():
     ap.add_argument("--detail", default=os.environ.get("DTC_BENCH_DETAIL"), help="where the full record (everything the result line leaves "
                     "out) goes; default gpurun_out/bench_detail.json")
     ap.add_argument("--cpu-baseline-full", action="store_true", help="time the CPU port on the WHOLE workload (no GPU work) and exit")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step computed (planner "
+                    "outputs, returns / advantages, the update's losses, the trained parameters) as DIR/<name>.npy, float32 / float64")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.cpu_baseline_full:
         emit_line(dict(cpu_baseline_full=cpu_baseline(full=True)))
         return
@@ -425,7 +466,9 @@ def run(a, rank, local_rank, world, wd):
 
         def step():
             with tracing.span("foothold_plan"):
-                foothold.plan(sc["measured_heights"], sc["root_states"], sc["thigh_pos"], sc["commands"])
+                plan = foothold.plan(sc["measured_heights"], sc["root_states"], sc["thigh_pos"], sc["commands"])
+            if keep is not None:                         # --dump-outputs: the planner's results of the latest step
+                keep["plan"] = plan
             with tracing.span("compute_returns"):
                 if gru:
                     alg.compute_returns(last["privileged_observations"])
@@ -487,11 +530,16 @@ def run(a, rank, local_rank, world, wd):
         return elapsed, rank_ms, out
 
     composite, gru = a.workload == "composite", a.workload == "gru"
+    keep = {} if a.dump_outputs else None
     alg, step = make_workload(a.workload)
     phase("first exchange of every gradient bucket", 240)
     prime_collectives(alg)
     phase(f"warm-up + timed region ({a.warmup} + {a.steps} steps)", 120 + 3.0 * (a.warmup + a.steps))
     elapsed, rank_ms, out = timed(step, a.steps, a.warmup)
+    if keep is not None:
+        if rank == 0:                                # before any further step changes the trainer's state
+            dump_outputs(a.dump_outputs, keep["plan"], alg, out)
+        keep = None
     phase("accuracy check, per-kernel pass", 900)
 
     # per-kernel HIP-event timing of one more step (same process, each kernel on the stream it is launched on)

@@ -133,3 +133,35 @@ def test_result_line_is_short_machine_readable_and_last_on_stdout(tmp_path, caps
     # nothing was dropped: the side file holds the whole record
     full = json.load(open(tmp_path / "bench_detail.json"))
     assert full["kernel_classes"] == detail["kernel_classes"] and len(full["gemm_accuracy_in_situ"]) == 39
+
+
+def test_dump_outputs_writes_float_arrays_within_64_mb(tmp_path):
+    """--dump-outputs: one DIR/<name>.npy per array the last timed step produced, float32 / float64 only (the foothold indices as
+    float64), at most 64 MB in all; an array over its share is replaced by the same seeded sample on every run."""
+    import types
+
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    st = types.SimpleNamespace(returns=torch.randn(24, 64, 1, generator=g), advantages=torch.randn(24, 64, 1, generator=g))
+    alg = types.SimpleNamespace(storage=st, actor_critic=torch.nn.Linear(32, 8), learning_rate=1e-3,
+                                last_update_stats=torch.randn(20, 12, generator=g))
+    plan = dict(optimal_foothold_indice=torch.randint(0, 693, (1536, 1, 4), generator=g), foothold_obs=torch.randn(1536, 8, generator=g),
+                wide=torch.randn(20 << 20, generator=g))              # 80 MB on its own
+    losses = (1.0, 2.0, 0.0, 0, 3.0, 4.0, 5.0)
+    names = bench.dump_outputs(str(tmp_path / "a"), plan, alg, losses)
+    bench.dump_outputs(str(tmp_path / "b"), plan, alg, losses)
+    assert sorted(os.listdir(tmp_path / "a")) == [n + ".npy" for n in names]
+    total = 0
+    for n in names:
+        x, y = np.load(tmp_path / "a" / (n + ".npy")), np.load(tmp_path / "b" / (n + ".npy"))
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), n
+        total += x.nbytes
+    assert total <= 64 << 20
+    assert np.array_equal(np.load(tmp_path / "a" / "plan_optimal_foothold_indice.npy"), plan["optimal_foothold_indice"].double().numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "returns.npy"), st.returns.numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "update_losses.npy"), np.array(losses, dtype=np.float64))
+    wide = np.load(tmp_path / "a" / "plan_wide.npy")
+    assert 0 < wide.size < plan["wide"].numel() and np.isin(wide, plan["wide"].numpy()).all()

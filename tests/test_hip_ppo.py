@@ -8,6 +8,8 @@ element errors, L2 error / 5) <= 2e-5 of the tensor's max (+ 3/B per ReLU knife 
 when the HIP optimiser steps on the ORACLE's gradient (the real arena, the batch's real sizes), a sanity bound on the
 weights from its own gradients (see _compare_weights).
 GPU only."""
+import contextlib
+
 import numpy as np
 import pytest
 import torch
@@ -232,6 +234,19 @@ def _compare_weights(k, which, pre, grads_ref, ref, alg):
     assert worst[0] <= 2e-6, (k, which, worst)
 
 
+@contextlib.contextmanager
+def _oracle_on_one_thread():
+    """The oracle's steps on ONE host thread.  torch's CPU kernels split their fp32 sums by the thread count, and the gradient norm
+    of a poorly conditioned step moves with that split (64 envs, third step: 30.198397 on 16 threads, 30.198606 on one, same
+    host) -- the reference must not depend on the number of cores of the machine that checks it."""
+    n = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        yield
+    finally:
+        torch.set_num_threads(n)
+
+
 def _teacher_forced_step(k, ref, alg, idx, e1, e2):
     """Both halves of a mini-batch, each started from the oracle's exact state."""
     from oracle.ppo_ref import StepRecord
@@ -243,7 +258,8 @@ def _teacher_forced_step(k, ref, alg, idx, e1, e2):
     can_force = alg.relu_masks and all(ops.relu_mask_ok(B, w) for w in (64, 128, 512))
     _sync_from_oracle(ref, alg)
     pre = _snapshot(ref)
-    ref.vae_step(idx, e1, rec)
+    with _oracle_on_one_thread():
+        ref.vae_step(idx, e1, rec)
     row, _ = alg.step_minibatch(idx, e1, e2, which="vae")
     assert not can_force or forced_log[-1] == ("vae", 7), forced_log
     _compare_scalars(k, rec, row, ref, ("recons", "vel", "kld", "height", "vae_gnorm"))
@@ -251,7 +267,8 @@ def _teacher_forced_step(k, ref, alg, idx, e1, e2):
     _compare_weights(k, "vae", pre, rec.extra["vae_grads"], ref, alg)
     _sync_from_oracle(ref, alg)
     pre = _snapshot(ref)
-    ref.ppo_step(idx, e2, rec)
+    with _oracle_on_one_thread():
+        ref.ppo_step(idx, e2, rec)
     row, lr = alg.step_minibatch(idx, e1, e2, which="ppo")
     _compare_scalars(k, rec, row, ref, ("surrogate", "value", "entropy", "kl_mean", "gnorm"))
     assert lr == ref.learning_rate, (k, lr, ref.learning_rate)
