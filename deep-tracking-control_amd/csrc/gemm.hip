@@ -537,6 +537,134 @@ __global__ __launch_bounds__(256, 3) void gru_step_fwd_kernel(const float* __res
 }
 
 // ------------------------------------------------------------------------------------------
+// One fused LSTM time step (forward): a = gi_t + h_{t-1} W_hh^T + b_hh for the four gates of 32 hidden units, then the
+// gate math of torch.nn.LSTM (gate order i, f, g, o) in the epilogue -- the [R,4H] recurrent pre-activations never
+// touch HBM:
+//   i, f, o = sigmoid(a_i, a_f, a_o), g = tanh(a_g), c_t = f * c_{t-1} + i * g, h_t = o * tanh(c_t)
+// Block tile: 128 rows x (32 units x 4 gates): the loader reads rows j, H+j, 2H+j, 3H+j of W_hh in place (no repacked
+// weights); wave w owns rows 32w..32w+31 and four 32x32 MFMA tiles (i, f, g, o of the same units).  K loop of
+// gru_step_fwd_kernel (loads two K steps ahead of the MFMAs).
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256, 3) void lstm_step_fwd_kernel(const float* __restrict__ hprev, const float* __restrict__ cprev,
+                                                            const float* __restrict__ Whh, const float* __restrict__ bhh,
+                                                            const float* __restrict__ gi, float* __restrict__ hout,
+                                                            float* __restrict__ cout, float* __restrict__ gates, int R, int H) {
+    constexpr int GB = 128, LDAg = BM + PAD, LDBg = GB + PAD;
+    __shared__ float As[2][BK][LDAg];
+    __shared__ float Bs[2][BK][LDBg];
+    int tr, tc;
+    if (!map_tile(blockIdx.x, (R + BM - 1) / BM, H / 32, tr, tc)) return;
+    const int m0 = tr * BM, j0 = tc * 32;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm_off = wave * 32;
+    const int kk = tid & (BK - 1), rbase = tid / BK;
+    constexpr int NA = BM / RP, NB = GB / RP;
+    u32 aoff[NA], woff[NB];
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+        const int m = m0 + rbase + RP * i;
+        aoff[i] = m < R ? (u32)(m * H + kk) * 4u : INVALID;
+    }
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+        const int n = rbase + RP * i;                       // 0..127: gate n / 32, unit j0 + n % 32
+        woff[i] = (u32)(((n >> 5) * H + j0 + (n & 31)) * H + kk) * 4u;
+    }
+    const rsrc_t ares = make_rsrc(hprev), wres = make_rsrc(Whh);
+    float ra[2][NA], rb[2][NB];
+    auto load_tile = [&](auto set, int kt) {
+        constexpr int S = decltype(set)::value;
+        const u32 ko = (u32)(kt * BK) * 4u;
+#pragma unroll
+        for (int i = 0; i < NA; ++i) ra[S][i] = bload(ares, aoff[i], ko);
+#pragma unroll
+        for (int i = 0; i < NB; ++i) rb[S][i] = bload(wres, woff[i], ko);
+    };
+    auto store_tile = [&](auto set, int buf) {
+        constexpr int S = decltype(set)::value;
+#pragma unroll
+        for (int i = 0; i < NA; ++i) As[buf][kk][rbase + RP * i] = ra[S][i];
+#pragma unroll
+        for (int i = 0; i < NB; ++i) Bs[buf][kk][rbase + RP * i] = rb[S][i];
+    };
+    f32x16 acc[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[g][r] = 0.f;
+    const int half = lane >> 5, l31 = lane & 31;
+    auto mfma = [&](int buf) {
+        const float* ap = &As[buf][0][0] + half * LDAg + wm_off + l31;
+        const float* bp = &Bs[buf][0][0] + half * LDBg + l31;
+#pragma unroll
+        for (int kp = 0; kp < BK / 2; ++kp) {
+            const float a = ap[2 * kp * LDAg];
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+                acc[g] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bp[2 * kp * LDBg + 32 * g], acc[g], 0, 0, 0);
+        }
+    };
+    const int KT = H / BK;                                  // even: H is a multiple of 32
+    int buf = 0;
+    load_tile(S0{}, 0);
+    store_tile(S0{}, 0);
+    __syncthreads();
+    load_tile(S1{}, 1);                                     // invariant: LDS[buf] = tile kt, set 1 = tile kt+1 in flight
+    for (int kt = 0; kt + 2 < KT; kt += 2) {
+        load_tile(S0{}, kt + 2);
+        mfma(buf);
+        store_tile(S1{}, buf ^ 1);
+        __syncthreads();
+        buf ^= 1;
+        load_tile(S1{}, kt + 3);
+        mfma(buf);
+        store_tile(S0{}, buf ^ 1);
+        __syncthreads();
+        buf ^= 1;
+    }
+    mfma(buf);
+    store_tile(S1{}, buf ^ 1);
+    __syncthreads();
+    mfma(buf ^ 1);
+
+    // epilogue: gate math; gi / c_{t-1} come in through unconditional buffer loads (rows >= R read 0)
+    const int j = j0 + l31;
+    const float bi = bhh[j], bf = bhh[H + j], bg = bhh[2 * H + j], bo = bhh[3 * H + j];
+    const rsrc_t gres = make_rsrc_bytes(gi, (long long)R * 4 * H * 4), cres = make_rsrc_bytes(cprev, (long long)R * H * 4);
+    const int row0 = m0 + wm_off + 4 * half;
+    float gvi[16], gvf[16], gvg[16], gvo[16], cp[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int ro = (r & 3) + 8 * (r >> 2);
+        const u32 go = (u32)((row0 + ro) * 4 * H + j) * 4u;
+        gvi[r] = bload(gres, go, 0u);
+        gvf[r] = bload(gres, go, (u32)H * 4u);
+        gvg[r] = bload(gres, go, (u32)H * 8u);
+        gvo[r] = bload(gres, go, (u32)H * 12u);
+        cp[r] = bload(cres, (u32)((row0 + ro) * H + j) * 4u, 0u);
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int row = row0 + (r & 3) + 8 * (r >> 2);
+        const float ig = sigmoid_f(gvi[r] + (acc[0][r] + bi));
+        const float fg = sigmoid_f(gvf[r] + (acc[1][r] + bf));
+        const float gg = tanhf(gvg[r] + (acc[2][r] + bg));
+        const float og = sigmoid_f(gvo[r] + (acc[3][r] + bo));
+        const float c = fg * cp[r] + ig * gg;
+        if (row < R) {
+            const long long e = (long long)row * H + j;
+            float* gp = gates + (long long)row * 4 * H + j;
+            cout[e] = c;
+            hout[e] = og * tanhf(c);
+            gp[0] = ig;
+            gp[H] = fg;
+            gp[2 * H] = gg;
+            gp[3 * H] = og;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // Data gradient: dX[M,K] = (dZ[M,N] W[N,K]) * act'(Xsaved)   (reduction over N)
 // ------------------------------------------------------------------------------------------
 // A = dZ rows (reduction index n contiguous): the stage image of the forward kernel (dwordx4 loads, ds_read_b128
@@ -944,6 +1072,18 @@ extern "C" int dtc_gru_step_fwd(const float* hprev, const float* W_hh, const flo
     dtc::ProfScope prof(dtc::prof_shape_name("gru_step_fwd", R, 3 * H, H), 2.0 * R * 3.0 * H * H, s);
     hipLaunchKernelGGL(gru_step_fwd_kernel, dim3(grid), dim3(256), 0, s, hprev, W_hh, b_hh, gi_t, hout, gates_t, hn_t, R, H);
     return dtc::check_launch("gru_step_fwd");
+}
+
+extern "C" int dtc_lstm_step_fwd(const float* hprev, const float* cprev, const float* W_hh, const float* b_hh, const float* gi_t,
+                                 float* hout, float* cout, float* gates_t, int R, int H, void* stream) {
+    DTC_REQUIRE(R > 0 && H > 0 && H % 32 == 0, "bad shape R=%d H=%d (H must be a multiple of 32)", R, H);
+    DTC_REQUIRE(hprev && cprev && W_hh && b_hh && gi_t && hout && cout && gates_t, "null pointer");
+    DTC_REQUIRE((long long)(R + BM) * 4 * H <= MAX_ELEMS && 4ll * H * H <= MAX_ELEMS, "matrix too large");
+    hipStream_t s = (hipStream_t)stream;
+    const int grid = grid_for((int)dtc::ceil_div(R, BM), H / 32);
+    dtc::ProfScope prof(dtc::prof_shape_name("lstm_step_fwd", R, 4 * H, H), 2.0 * R * 4.0 * H * H, s);
+    hipLaunchKernelGGL(lstm_step_fwd_kernel, dim3(grid), dim3(256), 0, s, hprev, cprev, W_hh, b_hh, gi_t, hout, cout, gates_t, R, H);
+    return dtc::check_launch("lstm_step_fwd");
 }
 
 static int linear_dgrad_impl(const float* dZ, int64_t lddz, const float* W, const DtcSegMat* dX, const float* Xsaved,

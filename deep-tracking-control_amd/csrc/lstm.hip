@@ -5,7 +5,9 @@
 //     a = gi_t + h_{t-1} W_hh^T + b_hh;  i, f, o = sigmoid(a_i, a_f, a_o), g = tanh(a_g)
 //     c_t = f * c_{t-1} + i * g;  h_t = o * tanh(c_t)
 // Same structure as gru.hip (all launches issued from this C++ loop, no Python between time steps):
-//   forward  t = 0..T-1 : gh = h_{t-1} W_hh^T + b_hh (dtc_linear_fwd, R rows) + lstm_gate_fwd_kernel (saves i, f, g, o)
+//   forward  t = 0..T-1 : gh = h_{t-1} W_hh^T + b_hh (dtc_linear_fwd, R rows) + lstm_gate_fwd_kernel (saves i, f, g, o);
+//                         dtc_lstm_fwd_fused: ONE launch per step (dtc_lstm_step_fwd in gemm.hip, the gate math in the GEMM's
+//                         epilogue) where H % 32 == 0
 //   backward t = T-1..0 : lstm_gate_bwd_kernel (da_t -> dgi_t, dc_{t-1});  dh_{t-1} = da_t W_hh as FOUR H-long chunks side by
 //                         side (dtc_linear_dgrad_split), added in a fixed order by the next gate kernel
 //            after loop : dW_hh, db_hh = [da_0..da_{T-1}]^T [h_{-1}..h_{T-2}]   (ONE dtc_linear_wgrad over T*R rows; for an LSTM
@@ -94,8 +96,9 @@ extern "C" int64_t dtc_lstm_workspace(int T, int R, int H) {
     return (int64_t)R * 4 * H * sizeof(float) + 16 + dtc_linear_wgrad_workspace(T * R, 4 * H, H);
 }
 
-extern "C" int dtc_lstm_fwd(const float* gi, const float* h0, const float* c0, const float* W_hh, const float* b_hh,
-                            float* hs_all, float* cs_all, float* gates, void* workspace, int T, int R, int H, void* stream) {
+// fused: one dtc_lstm_step_fwd launch per step where H % 32 == 0 (else, and always for dtc_lstm_fwd, the GEMM + gate pair)
+static int lstm_fwd_impl(const float* gi, const float* h0, const float* c0, const float* W_hh, const float* b_hh, float* hs_all,
+                         float* cs_all, float* gates, void* workspace, int T, int R, int H, void* stream, bool fused) {
     DTC_REQUIRE(T > 0 && R > 0 && H > 0, "bad shape T=%d R=%d H=%d", T, R, H);
     DTC_REQUIRE(gi && h0 && c0 && W_hh && b_hh && hs_all && cs_all && gates && workspace, "null pointer");
     hipStream_t s = (hipStream_t)stream;
@@ -109,6 +112,12 @@ extern "C" int dtc_lstm_fwd(const float* gi, const float* h0, const float* c0, c
     const unsigned grid = (unsigned)dtc::ceil_div((int64_t)RH, 256);
     for (int t = 0; t < T; ++t) {
         const float* hprev = hs_all + (size_t)t * RH;
+        if (fused && H % 32 == 0) {
+            int rc = dtc_lstm_step_fwd(hprev, cs_all + (size_t)t * RH, W_hh, b_hh, gi + (size_t)t * R4H, hs_all + (size_t)(t + 1) * RH,
+                                       cs_all + (size_t)(t + 1) * RH, gates + (size_t)t * R4H, R, H, stream);
+            if (rc != DTC_OK) return rc;
+            continue;
+        }
         const DtcSegMat X = plain(hprev, H, H, R);
         int rc = dtc_linear_fwd(&X, W_hh, b_hh, gh, 4 * H, R, 4 * H, H, DTC_ACT_NONE, stream);
         if (rc != DTC_OK) return rc;
@@ -116,7 +125,17 @@ extern "C" int dtc_lstm_fwd(const float* gi, const float* h0, const float* c0, c
         hipLaunchKernelGGL(lstm_gate_fwd_kernel, dim3(grid), dim3(256), 0, s, gi + (size_t)t * R4H, gh, cs_all + (size_t)t * RH,
                            hs_all + (size_t)(t + 1) * RH, cs_all + (size_t)(t + 1) * RH, gates + (size_t)t * R4H, R, H);
     }
-    return dtc::check_launch("lstm_fwd");
+    return dtc::check_launch(fused ? "lstm_fwd_fused" : "lstm_fwd");
+}
+
+extern "C" int dtc_lstm_fwd(const float* gi, const float* h0, const float* c0, const float* W_hh, const float* b_hh,
+                            float* hs_all, float* cs_all, float* gates, void* workspace, int T, int R, int H, void* stream) {
+    return lstm_fwd_impl(gi, h0, c0, W_hh, b_hh, hs_all, cs_all, gates, workspace, T, R, H, stream, false);
+}
+
+extern "C" int dtc_lstm_fwd_fused(const float* gi, const float* h0, const float* c0, const float* W_hh, const float* b_hh,
+                                  float* hs_all, float* cs_all, float* gates, void* workspace, int T, int R, int H, void* stream) {
+    return lstm_fwd_impl(gi, h0, c0, W_hh, b_hh, hs_all, cs_all, gates, workspace, T, R, H, stream, true);
 }
 
 extern "C" int dtc_lstm_bwd(const float* dhs, const float* hs_all, const float* cs_all, const float* gates, const float* W_hh,

@@ -278,6 +278,8 @@ _SIGS = {
     "dtc_lstm_workspace": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "dtc_lstm_fwd": (C.c_int, [c_f32p] * 8 + [C.c_void_p, C.c_int, C.c_int, C.c_int, c_stream]),
     "dtc_lstm_bwd": (C.c_int, [c_f32p] * 10 + [C.c_void_p, C.c_int, C.c_int, C.c_int, c_stream]),
+    "dtc_lstm_step_fwd": (C.c_int, [c_f32p] * 8 + [C.c_int, C.c_int, c_stream]),
+    "dtc_lstm_fwd_fused": (C.c_int, [c_f32p] * 8 + [C.c_void_p, C.c_int, C.c_int, C.c_int, c_stream]),
     "dtc_prof_enable": (None, [C.c_int]),
     "dtc_prof_reset": (None, []),
     "dtc_prof_report": (C.c_int, [C.POINTER(DtcProfRec), C.c_int]),

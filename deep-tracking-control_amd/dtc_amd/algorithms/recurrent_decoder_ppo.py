@@ -11,6 +11,10 @@ of ppo.py:189-338 (SURVEY.md §8a "Config 5"):
      fans out to z, mu[:, :3] and l_t -> CE-net / terrain encoder backward -> clip + Adam.
 Hidden states are recorded BEFORE each rollout step (the convention of the commented lines ppo.py:138-139) and the
 mini-batch takes the states at its trajectory starts, as `reccurent_mini_batch_generator` does.
+LSTM and stacked memories (`rnn_type='lstm'`, `rnn_num_layers > 1`) run the fp32 schedule above layer by layer: layer 0
+projects the composite features, layer k > 0 the valid rows of layer k-1's outputs; LSTM recurrences go forward through
+dtc_lstm_fwd_fused (one fused launch per time step) and back through dtc_lstm_bwd, BPTT runs top-down, and layer 0's dgi
+feeds the encoders as the 1-layer GRU's does.  The operand-image schedule serves the 1-layer GRU with H % 128 == 0 only.
 Same constructor keywords / method names as `PPO`; weight gradients run on the side stream (see PPO._bwd).
 """
 from __future__ import annotations
@@ -41,7 +45,7 @@ class RecurrentDecoderPPO(PPO):
         ac = self.actor_critic
         ac.ensure_arena()
         ac._ensure_hidden(obs.shape[0], obs.device)
-        hidden = tuple(h.clone() for h in ac.get_hidden_states())          # state BEFORE this step
+        hidden = tuple(m.clone_hidden(h) for m, h in zip((ac.memory_a, ac.memory_c), ac.get_hidden_states()))   # state BEFORE this step
         actions = super().act(obs, privileged_obs, obs_history, base_vel, rew_buf)
         self.transition.hidden_states = hidden
         return actions
@@ -49,7 +53,7 @@ class RecurrentDecoderPPO(PPO):
     def compute_returns(self, last_critic_obs, last_critic_privileged_obs, last_base_vel):
         self._require_gpu()
         ac = self.actor_critic
-        keep = ac.memory_c.hidden_states.clone() if ac.memory_c.hidden_states is not None else None
+        keep = ac.memory_c.clone_hidden(ac.memory_c.hidden_states)
         last_values = ac.evaluate(last_critic_obs, last_critic_privileged_obs, last_base_vel).detach()
         ac.memory_c.hidden_states = keep            # the bootstrap value must not advance the critic's state
         self.storage.compute_returns(last_values, self.gamma, self.lam)
@@ -57,12 +61,19 @@ class RecurrentDecoderPPO(PPO):
     # ---------------------------------------------------------------- recurrent mini-batches as index data
     def recurrent_slices(self, hid_a=None, hid_c=None):
         """Yield, per mini-batch of envs [a, b): time-major flat row indices of its samples, the padded-layout
-        row of each sample (`unpad_idx`), T, n_traj and the hidden states at the trajectory starts."""
+        row of each sample (`unpad_idx`), T, n_traj and the hidden states at the trajectory starts.
+        hid_a / hid_c: saved states [T, L, N, H], or a tuple (h, c) of two such for an LSTM (default: the storage's).  The
+        states at the trajectory starts are [R, H] for a 1-layer GRU (layer 0), else [L, R, H] (a pair of them for an LSTM).
+        For an LSTM the critic receives the ACTOR's saved states, as the storage's recurrent generator hands them out
+        (`lstm_critic_states`, rollout_storage.py:261-262)."""
         st = self.storage
         T, N = st.num_transitions_per_env, st.num_envs
         dev = st.dones.device
-        hid_a = st.saved_hidden_states_a[0] if hid_a is None else hid_a
-        hid_c = st.saved_hidden_states_c[0] if hid_c is None else hid_c
+        as_list = lambda h: list(h) if isinstance(h, (tuple, list)) else [h]
+        hid_a = as_list(st.saved_hidden_states_a if hid_a is None else hid_a)
+        hid_c = as_list(st.saved_hidden_states_c if hid_c is None else hid_c)
+        plain = len(hid_a) == 1 and hid_a[0].shape[1] == 1
+        actor_states_for_critic = len(hid_a) > 1 and getattr(st, "lstm_critic_states", "reference") == "reference"
         mb = N // self.num_mini_batches
         _, masks_all = split_and_pad_trajectories(st.dones, st.dones)
         dones = st.dones.squeeze(-1)
@@ -82,8 +93,14 @@ class RecurrentDecoderPPO(PPO):
             idx = (torch.arange(T, device=dev).unsqueeze(1) * N + torch.arange(a, b, device=dev)).reshape(-1).contiguous()
             starts = true_indices(lwd[:, a:b].permute(1, 0), R)      # (env, t) of every trajectory start, env-major; count known
             s_env, s_t = a + starts // T, starts % T
-            pick = lambda h: h[s_t, 0, s_env].contiguous()           # [R, H]: layer 0's saved state at every trajectory start
-            yield dict(a=a, b=b, idx=idx, unpad_idx=unpad_idx, T=T, R=R, hid_a=pick(hid_a), hid_c=pick(hid_c))
+            if plain:
+                pick = lambda hs: hs[0][s_t, 0, s_env].contiguous()      # [R, H]: layer 0's saved state at every trajectory start
+            else:
+                pick1 = lambda h: h[s_t, :, s_env].transpose(0, 1).contiguous()          # [L, R, H]
+                pick = lambda hs: pick1(hs[0]) if len(hs) == 1 else tuple(pick1(h) for h in hs)
+            ha = pick(hid_a)
+            hc = ha if actor_states_for_critic else pick(hid_c)
+            yield dict(a=a, b=b, idx=idx, unpad_idx=unpad_idx, T=T, R=R, hid_a=ha, hid_c=hc)
             first = last
 
     # ---------------------------------------------------------------- policy step with BPTT
@@ -94,8 +111,13 @@ class RecurrentDecoderPPO(PPO):
             t = tw._g[key] = torch.zeros(rows, width, dtype=torch.float32, device=tw._dev)
         return t
 
+    def _memory_images(self):
+        """The operand-image schedule of the policy step is built for 1-layer GRU memories with H % 128 == 0."""
+        ac = self.actor_critic
+        return (all(m.kind == 'gru' and m.num_layers == 1 for m in (ac.memory_a, ac.memory_c)) and ac.rnn_hidden_size % 128 == 0)
+
     def _ppo_step_recurrent(self, fw, tw, flat, bt, eps, stats, cfg):
-        if self._image_mode(fw):
+        if self._image_mode(fw) and self._memory_images():
             # every GEMM outside the GRU time steps on operand images (dtc_amd/h2i.py), as in PPO._ppo_step
             tw.narrow_wgrad = True
             wset = self._wset("ppo_recurrent")
@@ -124,24 +146,39 @@ class RecurrentDecoderPPO(PPO):
         Xa = ac.actor_input(fw, flat["observations"], idx)
         Xc = ac.critic_input(flat["observations"], flat["base_vel"], flat["privileged_observations"], idx)
 
-        def head_forward(name, X, mem, proj, layers, h0):
-            gi_v = tw.g("gi_" + name, 3 * H)
-            ops.linear_fwd(X, proj.W, proj.b, gi_v, None, M=M)
-            gi_p = self._padded(tw, "gi_" + name, T * R, 3 * H)     # padded steps keep finite stale values (never used)
-            ops.scatter_rows(gi_v, unpad_idx, gi_p)
-            hs_all = torch.empty(T + 1, R, H, device=dev)
-            gates, hn = torch.empty(T, R, 3 * H, device=dev), torch.empty(T, R, H, device=dev)
-            ws = ops.workspace(ops.gru_workspace_bytes(T, R, H), dev)
-            ops.gru_fwd(gi_p.view(T, R, 3 * H), h0.contiguous(), mem.W_hh, mem.b_hh, hs_all, gates, hn, ws)
-            X0 = segmat([seg(hs_all[1:].reshape(T * R, H), 0, H, gather=True)], unpad_idx)
-            outs, cur = [], X0
+        def head_forward(name, X, mem, proj, layers, hid):
+            """Every layer of the memory (layer 0 projects the features X, layer k > 0 the valid rows of layer k-1's outputs),
+            then the MLP head on the valid rows of the top layer's outputs."""
+            G = mem.G
+            h0, c0 = mem._split(hid)
+            recs, cur = [], X
+            for l in range(mem.num_layers):
+                key = name if l == 0 else f"{name}{l}"
+                lin = proj if l == 0 else Dense(mem.Wih[l], mem.bih[l], mem.gWih[l], mem.gbih[l], None)
+                gi_v = tw.g("gi_" + key, G * H)
+                ops.linear_fwd(cur, lin.W, lin.b, gi_v, None, M=M)
+                gi_p = self._padded(tw, "gi_" + key, T * R, G * H)     # padded steps keep finite stale values (never used)
+                ops.scatter_rows(gi_v, unpad_idx, gi_p)
+                hs_all = torch.empty(T + 1, R, H, device=dev)
+                rec = dict(X=cur, lin=lin, hs_all=hs_all, gates=torch.empty(T, R, G * H, device=dev))
+                if mem.kind == 'gru':
+                    rec.update(hn=torch.empty(T, R, H, device=dev), ws=ops.workspace(ops.gru_workspace_bytes(T, R, H), dev))
+                    ops.gru_fwd(gi_p.view(T, R, 3 * H), h0[l].contiguous(), mem.Whh[l], mem.bhh[l], hs_all, rec["gates"], rec["hn"],
+                                rec["ws"])
+                else:
+                    rec.update(cs_all=torch.empty(T + 1, R, H, device=dev), ws=ops.workspace(ops.lstm_workspace_bytes(T, R, H), dev))
+                    ops.lstm_fwd_fused(gi_p.view(T, R, 4 * H), h0[l].contiguous(), c0[l].contiguous(), mem.Whh[l], mem.bhh[l], hs_all,
+                                       rec["cs_all"], rec["gates"], rec["ws"])
+                recs.append(rec)
+                cur = segmat([seg(hs_all[1:].reshape(T * R, H), 0, H, gather=True)], unpad_idx)
+            X0 = cur
+            outs = []
             for li, L in enumerate(layers):
                 o = tw.g(f"{name}_o{li}", L.n_out)
                 ops.linear_fwd(cur, L.W, L.b, o, L.act, M=M)
                 outs.append(o)
                 cur = o
-            return dict(name=name, X=X, mem=mem, proj=proj, layers=layers, hs_all=hs_all, gates=gates, hn=hn, ws=ws,
-                        X0=X0, outs=outs)
+            return dict(name=name, X=X, mem=mem, proj=proj, layers=layers, recs=recs, X0=X0, outs=outs)
 
         def head_backward(hd, dOut):
             name, layers, outs = hd["name"], hd["layers"], hd["outs"]
@@ -153,14 +190,26 @@ class RecurrentDecoderPPO(PPO):
                 else:
                     self._bwd(tw, layers[li], dZ, hd["X0"], dX, None, None)
                 dZ = dX
-            dhs = self._padded(tw, "dhs_" + name, T * R, H)
-            dhs.zero_()
-            ops.scatter_rows(dZ, unpad_idx, dhs)
-            dgi_p, dh0 = torch.empty(T, R, 3 * H, device=dev), torch.empty(R, H, device=dev)
+            # BPTT top-down; returns layer 0's dgi over the valid rows (the caller runs its input projection's backward)
             mem = hd["mem"]
-            ops.gru_bwd(dhs.view(T, R, H), hd["hs_all"], hd["gates"], hd["hn"], mem.W_hh, dgi_p, mem.gW_hh, mem.gb_hh,
-                        dh0, hd["ws"], rows=unpad_idx)          # the W_hh weight gradient skips the padding slots
-            return ops.gather_rows(dgi_p.view(T * R, 3 * H), unpad_idx, out=tw.g("dgi_" + name, 3 * H))
+            G = mem.G
+            for l in range(mem.num_layers - 1, -1, -1):
+                rec, key = hd["recs"][l], (name if l == 0 else f"{name}{l}")
+                dhs = self._padded(tw, "dhs_" + key, T * R, H)
+                dhs.zero_()
+                ops.scatter_rows(dZ, unpad_idx, dhs)
+                dgi_p, dh0 = torch.empty(T, R, G * H, device=dev), torch.empty(R, H, device=dev)
+                if mem.kind == 'gru':
+                    ops.gru_bwd(dhs.view(T, R, H), rec["hs_all"], rec["gates"], rec["hn"], mem.Whh[l], dgi_p, mem.gWhh[l], mem.gbhh[l],
+                                dh0, rec["ws"], rows=unpad_idx)          # the W_hh weight gradient skips the padding slots
+                else:
+                    ops.lstm_bwd(dhs.view(T, R, H), rec["hs_all"], rec["cs_all"], rec["gates"], mem.Whh[l], dgi_p, mem.gWhh[l],
+                                 mem.gbhh[l], dh0, torch.empty(R, H, device=dev), rec["ws"])
+                dgi = ops.gather_rows(dgi_p.view(T * R, G * H), unpad_idx, out=tw.g("dgi_" + key, G * H))
+                if l == 0:
+                    return dgi
+                dZ = tw.g(f"dx_{key}", H)                 # gradient w.r.t. layer l-1's outputs (valid rows)
+                self._bwd(tw, rec["lin"], dgi, rec["X"], dZ, None, None)
 
         with tw.lane("aux"):
             hc = head_forward("c", Xc, ac.memory_c, ac.proj_c, ac.Cr, bt["hid_c"])

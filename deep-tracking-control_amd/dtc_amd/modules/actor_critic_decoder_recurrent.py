@@ -7,13 +7,17 @@ builders unchanged (actor_critic_decoder.py:409-437, 540-551)
     critic features = cat[obs, base_vel, priv[:, 693:696], priv[:, 696:]]   (752)
 
 feeding the reference's recurrent head (actor_critic_recurrent.py:40-116): `Memory(584 -> 512, gru)` -> actor
-MLP(512 -> 512 -> 256 -> 128 -> 12) and `Memory(752 -> 512, gru)` -> critic MLP(512 -> ... -> 1).
+MLP(512 -> 512 -> 256 -> 128 -> 12) and `Memory(752 -> 512, gru)` -> critic MLP(512 -> ... -> 1).  The memories take the
+reference's recurrence options as `Memory` does: `rnn_type` 'gru' or 'lstm', any `rnn_num_layers` >= 1 and `rnn_hidden_size`
+(AC_Args, actor_critic_decoder.py:85-88, names a 2-layer memory of 50 units); hidden states as torch holds them
+([L, N, H], or (h, c) for an LSTM).
 Parameter / `state_dict()` names: `vae.*` as ActorCriticDecoder, `std`, `actor.*`, `critic.*`, `memory_a.rnn.*`,
 `memory_c.rnn.*` as ActorCriticRecurrent.  Parameters live in the same flat arena as ActorCriticDecoder (main
 optimiser range = heads + shared encoders, VAE optimiser range = the whole `vae`).
 
-Compute: CE-net / terrain encoders on the valid rows (dtc_linear_* with the mini-batch gather folded in), GRU
-input projection on the valid rows (the four feature blocks are never concatenated), recurrence = dtc_gru_fwd.
+Compute: CE-net / terrain encoders on the valid rows (dtc_linear_* with the mini-batch gather folded in), layer 0's
+input projection on the valid rows (the four feature blocks are never concatenated), recurrence = dtc_gru_fwd or, for an
+LSTM, one fused dtc_lstm_step_fwd per rollout step (dtc_lstm_fwd_fused in the trainer).
 Training (BPTT + the VAE step) is driven by dtc_amd.algorithms.RecurrentDecoderPPO.  GPU only.
 """
 from __future__ import annotations
@@ -36,9 +40,6 @@ class ActorCriticDecoderRecurrent(ActorCriticDecoder):
             print("ActorCriticDecoderRecurrent.__init__ got unexpected arguments, which will be ignored: "
                   + str([key for key in kwargs.keys()]))
         nn.Module.__init__(self)
-        if rnn_type.lower() != 'gru' or rnn_num_layers != 1:
-            raise NotImplementedError("the composite model of BASELINE.json configs[4] is built for a 1-layer GRU "
-                                      "(ActorCriticRecurrent / Memory take 'lstm' and deeper stacks)")
         if activation not in ("elu", "relu"):
             raise NotImplementedError("the HIP layers implement 'elu' and 'relu'")
         A = AC_Args
@@ -68,7 +69,7 @@ class ActorCriticDecoderRecurrent(ActorCriticDecoder):
         self.Cr = [ar.dense(f"critic.{2 * i}.weight", f"critic.{2 * i}.bias", act if i < n_c - 1 else None) for i in range(n_c)]
         self.memory_a.bind(ar, "memory_a")
         self.memory_c.bind(ar, "memory_c")
-        # the GRU input projections as dense layers (no activation): gi = X W_ih^T + b_ih
+        # layer 0's input projections as dense layers (no activation): gi = X W_ih^T + b_ih
         mk = lambda m: Dense(m.W_ih, m.b_ih, m.gW_ih, m.gb_ih, None)
         self.proj_a, self.proj_c = mk(self.memory_a), mk(self.memory_c)
 
@@ -83,18 +84,43 @@ class ActorCriticDecoderRecurrent(ActorCriticDecoder):
     def _ensure_hidden(self, N, dev):
         for m in (self.memory_a, self.memory_c):
             if m.hidden_states is None:
-                m.hidden_states = torch.zeros(1, N, self.rnn_hidden_size, device=dev)
+                m.hidden_states = m.init_hidden(N, dev)
 
     def _step_memory(self, mem, proj, X, N, dev):
-        """One recurrent step over N envs: gi = X W_ih^T + b_ih, GRU cell, state advanced in place."""
-        H = self.rnn_hidden_size
-        gi = torch.empty(1, N, 3 * H, device=dev)
-        ops.linear_fwd(X, proj.W, proj.b, gi.view(N, 3 * H), None, M=N)
-        hs_all, gates, hn = torch.empty(2, N, H, device=dev), torch.empty(1, N, 3 * H, device=dev), torch.empty(1, N, H, device=dev)
-        ws = ops.workspace(ops.gru_workspace_bytes(1, N, H), dev)
-        ops.gru_fwd(gi, mem.hidden_states[0].contiguous(), mem.W_hh, mem.b_hh, hs_all, gates, hn, ws)
-        mem.hidden_states = hs_all[1:2].clone()
-        return mem.hidden_states[0]
+        """One recurrent step over N envs through every layer (layer 0 reads X through `proj`, layer k > 0 the new h of layer
+        k - 1): gi = X W_ih^T + b_ih, then the GRU cell (dtc_gru_fwd, T = 1) or the LSTM cell (dtc_lstm_step_fwd; H % 32 != 0:
+        dtc_lstm_fwd, T = 1).  The state is replaced by fresh tensors ([L, N, H], or (h, c) for an LSTM); returns the top h."""
+        H, G = self.rnn_hidden_size, mem.G
+        h0, c0 = mem._split(mem.hidden_states)
+        hs, cs, cur = [], [], X
+        for l in range(mem.num_layers):
+            gi = torch.empty(1, N, G * H, device=dev)
+            if l == 0:
+                ops.linear_fwd(cur, proj.W, proj.b, gi.view(N, G * H), None, M=N)
+            else:
+                ops.linear_fwd(cur, mem.Wih[l], mem.bih[l], gi.view(N, G * H), None, M=N)
+            if mem.kind == 'gru':
+                hs_all, gates, hn = torch.empty(2, N, H, device=dev), torch.empty(1, N, 3 * H, device=dev), torch.empty(1, N, H, device=dev)
+                ws = ops.workspace(ops.gru_workspace_bytes(1, N, H), dev)
+                ops.gru_fwd(gi, h0[l].contiguous(), mem.Whh[l], mem.bhh[l], hs_all, gates, hn, ws)
+                h = hs_all[1]
+            else:
+                h, c, gates = torch.empty(N, H, device=dev), torch.empty(N, H, device=dev), torch.empty(N, 4 * H, device=dev)
+                if H % 32 == 0:
+                    ops.lstm_step_fwd(h0[l].contiguous(), c0[l].contiguous(), mem.Whh[l], mem.bhh[l], gi.view(N, 4 * H), h, c, gates)
+                else:
+                    hs_all, cs_all = torch.empty(2, N, H, device=dev), torch.empty(2, N, H, device=dev)
+                    ws = ops.workspace(ops.lstm_workspace_bytes(1, N, H), dev)
+                    ops.lstm_fwd(gi, h0[l].contiguous(), c0[l].contiguous(), mem.Whh[l], mem.bhh[l], hs_all, cs_all, gates.view(1, N, 4 * H), ws)
+                    h, c = hs_all[1], cs_all[1]
+                cs.append(c)
+            hs.append(h)
+            cur = h
+        if mem.kind == 'gru':
+            mem.hidden_states = hs_all[1:2].clone() if mem.num_layers == 1 else torch.stack(hs)
+        else:
+            mem.hidden_states = (torch.stack(hs), torch.stack(cs))
+        return cur
 
     def _mlp(self, layers, X, M, dev):
         cur = X

@@ -818,6 +818,20 @@ def lstm_fwd(gi, h0, c0, W_hh, b_hh, hs_all, cs_all, gates, ws):
                              cptr(cs_all, f32), cptr(gates, f32), ptr(ws), T, R, H4 // 4, stream()), "dtc_lstm_fwd")
 
 
+def lstm_fwd_fused(gi, h0, c0, W_hh, b_hh, hs_all, cs_all, gates, ws):
+    """lstm_fwd with one fused launch per time step (dtc_lstm_step_fwd; H % 32 != 0: the GEMM + gate-kernel pair)."""
+    T, R, H4 = gi.shape
+    check(lib().dtc_lstm_fwd_fused(cptr(gi, f32), cptr(h0, f32), cptr(c0, f32), cptr(W_hh, f32), cptr(b_hh, f32), cptr(hs_all, f32),
+                                   cptr(cs_all, f32), cptr(gates, f32), ptr(ws), T, R, H4 // 4, stream()), "dtc_lstm_fwd_fused")
+
+
+def lstm_step_fwd(hprev, cprev, W_hh, b_hh, gi_t, hout, cout, gates_t):
+    """One fused LSTM time step: gi_t [R,4H], hprev / cprev [R,H] -> hout / cout [R,H], gates_t [R,4H] (i, f, g, o).  H % 32 == 0."""
+    R, H4 = gi_t.shape
+    check(lib().dtc_lstm_step_fwd(cptr(hprev, f32), cptr(cprev, f32), cptr(W_hh, f32), cptr(b_hh, f32), cptr(gi_t, f32), cptr(hout, f32),
+                                  cptr(cout, f32), cptr(gates_t, f32), R, H4 // 4, stream()), "dtc_lstm_step_fwd")
+
+
 def lstm_bwd(dhs, hs_all, cs_all, gates, W_hh, dgi, dW_hh, db_hh, dh0, dc0, ws):
     T, R, H = dhs.shape
     check(lib().dtc_lstm_bwd(cptr(dhs, f32), cptr(hs_all, f32), cptr(cs_all, f32), cptr(gates, f32), cptr(W_hh, f32),

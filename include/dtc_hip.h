@@ -712,6 +712,17 @@ int dtc_gru_bwd_multi(const DtcGruBwdItem* items, int count, int T, int R, int H
 int64_t dtc_lstm_workspace(int T, int R, int H);
 int dtc_lstm_fwd(const float* gi, const float* h0, const float* c0, const float* W_hh /*[4H,H]*/, const float* b_hh,
                  float* hs_all, float* cs_all, float* gates, void* workspace, int T, int R, int H, void* stream);
+/* One fused LSTM time step (forward), replacing one time step of torch.nn.LSTM inside `Memory` (actor_critic_recurrent.py:92-116,
+ * `rnn_type = 'gru'#lstm` / `rnn_num_layers = 2` of AC_Args, actor_critic_decoder.py:85-88): the recurrent GEMM a = gi_t + hprev
+ * W_hh^T + b_hh with the gate math above in its epilogue (a never reaches HBM).  A workgroup's column tile holds all four gate
+ * blocks of 32 hidden units (rows j, H+j, 2H+j, 3H+j of W_hh, read in place).  hout / cout [R,H], gates_t [R,4H] = (i | f | g | o),
+ * as one time step of dtc_lstm_fwd writes them.  H % 32 == 0; hout / cout must not alias hprev / cprev. */
+int dtc_lstm_step_fwd(const float* hprev /*[R,H]*/, const float* cprev /*[R,H]*/, const float* W_hh /*[4H,H]*/, const float* b_hh,
+                      const float* gi_t /*[R,4H]*/, float* hout, float* cout, float* gates_t, int R, int H, void* stream);
+/* dtc_lstm_fwd with ONE dtc_lstm_step_fwd launch per time step (same arguments and outputs; results within fp32 rounding of
+ * dtc_lstm_fwd's: another summation order of the same products).  H % 32 != 0: dtc_lstm_fwd's GEMM + gate-kernel pair. */
+int dtc_lstm_fwd_fused(const float* gi, const float* h0, const float* c0, const float* W_hh /*[4H,H]*/, const float* b_hh,
+                       float* hs_all, float* cs_all, float* gates, void* workspace, int T, int R, int H, void* stream);
 /* BPTT.  dhs [T,R,H] = gradient w.r.t. the outputs h_1..h_T (the final states carry no gradient).  Produces dgi [T,R,4H]
  * (gradient w.r.t. the gate pre-activations: feed it to dtc_linear_wgrad with x for W_ih / b_ih and to dtc_linear_dgrad
  * for the layer below), dW_hh [4H,H], db_hh [4H], dh0 and dc0 [R,H]. */
