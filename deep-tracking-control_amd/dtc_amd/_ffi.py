@@ -114,6 +114,35 @@ class DtcEnvStep(C.Structure):
                                            "heights")])
 
 
+REWARD_TERMS = 34
+
+
+class DtcRewardCfg(C.Structure):
+    """include/dtc_hip.h: the scales and settings of dtc_env_rewards; field order as there."""
+    _fields_ = ([("scale", C.c_float * REWARD_TERMS), ("row", C.c_int32 * REWARD_TERMS)] +
+                [(k, C.c_float) for k in ("dt", "tracking_sigma", "soft_dof_vel_limit", "soft_torque_limit", "base_height_target",
+                                          "max_contact_force", "max_acc", "lin_vel_x_max", "ang_vel_yaw_max")] +
+                [(k, C.c_int32) for k in ("only_positive_rewards", "num_dof", "n_penalised", "n_hip")] +
+                [("feet", C.c_int32 * 4), ("penalised", C.c_int32 * 32), ("hip", C.c_int32 * 16), ("num_points", C.c_int32),
+                 ("plane", C.c_void_p)])
+
+
+class DtcRewardStep(C.Structure):
+    """include/dtc_hip.h: the buffers of one dtc_env_rewards call (device pointers); field order as there."""
+    _fields_ = ([(k, C.c_void_p) for k in ("root_states", "base_lin_vel", "base_ang_vel", "projected_gravity", "commands", "dof_pos",
+                                           "default_dof_pos", "dof_vel", "last_dof_vel", "torques", "actions", "last_actions",
+                                           "last_actions_2", "contact_forces", "foot_positions", "foot_velocities",
+                                           "last_foot_velocities", "optimal_footholds_world", "contact_filt", "measured_heights",
+                                           "reset_buf", "time_out_buf", "robot_mass", "terrain_levels", "dof_pos_limits",
+                                           "dof_vel_limits", "torque_limits", "cmd_buffer", "lin_vel_buffer", "ang_vel_buffer",
+                                           "height_samples")] +
+                [("rows", C.c_int32), ("cols", C.c_int32), ("border_size", C.c_float), ("horizontal_scale", C.c_float),
+                 ("vertical_scale", C.c_float)] +
+                [(k, C.c_void_p) for k in ("foot_clearance", "feet_air_time", "last_contacts", "stumble", "pitch_est", "rew_buf",
+                                           "episode_sums", "per_term")] +
+                [("num_bodies", C.c_int32), ("num_commands", C.c_int32)])
+
+
 class DtcRowCopy(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("src_stride_bytes", C.c_int64), ("width_bytes", C.c_int32)]
 
@@ -147,6 +176,7 @@ _SIGS = {
     "dtc_compute_observations_where": (C.c_int, [c_f32p] * 11 + [C.c_int64] + [c_f32p] * 4 + [C.POINTER(DtcObsCfg)] +
                                        [c_f32p] * 3 + [c_u8p, C.c_int, c_stream]),
     "dtc_env_post_physics": (C.c_int, [C.POINTER(DtcEnvStep), C.POINTER(DtcGridCfg), C.POINTER(DtcObsCfg), C.c_int, c_stream]),
+    "dtc_env_rewards": (C.c_int, [C.POINTER(DtcRewardStep), C.POINTER(DtcRewardCfg), C.c_int, c_stream]),
     "dtc_check_termination": (C.c_int, [c_f32p, C.c_int, c_i32p, C.c_int, c_i64p, C.c_int64, c_f32p, c_f32p, c_f32p,
                                         C.POINTER(DtcObsCfg), c_u8p, c_u8p, c_f32p, C.c_int, c_stream]),
     "dtc_store_transition": (C.c_int, [C.POINTER(DtcRowCopy), C.c_int, c_f32p, c_f32p, c_u8p, C.c_float, c_f32p,

@@ -182,6 +182,87 @@ typedef struct DtcEnvStep {
 } DtcEnvStep;
 int dtc_env_post_physics(const DtcEnvStep* st, const DtcGridCfg* grid, const DtcObsCfg* obs, int N, void* stream);
 
+/* ---- env rewards: LeggedRobot.compute_reward, legged_gym/envs/base/legged_robot.py:274-291 ----------------------------------
+ * Every `_reward_*` term of LeggedRobotDTC (legged_robot.py:1321-1622, legged_robot_dtc.py:522-586) in ONE launch, accumulated in
+ * the reference's order: rew_buf = 0; for each active term but termination, in alphabetical order (the order class_to_dict gives
+ * the scales, legged_robot.py:929-952 / utils/helpers.py:11-26): r = term * scale, rew_buf += r, episode_sums[term] += r; clip
+ * rew_buf at 0 if only_positive_rewards; then the termination term.  The state the reference's terms change is updated in the same
+ * order: feet_air_time / last_contacts (_reward_feet_air_time, :1386-1412 -- feet_slip and foot_acc after it see the new
+ * last_contacts), the 5-step stumble history of _reward_foot_clearance (:1474-1492) and pitch_est (_reward_orientation,
+ * _reward_orientation_roll, :1559-1596; updated twice when both are on).  Term indices are the DTC_REW_* below. */
+#define DTC_REWARD_TERMS 34
+enum {
+    DTC_REW_ACTION_RATE, DTC_REW_ANG_VEL_XY, DTC_REW_BASE_HEIGHT, DTC_REW_BIG_PITCH, DTC_REW_COLLISION, DTC_REW_DOF_ACC,
+    DTC_REW_DOF_POS_LIMITS, DTC_REW_DOF_VEL, DTC_REW_DOF_VEL_LIMITS, DTC_REW_FEET_AIR_TIME, DTC_REW_FEET_CONTACT_FORCES,
+    DTC_REW_FEET_SLIP, DTC_REW_FEET_STUMBLE, DTC_REW_FOOT_ACC, DTC_REW_FOOT_CLEARANCE, DTC_REW_FOOTHOLD_MISS, DTC_REW_HIP_POS,
+    DTC_REW_LIN_VEL_Z, DTC_REW_ORIENTATION, DTC_REW_ORIENTATION_ROLL, DTC_REW_POS_ACC, DTC_REW_POWER, DTC_REW_POWERCHANGE,
+    DTC_REW_SMOOTH, DTC_REW_SOFT_TRACKING_ANG_VEL, DTC_REW_SOFT_TRACKING_LIN_VEL, DTC_REW_STAND_STILL, DTC_REW_STUMBLE,
+    DTC_REW_TERMINATION, DTC_REW_TORQUE_LIMITS, DTC_REW_TORQUES, DTC_REW_TRACKING_ANG_VEL, DTC_REW_TRACKING_LIN_VEL,
+    DTC_REW_TRACKING_OPTIMAL_FOOTHOLDS
+};
+
+typedef struct DtcRewardCfg {
+    float scale[DTC_REWARD_TERMS];  /* float32(scale * dt), dt = sim.dt * decimation in double (legged_robot.py:929-938); 0 = off */
+    int32_t row[DTC_REWARD_TERMS];  /* row of the term in episode_sums / per_term (its rank in the scales dict), -1 = off          */
+    float dt;                       /* cfg.sim.dt * cfg.control.decimation: dof_acc, foot_acc divide by it, feet_air_time adds it   */
+    float tracking_sigma;           /* cfg.rewards.tracking_sigma (legged_robot_config.py:174)                                      */
+    float soft_dof_vel_limit, soft_torque_limit;    /* cfg.rewards (legged_robot.py:1364-1371)                                     */
+    float base_height_target;       /* cfg.rewards.base_height_target (legged_robot_dtc.py:531-534)                                 */
+    float max_contact_force;        /* cfg.rewards.max_contact_force (legged_robot.py:1426-1428)                                    */
+    float max_acc;                  /* cfg.rewards.max_acc (legged_robot.py:1525-1531)                                              */
+    float lin_vel_x_max, ang_vel_yaw_max;   /* command_ranges["lin_vel_x"][1], ["ang_vel_yaw"][1] (:1373-1378, dtc.py:542-568) */
+    int32_t only_positive_rewards;  /* cfg.rewards.only_positive_rewards (legged_robot.py:284-285)                                  */
+    int32_t num_dof;                /* 12 (<= 64)                                                                                   */
+    int32_t n_penalised, n_hip;     /* lengths of the two index lists below                                                         */
+    int32_t feet[4];                /* self.feet_indices: bodies of contact_forces (legged_robot.py:1183)                           */
+    int32_t penalised[32];          /* self.penalised_contact_indices: bodies (:1187)                                               */
+    int32_t hip[16];                /* self.hip_indices: columns of dof_pos (:1108-1111, :1504-1505)                                */
+    int32_t num_points;             /* 693: columns of measured_heights                                                             */
+    const float* plane;             /* DEVICE [2, num_points]: rows 0, 1 of (A^T A)^-1 A^T, A = [x, y, 1] over height_points -- the
+                                       constant part of get_plane_norm's batched least squares (:1535-1557); fp32 of float64     */
+} DtcRewardCfg;
+
+typedef struct DtcRewardStep {
+    /* inputs (device; shapes and dtypes of the reference's attributes; N envs, D dofs, B bodies, C = num_commands) */
+    const float *root_states;                         /* [N,13]                                                                */
+    const float *base_lin_vel, *base_ang_vel, *projected_gravity;    /* [N,3]                                                   */
+    const float *commands;                            /* [N,C], C >= 3                                                          */
+    const float *dof_pos, *default_dof_pos;           /* [N,D], [D]                                                             */
+    const float *dof_vel, *last_dof_vel, *torques, *actions, *last_actions, *last_actions_2;   /* [N,D]                        */
+    const float *contact_forces;                      /* [N,B,3]                                                                */
+    const float *foot_positions, *foot_velocities, *last_foot_velocities, *optimal_footholds_world;   /* [N,4,3]              */
+    const uint8_t *contact_filt;                      /* [N,4] bool: set by _post_physics_step_callback (:561-564)              */
+    const float *measured_heights;                    /* [N,num_points]                                                         */
+    const uint8_t *reset_buf, *time_out_buf;          /* [N] bool                                                               */
+    const float *robot_mass;                          /* [N]                                                                    */
+    const int64_t *terrain_levels;                    /* [N]                                                                    */
+    const float *dof_pos_limits;                      /* [D,2]                                                                  */
+    const float *dof_vel_limits, *torque_limits;      /* [D]                                                                    */
+    /* ring buffers, time-major as the reference holds them (legged_robot.py:844-846) */
+    const float *cmd_buffer;                          /* [10,N,C]                                                               */
+    const float *lin_vel_buffer;                      /* [10,N,2]                                                               */
+    const float *ang_vel_buffer;                      /* [10,N,1]                                                               */
+    /* foot clearance (_get_foot_clearance, :1443-1472): from the int16 height table when height_samples != NULL (then written to
+       foot_clearance if that is not NULL), else read from foot_clearance = the env's measured_foot_clearance [N,4] */
+    const int16_t *height_samples;
+    int32_t rows, cols;
+    float border_size, horizontal_scale, vertical_scale;
+    float *foot_clearance;
+    /* state, read and written */
+    float *feet_air_time;                             /* [N,4]                                                                  */
+    uint8_t *last_contacts;                           /* [N,4] bool: as the env holds it after the callback; written only when
+                                                         feet_air_time is on (the reference rebinds it there)                    */
+    uint8_t *stumble;                                 /* [N,4]: bit k = the stumble mask pushed k steps ago (the 5-list of :1485) */
+    float *pitch_est;                                 /* [N]                                                                    */
+    /* outputs */
+    float *rew_buf;                                   /* [N]                                                                    */
+    float *episode_sums;                              /* [n_active, N], row DtcRewardCfg.row[term]: accumulated                 */
+    float *per_term;                                  /* [n_active, N] term * scale, or NULL                                    */
+    int32_t num_bodies, num_commands;
+} DtcRewardStep;
+/* One launch for all N envs.  Pointers of terms that are off may be NULL.  `st`, `cfg` are HOST pointers. */
+int dtc_env_rewards(const DtcRewardStep* st, const DtcRewardCfg* cfg, int N, void* stream);
+
 /* ---- rollout-side store (row f2) ---------------------------------------------------------
  * RolloutStorage.add_transitions, rsl_rl/rsl_rl/storage/rollout_storage.py:99-116: the 13 `copy_` of one env step as
  * ONE launch (each item: N rows of width_bytes, source row stride src_stride_bytes -- 0 for a broadcast row such as
