@@ -11,8 +11,12 @@ One "step" = one pass of the hot path over one recorded rollout of 4096 envs x 2
 Inputs are resident in HBM before the timed region.  Multi-GPU = data parallel, weak scaling
 (4096 envs per rank, RCCL all-reduce of the two flat gradient buckets + three scalars per step).
 Rank 0 prints ONE JSON line.  N > 1: the headline stays configs[1] PER RANK at every N (the configuration BASELINE.json's
-metric is quoted on: the driver's 1 -> 8 efficiency is then a like-for-like ratio), and the same line carries
-`configs4_composite`: configs[4]'s model (GRU + CE-net + foothold obs) on 4096 x N envs, timed in the same job.
+metric is quoted on: the driver's 1 -> 8 efficiency is then a like-for-like ratio).
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs, the line.  Everything
+else this file measures or checks runs after the timed steps with --full only: GEMM accuracy against fp64 (random and
+in-situ operands), the configs[3] planner line, the serialised per-kernel pass behind `roofline` / `kernel_classes`, the
+rocprofv3 counter passes (child runs of this file), the collective-sequence check, the single-pass fp32 MFMA step, the
+CPU baseline, and at N > 1 `configs4_composite`: configs[4]'s model (GRU + CE-net + foothold obs) on 4096 x N envs.
 Failure is loud: a run that cannot complete (missing GPU, a rank that died, a hung collective, the launcher's SIGTERM) ends
 with ONE JSON line carrying `"error"` and a non-zero exit code within the deadline -- never a silent hang.
 """
@@ -337,16 +341,19 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the two rocprofv3 PMC passes behind roofline.traffic")
-    ap.add_argument("--no-in-situ", action="store_true", help="skip the fp64 check of one step's products on their actual operands")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run every other measurement and check of this "
+                    "file (accuracy, per-kernel and roofline figures, counter passes, CPU baseline, configs[4] at N > 1); a plain "
+                    "run reports the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-traffic", action="store_true", help="--full: skip the rocprofv3 PMC passes behind roofline.traffic / mfma_busy")
+    ap.add_argument("--no-in-situ", action="store_true", help="--full: skip the fp64 check of one step's products on their actual operands")
     ap.add_argument("--workload", default=os.environ.get("DTC_BENCH_WORKLOAD", "decoder"), choices=["decoder", "composite", "gru"],
                     help="decoder = BASELINE configs[1] (the headline, default); composite = configs[4]'s model "
                          "(GRU + CE-net + foothold obs, build-defined); gru = configs[2] (ActorCriticRecurrent, GRU 512, BPTT); "
                          "both on the same rollout shapes -- informative only.  Default from DTC_BENCH_WORKLOAD (a driver that "
                          "cannot pass flags selects configs[4]'s model with DTC_BENCH_WORKLOAD=composite)")
     ap.add_argument("--detail", default=os.environ.get("DTC_BENCH_DETAIL"), help="where the full record (everything the result line leaves "
-                    "out) goes; default gpurun_out/bench_detail.json")
+                    "out) goes; default with --full: DETAIL_PATH; a plain run writes it only to a path given here")
     ap.add_argument("--cpu-baseline-full", action="store_true", help="time the CPU port on the WHOLE workload (no GPU work) and exit")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step computed (planner "
                     "outputs, returns / advantages, the update's losses, the trained parameters) as DIR/<name>.npy, float32 / float64")
@@ -529,6 +536,63 @@ def run(a, rank, local_rank, world, wd):
             rank_ms = [float(x.item()) for x in tl]
         return elapsed, rank_ms, out
 
+    def result_line(**config_extra):
+        """Rank 0's record of the timed region: the headline and what it ran on (--full adds its figures to it)."""
+        value = NUM_ENVS * NUM_STEPS * world * a.steps / elapsed
+        return {
+            "metric": METRIC,
+            "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": elapsed / a.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": ("f32 (emulated: f16x2 split per operand, f32 accumulate)" if (ops.SPLIT and (ops.H2 or getattr(alg, "use_images", False)))
+                      else "f32 (emulated: bf16x3 split per operand, f32 accumulate)" if ops.SPLIT else "f32"),
+            "data": "synthetic",
+            "gemm_arithmetic": ("results, accumulation, narrow layers, losses and optimiser in f32; the operands of the wide layers (>= 128 columns) live "
+                                "in HBM as block-scaled two-term fp16 images (x 2^e = hi + lo: 22 significant bits; e per ROW and block of 128 "
+                                "columns from that block's own largest finite element, weights per 128 x 128 block), 3 fp16 MFMA passes per "
+                                "product (exact in the f32 accumulator; dropped lo lo' = 2^-22 of a product), accumulator rows rescaled exactly "
+                                "at block borders: every row is as accurate relative to ITSELF as an f32 dot product, whatever the other rows "
+                                "hold, and a non-finite element poisons only its own row / column (csrc/h2i_core.hpp).  Measured against fp64 "
+                                "with --full: gemm_accuracy (random operands) and gemm_accuracy_in_situ (the step's real operands).  DTC_H2I=0: "
+                                "round 4's converting kernels (tensor-amax scale); DTC_GEMM_SPLIT=0: single-pass fp32 MFMA everywhere"
+                                if getattr(alg, "use_images", False) and ops.SPLIT else
+                                ("f32 operands and results; wide layers on the fp16 matrix pipe as 2-term splits (x 2^e = hi + lo, e from the "
+                                 "tensor's amax: 22 significant bits, the sums scaled back exactly), 3 MFMA passes, fp32 accumulate -- the error "
+                                 "level of the fp32 MFMA chain, measured with --full against fp64 next to the single-pass fp32 MFMA kernels and "
+                                 "the bf16 x 3 / six-pass kernels (DTC_GEMM_SPLIT=1); DTC_GEMM_SPLIT=0 selects the single-pass kernels everywhere")
+                                if ops.H2 else
+                                ("f32 operands and results; wide layers on the bf16 matrix pipe as 3-term splits (a = a1 + a2 + a3 exactly to 2^-24), "
+                                 "6 MFMA passes, fp32 accumulate -- fp32-level accuracy, measured with --full against fp64 next to the single-pass "
+                                 "fp32 MFMA kernels; DTC_GEMM_SPLIT=0 selects the single-pass kernels everywhere") if ops.SPLIT else
+                                "f32 single-pass v_mfma_f32_32x32x2_f32 (DTC_GEMM_SPLIT=0)"),
+            "config": dict({"workload": ("BASELINE configs[1]: 4096 envs x 24 steps/GPU, ActorCriticDecoder (CE-net + terrain encoder 512 + MLP "
+                                         "heads): planner over 98304 recorded maps + compute_returns + PPO.update (5 epochs x 4 x 24576)")
+                            if not (composite or gru) else
+                            ("BASELINE configs[2]: ActorCriticRecurrent (GRU 512), 4096 envs x 24 steps: planner + compute_returns + "
+                             "RecurrentPPO.update (5 epochs x 4 recurrent mini-batches of 1024 envs x 24 steps, BPTT)") if gru else
+                            ("BASELINE configs[4] model (GRU + CE-net + foothold obs), 4096 envs x 24 steps/GPU: planner + compute_returns + "
+                             "RecurrentDecoderPPO.update (5 epochs x 4 recurrent mini-batches of 1024 envs x 24 steps, BPTT)"),
+                            "num_envs_per_gpu": NUM_ENVS, "num_steps_per_env": NUM_STEPS, "mini_batch": 24576,
+                            "epochs": 5, "wgrad_overlap_stream": bool(overlap),
+                            "headline_at_every_n": "configs[1] per rank (weak scaling: the N = 1 workload on every GPU); with --full, configs[4]'s "
+                                                   "model on 4096 x N envs is measured in the same job at N > 1: configs4_composite",
+                            "parallelism": f"dp{world}" if world > 1 else "single",
+                            "mfma_frac_whole_step": None if (composite or gru) else
+                            (FLOP_PER_ENV_STEP * value / world) / ((split_peak(ops) if ops.SPLIT else PEAK_FP32_MFMA_TFLOPS) * 1e12),
+                            "rank_ms_per_step": {"min": min(rank_ms), "max": max(rank_ms)},
+                            "rccl_world": (world_facts["world"] if world_facts and world_facts["backend"] == "nccl" else None),
+                            "world": world_facts}, **config_extra),
+            "last_update": [float(x) for x in out],
+        }
+
+    def teardown():
+        if world > 1:
+            phase("teardown", 60)
+            dist.barrier()
+            if wd is not None:
+                wd.finish()                          # the line is out: a slow communicator teardown is not a failure
+            dist.destroy_process_group()
+
     composite, gru = a.workload == "composite", a.workload == "gru"
     keep = {} if a.dump_outputs else None
     alg, step = make_workload(a.workload)
@@ -540,6 +604,26 @@ def run(a, rank, local_rank, world, wd):
         if rank == 0:                                # before any further step changes the trainer's state
             dump_outputs(a.dump_outputs, keep["plan"], alg, out)
         keep = None
+    overlap, overlap_rec = getattr(alg, "overlap_wgrad", False), getattr(alg, "overlap", False)
+    world_facts = None
+    if world > 1:
+        # what the job actually ran on: the communicator's backend and size, and every rank's device (PCI bus id + name) --
+        # two ranks on one device, or a gloo rehearsal, must be visible in the line
+        pr = torch.cuda.get_device_properties(local_rank)
+        mine_dev = dict(rank=rank, local_rank=local_rank, name=pr.name,
+                        pci_bus_id="%04x:%02x:%02x.0" % (getattr(pr, "pci_domain_id", 0), getattr(pr, "pci_bus_id", 0), getattr(pr, "pci_device_id", 0)),
+                        uuid=str(getattr(pr, "uuid", "")))
+        devs = [None] * world
+        dist.all_gather_object(devs, mine_dev)
+        world_facts = dict(backend=dist.get_backend(), world=dist.get_world_size(), devices=devs,
+                           distinct_devices=len({d["pci_bus_id"] for d in devs}))
+    if not a.full:
+        phase("result line", 120)
+        if rank == 0:
+            line = result_line()
+            emit_line(compact_line(line, write_detail(line, a.detail) if a.detail else None))
+        teardown()
+        return
     phase("accuracy check, per-kernel pass", 900)
 
     # per-kernel HIP-event timing of one more step (same process, each kernel on the stream it is launched on)
@@ -656,7 +740,6 @@ def run(a, rank, local_rank, world, wd):
 
     # EVERY rank runs these two extra steps (they contain the data-parallel collectives); only rank 0 records events
     lib = _ffi.lib()
-    overlap, overlap_rec = getattr(alg, "overlap_wgrad", False), getattr(alg, "overlap", False)
     alg.overlap_wgrad = alg.overlap = False
     in_situ = None
     if rank == 0 and world == 1 and a.workload == "decoder" and getattr(alg, "use_images", False) and not a.no_in_situ:
@@ -684,18 +767,6 @@ def run(a, rank, local_rank, world, wd):
     torch.cuda.synchronize()
     coll_log = dp.assert_same_collective_sequence()      # raises on any rank whose sequence differs
     dp.trace_collectives(False)
-    world_facts = None
-    if world > 1:
-        # what the job actually ran on: the communicator's backend and size, and every rank's device (PCI bus id + name) --
-        # two ranks on one device, or a gloo rehearsal, must be visible in the line
-        pr = torch.cuda.get_device_properties(local_rank)
-        mine_dev = dict(rank=rank, local_rank=local_rank, name=pr.name,
-                        pci_bus_id="%04x:%02x:%02x.0" % (getattr(pr, "pci_domain_id", 0), getattr(pr, "pci_bus_id", 0), getattr(pr, "pci_device_id", 0)),
-                        uuid=str(getattr(pr, "uuid", "")))
-        devs = [None] * world
-        dist.all_gather_object(devs, mine_dev)
-        world_facts = dict(backend=dist.get_backend(), world=dist.get_world_size(), devices=devs,
-                           distinct_devices=len({d["pci_bus_id"] for d in devs}))
     if rank == 0:
         lib.dtc_prof_reset()
         lib.dtc_prof_enable(1)
@@ -842,62 +913,11 @@ def run(a, rank, local_rank, world, wd):
         alg = alg4
     phase("result line", 120)
     if rank == 0:
-        env_steps = NUM_ENVS * NUM_STEPS * world * a.steps
-        value = env_steps / elapsed
-        line = {
-            "metric": METRIC,
-            "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": elapsed / a.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": ("f32 (emulated: f16x2 split per operand, f32 accumulate)" if (ops.SPLIT and (ops.H2 or getattr(alg, "use_images", False)))
-                      else "f32 (emulated: bf16x3 split per operand, f32 accumulate)" if ops.SPLIT else "f32"),
-            "data": "synthetic",
-            "gemm_arithmetic": ("results, accumulation, narrow layers, losses and optimiser in f32; the operands of the wide layers (>= 128 columns) live "
-                                "in HBM as block-scaled two-term fp16 images (x 2^e = hi + lo: 22 significant bits; e per ROW and block of 128 "
-                                "columns from that block's own largest finite element, weights per 128 x 128 block), 3 fp16 MFMA passes per "
-                                "product (exact in the f32 accumulator; dropped lo lo' = 2^-22 of a product), accumulator rows rescaled exactly "
-                                "at block borders: every row is as accurate relative to ITSELF as an f32 dot product, whatever the other rows "
-                                "hold, and a non-finite element poisons only its own row / column (csrc/h2i_core.hpp).  Measured against fp64: "
-                                "gemm_accuracy (random operands) and gemm_accuracy_in_situ (the step's real operands).  DTC_H2I=0: round 4's "
-                                "converting kernels (tensor-amax scale); DTC_GEMM_SPLIT=0: single-pass fp32 MFMA everywhere"
-                                if getattr(alg, "use_images", False) and ops.SPLIT else
-                                ("f32 operands and results; wide layers on the fp16 matrix pipe as 2-term splits (x 2^e = hi + lo, e from the "
-                                 "tensor's amax: 22 significant bits, the sums scaled back exactly), 3 MFMA passes, fp32 accumulate -- the error "
-                                 "level of the fp32 MFMA chain, measured below against fp64 next to the single-pass fp32 MFMA kernels and the "
-                                 "bf16 x 3 / six-pass kernels (DTC_GEMM_SPLIT=1); DTC_GEMM_SPLIT=0 selects the single-pass kernels everywhere")
-                                if ops.H2 else
-                                ("f32 operands and results; wide layers on the bf16 matrix pipe as 3-term splits (a = a1 + a2 + a3 exactly to 2^-24), "
-                                 "6 MFMA passes, fp32 accumulate -- fp32-level accuracy, measured below against fp64 next to the single-pass "
-                                 "fp32 MFMA kernels; DTC_GEMM_SPLIT=0 selects the single-pass kernels everywhere") if ops.SPLIT else
-                                "f32 single-pass v_mfma_f32_32x32x2_f32 (DTC_GEMM_SPLIT=0)"),
-            "gemm_accuracy": accuracy,
-            "gemm_accuracy_in_situ": in_situ,
-            "config": {"workload": ("BASELINE configs[1]: 4096 envs x 24 steps/GPU, ActorCriticDecoder (CE-net + terrain encoder 512 + MLP "
-                                    "heads): planner over 98304 recorded maps + compute_returns + PPO.update (5 epochs x 4 x 24576)")
-                       if not (composite or gru) else
-                       ("BASELINE configs[2]: ActorCriticRecurrent (GRU 512), 4096 envs x 24 steps: planner + compute_returns + "
-                        "RecurrentPPO.update (5 epochs x 4 recurrent mini-batches of 1024 envs x 24 steps, BPTT)") if gru else
-                       ("BASELINE configs[4] model (GRU + CE-net + foothold obs), 4096 envs x 24 steps/GPU: planner + compute_returns + "
-                        "RecurrentDecoderPPO.update (5 epochs x 4 recurrent mini-batches of 1024 envs x 24 steps, BPTT)"),
-                       "num_envs_per_gpu": NUM_ENVS, "num_steps_per_env": NUM_STEPS, "mini_batch": 24576,
-                       "epochs": 5, "wgrad_overlap_stream": bool(overlap),
-                       "headline_at_every_n": "configs[1] per rank (weak scaling: the N = 1 workload on every GPU); configs[4]'s model on "
-                                              "4096 x N envs is measured in the same job at N > 1: configs4_composite", "parallelism": f"dp{world}" if world > 1 else "single",
-                       "mfma_frac_whole_step": None if (composite or gru) else
-                       (FLOP_PER_ENV_STEP * value / world) / ((split_peak(ops) if ops.SPLIT else PEAK_FP32_MFMA_TFLOPS) * 1e12),
-                       "rank_ms_per_step": {"min": min(rank_ms), "max": max(rank_ms)},
-                       "allreduce_bytes_per_step_per_rank": dp.bytes_reduced(coll_log) if world > 1 else 0,
-                       "collectives_per_step": len(coll_log),
-                       "collective_sequence_ok": True,      # assert_same_collective_sequence() above passed on every rank
-                       "rccl_world": (world_facts["world"] if world_facts and world_facts["backend"] == "nccl" else None),
-                       "world": world_facts},
-            "configs4_composite": configs4,
-            "roofline": roof,
-            "roofline_planner": planner,
-            "roofline_planner_4096": planner_4096,
-            "kernel_classes": classes,
-            "last_update": [float(x) for x in out],
-        }
+        line = result_line(allreduce_bytes_per_step_per_rank=dp.bytes_reduced(coll_log) if world > 1 else 0,
+                           collectives_per_step=len(coll_log),
+                           collective_sequence_ok=True)      # assert_same_collective_sequence() above passed on every rank
+        line.update(gemm_accuracy=accuracy, gemm_accuracy_in_situ=in_situ, configs4_composite=configs4, roofline=roof,
+                    roofline_planner=planner, roofline_planner_4096=planner_4096, kernel_classes=classes)
         if world == 1 and ops.SPLIT and not a.no_traffic:
             # the SAME workload on the single-pass fp32 MFMA kernels, timed in this process after everything above (same box, same
             # data): for a reader who wants the headline without the split arithmetic.  (Not in the --no-traffic child runs of the
@@ -920,12 +940,7 @@ def run(a, rank, local_rank, world, wd):
         if world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
         emit_line(compact_line(line, write_detail(line, a.detail)))
-    if world > 1:
-        phase("teardown", 60)
-        dist.barrier()
-        if wd is not None:
-            wd.finish()                              # the line is out: a slow communicator teardown is not a failure
-        dist.destroy_process_group()
+    teardown()
 
 
 if __name__ == "__main__":

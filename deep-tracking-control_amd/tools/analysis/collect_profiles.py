@@ -62,7 +62,7 @@ if os.path.exists(p) and "kernel_classes" in last_json(p):
     red = sum(r[0] for r in rows if r[1].startswith("wgrad_reduce"))
     with open(f"{dst}/{tag}_gemm_shapes.md", "w") as f:
         f.write("# Per-shape HIP-event table of one serialised bench step (round %d)\n\n" % rnd)
-        f.write("`DTC_PROF_SHAPES=1 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-traffic`; names `linear_*[M x N x K]` "
+        f.write("`DTC_PROF_SHAPES=1 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-traffic`; names `linear_*[M x N x K]` "
                 "(N = output features, K = input features; `linear_wgrad[M x tiles x layers]` = one grouped weight-gradient launch, "
                 "`wgrad_reduce[splits x tiles x layers]` its split reduce).  Rate: TFLOP/s for the GEMM rows, TB/s for the others.  "
                 "Times include the ~3 us the two HIP events around a launch add.\n\n")

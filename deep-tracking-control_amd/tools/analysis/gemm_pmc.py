@@ -1,6 +1,6 @@
 """SQ / GRBM counters of the GEMM-family kernels over one serialised bench step (rocprofv3 PMC, --kernel-trace only).
 
-    python gemm_pmc.py collect <out_dir> [workload]    two counter passes over `bench.py --steps 1 --warmup 0` + summary (markdown)
+    python gemm_pmc.py collect <out_dir> [workload]    two counter passes over `bench.py --full --steps 1 --warmup 0` + summary (markdown)
     python gemm_pmc.py parse <out_dir>                 re-read existing passes
 
 Per kernel (template instance): launches, kernel time (rocprofv3 start -> end of the same pass), MFMA-pipe busy fraction
@@ -42,7 +42,7 @@ def run_pass(tag, out_dir, workload="decoder", timeout=900):
     os.makedirs(d, exist_ok=True)
     env = dict(os.environ, TMPDIR="/tmp", DTC_OVERLAP_WGRAD="0", DTC_OVERLAP_LANES="0")
     cmd = ["rocprofv3", "--kernel-trace", "--pmc", *PASSES[tag].split(), "-d", d, "-o", "pmc", "--output-format", "csv", "--",
-           sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-traffic",
+           sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-traffic",
            "--workload", workload]
     r = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout)
     if r.returncode != 0:

@@ -1,4 +1,4 @@
-"""Per-kernel-class table of a bench.py JSON line (DTC_PROF_SHAPES=1): python shapes.py <bench.json> [min_ms]"""
+"""Per-kernel-class table of a `bench.py --full` JSON line (DTC_PROF_SHAPES=1): python shapes.py <bench.json> [min_ms]"""
 import json
 import sys
 

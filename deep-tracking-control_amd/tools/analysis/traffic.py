@@ -2,7 +2,7 @@
 
     python traffic.py collect <out_dir>     run the two counter passes (FETCH_SIZE, WRITE_SIZE; separate runs, --kernel-trace
                                             only, as MI355X_MICROARCH.md §HBM / §rocprofv3 prescribes) over
-                                            `bench.py --steps 1 --warmup 0` and print the summary as JSON
+                                            `bench.py --full --steps 1 --warmup 0` and print the summary as JSON
     python traffic.py parse <out_dir>       re-read existing passes
 
 bench.py imports `collect()` for its `roofline.traffic` field.
@@ -12,7 +12,7 @@ coalesced read on gfx950 -> x2 for kernels whose loads are dwordx4 (all operand 
 WRITE_SIZE x1 (calibrated in round 1 on a launch with a known output size, profiles/r01_gemm_traffic.md).  Both counters
 sit on the L2's fabric side: Infinity-Cache hits are included, so this is traffic LEAVING THE L2s, an upper bound of
 the DRAM traffic.  A "step" is delimited by the foothold planner's dispatch; the LAST step of the run is the serialised
-profiling step of bench.py.
+profiling step of `bench.py --full`.
 """
 import csv
 import json
@@ -43,7 +43,7 @@ def run_pass(counter, out_dir, workload="decoder", timeout=600):
     os.makedirs(d, exist_ok=True)
     env = dict(os.environ, TMPDIR="/tmp", DTC_OVERLAP_WGRAD="0", DTC_OVERLAP_LANES="0")
     cmd = ["rocprofv3", "--kernel-trace", "--pmc", counter, "-d", d, "-o", "pmc", "--output-format", "csv", "--",
-           sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-traffic",
+           sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-traffic",
            "--workload", workload]
     r = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout)
     if r.returncode != 0:
@@ -90,7 +90,7 @@ def summarise(out_dir):
     launches = sum(v["launches"] for v in kernels.values())
     return dict(step_bytes=total, launches=launches, fetch_factor=FETCH_FACTOR, write_factor=WRITE_FACTOR, kernels=kernels,
                 method="rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over the serialised last step of "
-                       "bench.py --steps 1 --warmup 0; FETCH_SIZE x2 (16 B/lane loads, MI355X_MICROARCH.md §HBM), WRITE_SIZE x1 "
+                       "bench.py --full --steps 1 --warmup 0; FETCH_SIZE x2 (16 B/lane loads, MI355X_MICROARCH.md §HBM), WRITE_SIZE x1 "
                        "(profiles/r01_gemm_traffic.md); fabric-side counters (Infinity-Cache hits included)")
 
 

@@ -165,3 +165,20 @@ def test_dump_outputs_writes_float_arrays_within_64_mb(tmp_path):
     assert np.array_equal(np.load(tmp_path / "a" / "update_losses.npy"), np.array(losses, dtype=np.float64))
     wide = np.load(tmp_path / "a" / "plan_wide.npy")
     assert 0 < wide.size < plan["wide"].numel() and np.isin(wide, plan["wide"].numpy()).all()
+
+
+@pytest.mark.gpu
+def test_plain_run_reports_the_headline_alone(tmp_path):
+    """Without --full the run stops after the timed steps and --dump-outputs: the line carries the headline fields and none of
+    the extras (accuracy, roofline, counter passes, CPU baseline), and no detail file is written unless --detail names one."""
+    p, lines, _ = _bench(["--gpus", "1", "--steps", "1", "--warmup", "1", "--dump-outputs", str(tmp_path / "dump")], {}, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert len(lines) == 1, p.stdout
+    got = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert got.get(k) is not None, k
+    assert got["steps"] == 1 and got["warmup"] == 1 and got["value"] > 0
+    for k in ("roofline", "cpu_baseline", "single_pass_fp32_mfma", "configs4_composite"):
+        assert k not in got, k
+    assert got["roofline_planner"] is None and got["detail_file"] is None
+    assert os.path.exists(tmp_path / "dump" / "parameters.npy")
