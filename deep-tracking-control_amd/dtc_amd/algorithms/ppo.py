@@ -29,6 +29,7 @@ from .. import _ffi, distributed as dp, h2i, ops, tracing
 from .._ffi import seg, segmat
 from ..modules.actor_critic_decoder import AC_Args, ActorCriticDecoder
 from ..storage import RolloutStorage
+from ..utils import PaddedBuffers
 
 # columns of the per-step statistics table
 S_RECONS, S_VEL, S_KLD, S_HEIGHT, S_VAE_GNORM, S_SURR, S_VALUE, S_ENTROPY, S_KL, S_GNORM = range(10)
@@ -118,54 +119,57 @@ def arena_named(arena):
     return [(k, p) for k, p in arena._named]
 
 
-class _Lanes:
-    """Streams of one optimisation step: `main` (torch's current stream), `aux` = a second compute lane for the branch
-    of the layer graph that is independent of the one on main, `side` = weight gradients.  `order(a, b)` is the only
-    synchronisation primitive: everything launched so far on lane a happens before what lane b launches next."""
+_LANE_STREAMS = {}
 
-    def __init__(self, dev):
-        # the second compute lane and the weight-gradient streams are high-priority HIP streams: their (short, latency-bound) kernels get
-        # the workgroup slots the main lane's 768-workgroup launches free up first -- 50.3 vs 50.9 ms per step, two interleaved rounds
-        # (tools/jobs/r5_prio.sh; "aux" alone 50.85, "side" alone 50.6).  DTC_LANE_PRIO=none: default priorities everywhere
-        prio = os.environ.get("DTC_LANE_PRIO", "aux,side").split(",")
-        # ... EXCEPT where several ranks of a job share this device (the one-GPU rehearsals of the data-parallel path over gloo; RCCL refuses
-        # two ranks on one device): there the lanes are torch's pooled default-priority streams, the one configuration in which the 2-rank
-        # runs never differed from run to run (0 of 30; 3 of 10 with high-priority lanes, pooled or our own; one process: 0 of 50; two
-        # processes that exchange nothing: 0 of 30 -- DESIGN.md §5, profiles/r06_flake*.txt)
-        shared = "DTC_LANE_PRIO" not in os.environ and dp.world_size() > 1 and dp.backend() != "nccl"
-        if shared:
-            prio = []
-        # ... and they are streams of the library's own (dtc_stream_create), NOT entries of torch's stream pool: torch.cuda.Stream(priority=-1)
-        # hands out the 32 pooled high-priority streams round-robin, and torch.distributed's gloo backend takes the work stream of every
-        # collective on a device tensor from the SAME pool -- every few exchanges a collective's staging copies ran on the stream that is
-        # also a compute lane here (DESIGN.md §5).  DTC_LANE_POOL=1: torch's pool, as until round 6
-        pooled = shared or os.environ.get("DTC_LANE_POOL", "0") == "1"
-        self._own = []
 
+def _lane_streams(dev):
+    """(side, side2, aux) of device `dev`: created on first use per (device, priorities, pooled-or-own) and never destroyed.  Every step
+    workspace on the device shares them (each step joins them before it ends), and no caching-allocator block outlives its stream."""
+    # the second compute lane and the weight-gradient streams are high-priority HIP streams: their (short, latency-bound) kernels get
+    # the workgroup slots the main lane's 768-workgroup launches free up first -- 50.3 vs 50.9 ms per step, two interleaved rounds
+    # (tools/jobs/r5_prio.sh; "aux" alone 50.85, "side" alone 50.6).  DTC_LANE_PRIO=none: default priorities everywhere
+    prio = os.environ.get("DTC_LANE_PRIO", "aux,side").split(",")
+    # ... EXCEPT where several ranks of a job share this device (the one-GPU rehearsals of the data-parallel path over gloo; RCCL refuses
+    # two ranks on one device): there the lanes are torch's pooled default-priority streams, the one configuration in which the 2-rank
+    # runs never differed from run to run (0 of 30; 3 of 10 with high-priority lanes, pooled or our own; one process: 0 of 50; two
+    # processes that exchange nothing: 0 of 30 -- DESIGN.md §5, profiles/r06_flake*.txt)
+    shared = "DTC_LANE_PRIO" not in os.environ and dp.world_size() > 1 and dp.backend() != "nccl"
+    if shared:
+        prio = []
+    # ... and they are streams of the library's own (dtc_stream_create), NOT entries of torch's stream pool: torch.cuda.Stream(priority=-1)
+    # hands out the 32 pooled high-priority streams round-robin, and torch.distributed's gloo backend takes the work stream of every
+    # collective on a device tensor from the SAME pool -- every few exchanges a collective's staging copies ran on the stream that is
+    # also a compute lane here (DESIGN.md §5).  DTC_LANE_POOL=1: torch's pool, as until round 6
+    pooled = shared or os.environ.get("DTC_LANE_POOL", "0") == "1"
+    dev = torch.device(dev)
+    if dev.index is None:
+        dev = torch.device(dev.type, torch.cuda.current_device())
+    key = (dev, "side" in prio, "aux" in prio, pooled)
+    if key not in _LANE_STREAMS:
         def make(name):
             if pooled:
                 return torch.cuda.Stream(device=dev, **(dict(priority=-1) if name in prio else {}))
             h = ctypes.c_void_p()
             with torch.cuda.device(dev):
                 _ffi.check(_ffi.lib().dtc_stream_create(int(name in prio), ctypes.byref(h)), "dtc_stream_create")
-            self._own.append(h)
             return torch.cuda.ExternalStream(h.value, device=dev)
-        self.side = make("side")
-        self.side2 = make("side")          # image chain: the narrow layers' (latency-bound) weight-gradient group beside the wide one
-        self.aux = make("aux")
+        # side2, image chain: the narrow layers' (latency-bound) weight-gradient group beside the wide one
+        _LANE_STREAMS[key] = (make("side"), make("side"), make("aux"))
+    return _LANE_STREAMS[key]
+
+
+class _Lanes:
+    """Lanes of one optimisation step: `main` (torch's current stream), `aux` = a second compute lane for the branch of the layer graph
+    that is independent of the one on main, `side` / `side2` = weight gradients (the streams: _lane_streams).  `order(a, b)` is the only
+    synchronisation primitive: everything launched so far on lane a happens before what lane b launches next."""
+
+    def __init__(self, dev):
+        self.side, self.side2, self.aux = _lane_streams(dev)
         self.main = None                    # torch's current stream at the start of the step
         self.two_lanes = False
         self._events, self._ev_next = [], 0
         self.joined, self.joined2 = torch.cuda.Event(), torch.cuda.Event()
         self.side_busy = self.side2_busy = False
-
-    def __del__(self):
-        try:
-            for h in self._own:
-                _ffi.lib().dtc_stream_destroy(h)        # (hipStreamDestroy returns at once; the stream goes when its work has drained)
-            self._own = []
-        except Exception:                                # interpreter shutdown: the library / torch may be gone already
-            pass
 
     def begin(self, two_lanes):
         self.main = torch.cuda.current_stream()
@@ -210,37 +214,27 @@ class _Lanes:
         self._ev_next = 0
 
 
-class _TrainWorkspace(_Lanes):
-    """Activation / gradient buffers of one mini-batch step (allocated once per batch size).
+class _StepWorkspace(_Lanes):
+    """Buffers of one optimisation step on mini-batches of B rows (one workspace per batch size and device): fp32 activations /
+    gradients by name (`g`), operand images (`img`), padded recurrent buffers (`padded`), the queued weight-gradient jobs and the
+    workspaces of their launches.
 
     Every layer's input-gradient gets its OWN buffer (`g(name, width)`): the weight gradients run on a side
     stream concurrently with the data-gradient chain (see PPO._bwd), so a buffer that a later layer's dgrad
-    would overwrite may still be being read.  26 buffers x B x <=693 floats ~ 1 GB at B = 24576."""
+    would overwrite may still be being read."""
 
-    def __init__(self, B, dev, num_actions):
+    def __init__(self, B, dev, grow_padded=True):
         super().__init__(dev)
-        e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         self.B, self._dev = B, dev
-        # VAE-only forward activations
-        self.c1, self.c2, self.rec = e(B, 64), e(B, 128), e(B, 53)
-        self.d1, self.d2, self.hr = e(B, 512), e(B, 512), e(B, 693)
-        # loss gradients
-        self.g_rec, self.g_hr = e(B, 53), e(B, 693)
-        self.dlt = e(B, 512)
-        self.dmulv, self.dz = e(B, 35), e(B, 16)
-        self.dmean, self.dval = e(B, num_actions), e(B, 1)
-        self._g = {}
-        lib = _ffi.lib()
-        shapes = [(512, 693), (512, 512), (693, 512), (512, 584), (512, 752), (256, 512), (128, 256), (64, 531),
-                  (128, 64), (53, 128), (128, 265), (64, 128), (35, 64), (num_actions, 128), (1, 128)]
-        self.wg = ops.workspace(max(lib.dtc_linear_wgrad_workspace(B, n, k) for n, k in shapes), dev)
-        self.loss_ws = ops.workspace(lib.dtc_loss_workspace(B), dev)
-        self.hpart = torch.zeros(int(lib.dtc_linear_fwd_mse_parts(B, 693)), dtype=torch.float64, device=dev)
-        self.gws = self.gws2 = self.gws_img = None
+        self._g, self._imgs, self.live_img = {}, {}, set()
+        self.pad = PaddedBuffers(grow_padded)
+        self.wg = self.gws = self.gws2 = self.gws_img = None
         self.pending, self.held = [], []      # queued weight-gradient jobs; operands of flushed jobs (alive until the join)
         self.pending_img = []                 # queued weight-gradient jobs whose operands are activation images
-        self._imgs, self.live_img = {}, set()
         self.narrow_wgrad = False             # the step in flight runs the image chain: its fp32 weight-gradient jobs are the narrow layers
+
+    def padded(self, name, rows, width, slots=None):
+        return self.pad.get(name, rows, width, self._dev, slots)
 
     def img(self, name, width=None):
         """Operand image (h2i.HImage) of the [B, width] activation / gradient `name`, allocated on first use."""
@@ -274,10 +268,10 @@ class _TrainWorkspace(_Lanes):
             setattr(self, name, cur)
         return cur
 
-    def wgrad_ws(self, N, K):
-        """Split-partials workspace, grown on demand (rare: first use of a larger layer shape)."""
-        need = ops.wgrad_workspace_bytes(self.B, N, K)
-        if self.wg.numel() * self.wg.element_size() < need:
+    def wgrad_ws(self, N, K, M=None):
+        """Split-partials workspace of a weight gradient over M rows (default B), grown on demand (rare: first use of a larger shape)."""
+        need = ops.wgrad_workspace_bytes(self.B if M is None else M, N, K)
+        if self.wg is None or self.wg.numel() * self.wg.element_size() < need:
             torch.cuda.synchronize()            # nothing may still be reading the buffer being replaced
             self.wg = ops.workspace(need, self._dev)
         return self.wg
@@ -287,6 +281,29 @@ class _TrainWorkspace(_Lanes):
         if t is None:
             t = self._g[name] = torch.empty(self.B, width, dtype=torch.float32, device=self._dev)
         return t
+
+
+class _TrainWorkspace(_StepWorkspace):
+    """The step workspace of the decoder trainers, with the fixed activation / gradient buffers of their VAE and policy steps
+    (26 buffers x B x <=693 floats ~ 1 GB at B = 24576)."""
+
+    def __init__(self, B, dev, num_actions):
+        super().__init__(B, dev, grow_padded=False)
+        e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        # VAE-only forward activations
+        self.c1, self.c2, self.rec = e(B, 64), e(B, 128), e(B, 53)
+        self.d1, self.d2, self.hr = e(B, 512), e(B, 512), e(B, 693)
+        # loss gradients
+        self.g_rec, self.g_hr = e(B, 53), e(B, 693)
+        self.dlt = e(B, 512)
+        self.dmulv, self.dz = e(B, 35), e(B, 16)
+        self.dmean, self.dval = e(B, num_actions), e(B, 1)
+        lib = _ffi.lib()
+        shapes = [(512, 693), (512, 512), (693, 512), (512, 584), (512, 752), (256, 512), (128, 256), (64, 531),
+                  (128, 64), (53, 128), (128, 265), (64, 128), (35, 64), (num_actions, 128), (1, 128)]
+        self.wg = ops.workspace(max(lib.dtc_linear_wgrad_workspace(B, n, k) for n, k in shapes), dev)
+        self.loss_ws = ops.workspace(lib.dtc_loss_workspace(B), dev)
+        self.hpart = torch.zeros(int(lib.dtc_linear_fwd_mse_parts(B, 693)), dtype=torch.float64, device=dev)
 
 
 class PPO:
@@ -534,7 +551,11 @@ class PPO:
     def _bwd_img(self, tw, L, dZimg, Ximg, wcol0=0, bias=True):
         """The weight gradient of a layer (or of the column block of it that meets operand image Ximg) whose operands are images:
         queued for the bucket's image-operand grouped launch."""
-        tw.pending_img.append((dZimg, Ximg, L.gW, wcol0, L.gb if bias else None))
+        self._wgrad_img(tw, dZimg, Ximg, L.gW, wcol0, L.gb if bias else None)
+
+    def _wgrad_img(self, tw, *job):
+        """Queue the image-operand weight-gradient job (dZimg, Ximg, gW, wcol0, gb); a full group is launched at once."""
+        tw.pending_img.append(job)
         if len(tw.pending_img) == tw.MAX_GROUP:
             self._flush_wgrads(tw)
 
@@ -965,18 +986,16 @@ class PPO:
         flat = {k: st.flat(k) for k in self._FLAT_NAMES}
         fw, tw = ac._fwd_ws(B), self._train_ws(B)
         self._amax_static(flat, fw)
-        self._pack_gen = getattr(self, "_pack_gen", 0) + 1
-        fw.pack_gen, fw.pack_slot = self._pack_gen, 0
         self.optimizer.set_lr(self.learning_rate)
         stats = torch.zeros(STAT_COLS, dtype=torch.float32, device=dev) if stats is None else stats.to(dev)
-        try:
-            if which in ("vae", "both"):
-                self._vae_step(fw, tw, flat, idx, eps1.to(dev).contiguous(), stats)
-            if which in ("ppo", "both"):
-                self._ppo_step(fw, tw, flat, idx, eps2.to(dev).contiguous(), stats, self._loss_cfg())
-        finally:
-            ops.amax_static_clear()
-            fw.pack_gen = None
+        with fw.slots.open():                          # the packed rollout rows serve both optimisation steps of this call
+            try:
+                if which in ("vae", "both"):
+                    self._vae_step(fw, tw, flat, idx, eps1.to(dev).contiguous(), stats)
+                if which in ("ppo", "both"):
+                    self._ppo_step(fw, tw, flat, idx, eps2.to(dev).contiguous(), stats, self._loss_cfg())
+            finally:
+                ops.amax_static_clear()
         self.learning_rate = float(self.optimizer.lr_dev.item())
         for g in self.optimizer.param_groups:
             g['lr'] = self.learning_rate
@@ -1037,23 +1056,21 @@ class PPO:
         stats = torch.zeros(steps, STAT_COLS, dtype=torch.float32, device=dev)
         lr_hist = torch.zeros(steps, dtype=torch.float64, device=dev) if return_stats else None
         k = 0
-        self._pack_gen = getattr(self, "_pack_gen", 0) + 1
-        fw.pack_gen = self._pack_gen                   # the packed rollout rows of a mini-batch serve all five epochs (packed_input)
-        try:
-            for _ in range(epochs):
-                for i in range(nmb):
-                    fw.pack_slot = i
-                    idx = perm[i * B:(i + 1) * B]
-                    with tracing.span("vae_step"):
-                        self._vae_step(fw, tw, flat, idx, eps1[k], stats[k])
-                    with tracing.span("ppo_step"):
-                        self._ppo_step(fw, tw, flat, idx, eps2[k], stats[k], cfg)
-                    if lr_hist is not None:
-                        lr_hist[k:k + 1].copy_(self.optimizer.lr_dev)
-                    k += 1
-        finally:                                       # (an exception mid-update must not leave the generation live: a later direct step would
-            fw.pack_gen = None                         # find the packed rows of THIS rollout under a recycled index address)
-            ops.amax_static_clear()                    # the storage is about to be refilled: its amax slots are void
+        with fw.slots.open():                          # the packed rollout rows of a mini-batch serve all five epochs (packed_input)
+            try:
+                for _ in range(epochs):
+                    for i in range(nmb):
+                        fw.slots.slot = i
+                        idx = perm[i * B:(i + 1) * B]
+                        with tracing.span("vae_step"):
+                            self._vae_step(fw, tw, flat, idx, eps1[k], stats[k])
+                        with tracing.span("ppo_step"):
+                            self._ppo_step(fw, tw, flat, idx, eps2[k], stats[k], cfg)
+                        if lr_hist is not None:
+                            lr_hist[k:k + 1].copy_(self.optimizer.lr_dev)
+                        k += 1
+            finally:
+                ops.amax_static_clear()                # the storage is about to be refilled: its amax slots are void
         # the single device -> host synchronisation of the update
         host = stats.cpu()
         self.learning_rate = float(self.optimizer.lr_dev.item())

@@ -23,6 +23,7 @@ import os
 
 from .. import _ffi, h2i, ops
 from .._ffi import seg, segmat
+from ..utils import UpdateSlots
 
 # The actor's / critic's tails 512 -> 256 -> 128 as one launch per direction (round 6): built, bit-identical, and measured
 # SLOWER -- 50.2 vs ~49.0 ms per step on one box, two interleaved rounds (860 instead of 940 launches): a row tile's workgroup then runs 3
@@ -300,8 +301,7 @@ class ActorCriticDecoder(nn.Module):
             self.lat_ws = torch.empty(int(_ffi.lib().dtc_cenet_workspace(B)) // 8 + 1, dtype=torch.float64, device=dev)
             self._dev, self._masks = dev, {}
             self._imgs, self.live_img = {}, set()
-            self.pack_key = {}               # operand image name -> what it was packed from (see ActorCriticDecoder.packed_input)
-            self.pack_gen, self.pack_slot = None, 0      # set by the trainer for the duration of an update (packed_input)
+            self.slots = UpdateSlots()       # opened by the trainer for the duration of an update (packed_input)
             self.cur = {}                    # logical name -> the packed image the step in flight uses
 
         def img(self, name, width=None):
@@ -400,16 +400,10 @@ class ActorCriticDecoder(nn.Module):
         """Operand image `name` of the fp32 operand X (DtcSegMat: the gathered rollout rows, narrow hand-over tensors).
         `reuse`: X is a function of the rollout storage and the mini-batch index only.  The reference's mini-batches are the SAME four
         index sets in all five epochs of an update (rollout_storage.py:165, 188-193: one randperm, then the epoch loop), so inside an
-        update -- the trainer sets `ws.pack_gen` / `ws.pack_slot` for its duration -- each mini-batch's image is packed once, into its
-        own buffer, and serves both optimisation steps of all epochs.  Outside an update (pack_gen None) every call packs."""
-        gen = ws.pack_gen if reuse else None
-        slot = ws.pack_slot if gen is not None else 0
-        img = ws.img(f"{name}@{slot}", X.cols)
-        key = None if gen is None else (gen, None if idx is None else (idx.data_ptr(), idx.numel()))
-        if key is None or ws.pack_key.get((name, slot)) != key:
-            img.pack(X, ws.B)
-            ws.pack_key[(name, slot)] = key
-        ws.cur[name] = img
+        update -- the trainer opens `ws.slots` for its duration -- each mini-batch's image is packed once, into its own buffer, and serves
+        both optimisation steps of all epochs.  Outside an update every call packs."""
+        key = (() if idx is None else (idx.data_ptr(), idx.numel())) if reuse else None
+        img = ws.cur[name] = ws.slots.packed(ws, name, lambda: X, X.cols, ws.B, key)
         return img
 
     def terrain_encoder_(self, ws, priv, idx=None, masks=False, images=False, wset=None, lt_fp32=True, split=None):

@@ -18,6 +18,7 @@ import torch.nn as nn
 
 from .. import _ffi, ops
 from .._ffi import seg, segmat
+from ..utils import PaddedBuffers
 from .actor_critic_decoder import Dense, get_activation
 
 
@@ -187,6 +188,7 @@ class Memory(nn.Module):
         self.hidden_states = None
         self.input_size, self.hidden_size = input_size, hidden_size
         self.saved = None          # tensors of the last batch-mode forward (for BPTT)
+        self._pad = PaddedBuffers(grow=True)   # the compacted input projection's padded layout (run(rows=...)), zeroed by new_update
 
     def bind(self, arena, prefix):
         v = lambda buf, n: arena.view(buf, f"{prefix}.rnn.{n}")
@@ -223,19 +225,8 @@ class Memory(nn.Module):
 
     def new_update(self):
         """Called by the trainers at the start of an update: the padding slots of the compacted input projection start from zero, so
-        an update's result never depends on what earlier updates left there (within an update they hold finite values of its own
-        earlier mini-batches, which nothing reads: the outputs of padding steps are masked out and their gradients are zero)."""
-        buf = getattr(self, "_gi_pad", None)
-        if buf is not None:
-            buf.zero_()
-
-    def _padded_gi(self, rows_total, width, dev):
-        """Persistent, zero-initialised [T * R, G * H] buffer for the compacted input projection (grown on demand): the slots a
-        mini-batch does not write keep finite values of earlier mini-batches of the same update (new_update)."""
-        buf = getattr(self, "_gi_pad", None)
-        if buf is None or buf.numel() < rows_total * width or buf.device != dev:
-            buf = self._gi_pad = torch.zeros(rows_total * width, device=dev)
-        return buf[:rows_total * width].view(rows_total, width)
+        an update's result never depends on what earlier updates left there."""
+        self._pad.zero("gi")
 
     def run(self, x, hidden, rows=None):
         """x [T,R,I], hidden as in `hidden_states` ([L,R,H] or (h, c)) -> saved dict; saved['out'] = top layer's [T,R,H].
@@ -250,7 +241,7 @@ class Memory(nn.Module):
                 # ~30 % of a padded recurrent mini-batch is padding: project the valid rows (gathered) and scatter them into place
                 gi_c = torch.empty(rows.numel(), G * H, device=dev)
                 ops.linear_fwd(segmat([seg(cur, 0, cur.shape[1], gather=True)], rows), self.Wih[l], self.bih[l], gi_c, None, M=rows.numel())
-                gi = self._padded_gi(T * R, G * H, dev).view(T, R, G * H)
+                gi = self._pad.get("gi", T * R, G * H, dev).view(T, R, G * H)
                 ops.scatter_rows(gi_c, rows, gi.view(T * R, G * H))
             else:
                 gi = torch.empty(T, R, G * H, device=dev)
