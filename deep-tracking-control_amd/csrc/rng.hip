@@ -13,21 +13,9 @@
 #include <math.h>
 
 #include "common.hpp"
+#include "philox.hpp"
 
 namespace {
-
-struct U4 { unsigned x, y, z, w; };
-
-__device__ __forceinline__ U4 philox4x32_10(U4 c, unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c.x, p1 = (unsigned long long)0xCD9E8D57u * c.z;
-        c = U4{(unsigned)(p1 >> 32) ^ c.y ^ k0, (unsigned)p1, (unsigned)(p0 >> 32) ^ c.w ^ k1, (unsigned)p0};
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
 
 __device__ __forceinline__ void box_muller(unsigned a, unsigned b, float& n0, float& n1) {
     const float u1 = (float)((a >> 8) + 1u) * 5.9604644775390625e-08f;       // (0, 1]: 24 uniform bits

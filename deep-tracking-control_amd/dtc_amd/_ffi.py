@@ -143,6 +143,37 @@ class DtcRewardStep(C.Structure):
                 [("num_bodies", C.c_int32), ("num_commands", C.c_int32)])
 
 
+RESET_MAX_ROWS, RESET_MAX_TIME_ROWS, RESET_MAX_SUMS, RESET_FIXED_DRAWS = 32, 8, 64, 14
+
+
+class DtcResetRows(C.Structure):
+    _fields_ = [("ptr", C.c_void_p), ("T", C.c_int32), ("row_bytes", C.c_int32)]
+
+
+class DtcResetCfg(C.Structure):
+    """include/dtc_hip.h: the flags, ranges and per-call scalars of dtc_env_reset; field order as there."""
+    _fields_ = ([(k, C.c_int32) for k in ("num_dof", "num_bodies", "num_commands", "num_points", "terrain_curriculum", "init_done",
+                                          "custom_origins", "heading_command", "play_command", "randomize_motor_strength",
+                                          "randomize_kp", "randomize_kd", "max_terrain_level", "terrain_rows", "terrain_cols")] +
+                [("move_up_distance", C.c_float), ("max_episode_length_s", C.c_double), ("base_init_state", C.c_float * 13),
+                 ("height_noise", C.c_float)] +
+                [(k, C.c_double * 2) for k in ("origin_xy", "lin_vel_x", "lin_vel_y", "ang_vel_yaw", "heading", "motor_strength",
+                                               "kp_range", "kd_range")] +
+                [("seed", C.c_uint64), ("counter", C.c_uint64)])
+
+
+class DtcResetStep(C.Structure):
+    """include/dtc_hip.h: the buffers of one dtc_env_reset call (device pointers); field order as there."""
+    _fields_ = ([(k, C.c_void_p) for k in ("reset_buf", "u", "level_draw", "terrain_origins", "terrain_types", "default_dof_pos",
+                                           "terrain_levels", "env_origins", "root_states", "commands", "dof_pos", "dof_vel")] +
+                [(k, C.c_int64) for k in ("dof_pos_row_stride", "dof_pos_elem_stride", "dof_vel_row_stride", "dof_vel_elem_stride")] +
+                [(k, C.c_void_p) for k in ("forces", "motor_strengths", "Kp_factors", "Kd_factors", "height_noise_offset",
+                                           "episode_sums")] +
+                [(k, C.c_int32) for k in ("n_sums", "n_rows", "n_time_rows", "pad_")] +
+                [("rows", DtcResetRows * RESET_MAX_ROWS), ("time_rows", DtcResetRows * RESET_MAX_TIME_ROWS)] +
+                [(k, C.c_void_p) for k in ("env_ids", "count", "episode_means", "terrain_level_mean", "workspace")])
+
+
 class DtcRowCopy(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("src_stride_bytes", C.c_int64), ("width_bytes", C.c_int32)]
 
@@ -155,7 +186,7 @@ class DtcProfRec(C.Structure):
 ACT = {None: 0, "none": 0, "relu": 1, "crelu": 1, "elu": 2, "selu": 3, "lrelu": 4, "tanh": 5, "sigmoid": 6}
 MAX_OPERAND_ELEMS = (1 << 29) - 1
 
-ABI_VERSION = 15         # DTC_ABI_VERSION of include/dtc_hip.h this binding was written against
+ABI_VERSION = 16         # DTC_ABI_VERSION of include/dtc_hip.h this binding was written against
 
 _SIGS = {
     "dtc_version": (C.c_int, []),
@@ -177,6 +208,9 @@ _SIGS = {
                                        [c_f32p] * 3 + [c_u8p, C.c_int, c_stream]),
     "dtc_env_post_physics": (C.c_int, [C.POINTER(DtcEnvStep), C.POINTER(DtcGridCfg), C.POINTER(DtcObsCfg), C.c_int, c_stream]),
     "dtc_env_rewards": (C.c_int, [C.POINTER(DtcRewardStep), C.POINTER(DtcRewardCfg), C.c_int, c_stream]),
+    "dtc_env_reset_workspace": (C.c_int64, [C.c_int, C.c_int]),
+    "dtc_env_reset_abi_sizes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
+    "dtc_env_reset": (C.c_int, [C.POINTER(DtcResetStep), C.POINTER(DtcResetCfg), C.c_int, c_stream]),
     "dtc_check_termination": (C.c_int, [c_f32p, C.c_int, c_i32p, C.c_int, c_i64p, C.c_int64, c_f32p, c_f32p, c_f32p,
                                         C.POINTER(DtcObsCfg), c_u8p, c_u8p, c_f32p, C.c_int, c_stream]),
     "dtc_store_transition": (C.c_int, [C.POINTER(DtcRowCopy), C.c_int, c_f32p, c_f32p, c_u8p, C.c_float, c_f32p,
@@ -347,6 +381,9 @@ def _check_abi(l):
     sizes = (C.c_int64 * 32)()
     n = l.dtc_abi_sizes(sizes, 32)
     theirs = list(sizes[:n])
+    mine += [DtcResetRows, DtcResetCfg, DtcResetStep]                     # reported by the reset entry points' own table
+    n = l.dtc_env_reset_abi_sizes(sizes, 32)
+    theirs += list(sizes[:n])
     if l.dtc_version() != ABI_VERSION or theirs != [C.sizeof(t) for t in mine]:
         _lib = None
         raise DtcError(f"{LIB_PATH}: ABI mismatch (library version {l.dtc_version()}, struct sizes {theirs}; binding version "

@@ -272,3 +272,85 @@ def reward_table(rows: int = 1400, cols: int = 900, seed: int = 37, device="cpu"
     """int16 terrain table (horizontal 0.05 m, vertical 0.005 m, 20 m border) under the feet of `reward_state`."""
     g = _gen(seed, device)
     return torch.randint(-200, 200, (rows, cols), generator=g, device=device).to(torch.int16)
+
+
+# tensors of a LeggedRobotDTC env that reset_idx clears row-wise ([N, ...]) and the time-major ring buffers ([10, N, C])
+RESET_ROW_ITEMS = ("last_actions", "last_actions_2", "last_dof_vel", "feet_air_time", "feet_contact_time", "last_scale_actions",
+                   "last_scale_actions2", "pitch_est", "base_ang_vel_last", "base_lin_vel_last", "episode_length_buf", "contact_filt",
+                   "last_contacts")
+RESET_TIME_ITEMS = ("lin_vel_buffer", "ang_vel_buffer", "cmd_buffer")
+
+
+def reset_state(num_envs: int, seed: int = 41, device="cpu", *, terrain_rows: int = 6, terrain_cols: int = 2, n_sums: int = 24,
+                reset: str = "some", env_length: float = 8.0, episode_length_s: float = 20.0) -> dict:
+    """Mock env state for `reset_idx` (legged_robot.py:200-272): every tensor it and its callees read or write, keyed by the env's
+    attribute names (`lag_buffer` / `stumb_buffer` are lists, `episode_sums` is [n_sums, N]).  About one env in eight is reset
+    (`reset` = "some"; "all" / "none" set every / no flag).  The terrain curriculum (legged_robot.py:690-711) meets all its branches:
+    levels are weighted towards 0 and terrain_rows - 1, and the walked distance is drawn beyond env_length * 0.6 (move up), below
+    |commands_xy| * episode_length_s * 0.5 (move down) or between, each >= 2e-3 (relative) away from its threshold.  A few envs
+    that are NOT reset hold NaN rows, so that an untouched row is provable."""
+    g = _gen(seed, device)
+    N, D, B = num_envs, 12, 17
+    ru = lambda *s: torch.rand(*s, generator=g, device=device)          # noqa: E731
+    rn = lambda *s: torch.randn(*s, generator=g, device=device)         # noqa: E731
+    ri = lambda hi, *s: torch.randint(0, hi, s, generator=g, device=device)          # noqa: E731
+    flag = {"some": ru(N) < 0.125, "all": torch.ones(N, dtype=torch.bool, device=device),
+            "none": torch.zeros(N, dtype=torch.bool, device=device)}[reset]
+    R, Ct = terrain_rows, terrain_cols
+    origins = torch.zeros(R, Ct, 3, device=device)
+    origins[:, :, 0] = 24.0 + 8.0 * torch.arange(R, device=device, dtype=torch.float32)[:, None]
+    origins[:, :, 1] = 24.0 + 8.0 * torch.arange(Ct, device=device, dtype=torch.float32)[None, :]
+    origins[:, :, 2] = 0.1 * rn(R, Ct)
+    types = (torch.arange(N, device=device) * Ct) // max(N, 1)
+    edge = ru(N)
+    levels = torch.where(edge < 0.3, torch.zeros(N, dtype=torch.int64, device=device),
+                         torch.where(edge < 0.6, torch.full((N,), R - 1, dtype=torch.int64, device=device), ri(R, N)))
+    env_origins = origins[levels, types].clone()
+    cmd = 0.6 * rn(N, 4)
+    still = ru(N) < 0.15
+    cmd[still, :2] *= 0.05
+    cn = cmd[:, :2].norm(dim=1)
+    half = cn * (episode_length_s * 0.5)
+    up_at = env_length * 0.6
+    kind = ru(N)
+    dist = torch.where(kind < 0.4, up_at * 1.01 + 3.0 * ru(N),
+                       torch.where(kind < 0.85, 0.95 * ru(N) * torch.minimum(half, torch.full_like(half, up_at * 0.98)),
+                                   _away(half * 1.1, up_at)))
+    ang = 2 * math.pi * ru(N)
+    root = torch.zeros(N, 13, device=device)
+    root[:, 0] = env_origins[:, 0] + dist * torch.cos(ang)
+    root[:, 1] = env_origins[:, 1] + dist * torch.sin(ang)
+    root[:, 2] = env_origins[:, 2] + 0.3 + 0.1 * ru(N)
+    q = rn(N, 4)
+    root[:, 3:7] = q / q.norm(dim=1, keepdim=True)
+    root[:, 7:13] = 0.5 * rn(N, 6)
+    default = torch.tensor([0.1, -0.8, 1.6, -0.1, -0.8, 1.6] * 2, device=device)
+    d = dict(reset_buf=flag, root_states=root, env_origins=env_origins, commands=cmd, terrain_levels=levels, terrain_types=types,
+             terrain_origins=origins, default_dof_pos=default, dof_pos=default + 0.3 * rn(N, D), dof_vel=2.0 * rn(N, D),
+             forces=10.0 * rn(N, B, 3), motor_strengths=0.9 + 0.2 * ru(N, D), Kp_factors=0.95 + 0.1 * ru(N, D),
+             Kd_factors=0.95 + 0.1 * ru(N, D), height_noise_offset=(0.02 * rn(N, 1)).expand(N, N_POINTS).contiguous(),
+             base_init_state=torch.tensor([0.0, 0.0, 0.4, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0], device=device),
+             episode_sums=5.0 * rn(n_sums, N),
+             last_actions=rn(N, D), last_actions_2=rn(N, D), last_dof_vel=2.0 * rn(N, D), feet_air_time=0.6 * ru(N, 4),
+             feet_contact_time=0.6 * ru(N, 4), last_scale_actions=0.25 * rn(N, D), last_scale_actions2=0.25 * rn(N, D),
+             pitch_est=0.1 * rn(N), base_ang_vel_last=0.5 * rn(N, 3), base_lin_vel_last=0.5 * rn(N, 3),
+             episode_length_buf=1 + ri(1000, N), contact_filt=ru(N, 4) < 0.6, last_contacts=ru(N, 4) < 0.5,
+             lag_buffer=[0.25 * rn(N, D) for _ in range(6)], stumb_buffer=[ru(N, 4) < 0.3 for _ in range(5)],
+             lin_vel_buffer=0.5 * rn(10, N, 2), ang_vel_buffer=0.5 * rn(10, N, 1), cmd_buffer=0.6 * rn(10, N, 4))
+    # NaN rows in envs that are not reset (every 7th of them): they must come out bit-identical
+    keep = torch.nonzero(~flag).flatten()[::7]
+    for k in ("dof_pos", "dof_vel", "last_actions", "height_noise_offset", "motor_strengths", "feet_air_time", "forces"):
+        d[k][keep] = float("nan")
+    d["root_states"][keep, 7:] = float("nan")
+    d["commands"][keep, 2:] = float("nan")
+    d["episode_sums"][:, keep] = float("nan")
+    d["cmd_buffer"][:, keep] = float("nan")
+    return d
+
+
+def reset_draws(num_envs: int, seed: int = 43, device="cpu", *, num_dof: int = 12, max_terrain_level: int = 6):
+    """The draws one `reset_idx` call may consume, one row per env (include/dtc_hip.h, dtc_env_reset): u [N, num_dof + 14] in [0, 1)
+    and level_draw [N] int64 in [0, max_terrain_level)."""
+    g = _gen(seed, device)
+    u = torch.rand(num_envs, num_dof + 14, generator=g, device=device)
+    return u, torch.randint(0, max_terrain_level, (num_envs,), generator=g, device=device)

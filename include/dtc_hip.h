@@ -38,7 +38,7 @@ extern "C" {
 #define DTC_ACT_SIGMOID 6
 
 /* library / device info ------------------------------------------------------------------ */
-#define DTC_ABI_VERSION 15                   /* bumped whenever a signature or a by-value struct layout changes       */
+#define DTC_ABI_VERSION 16                   /* bumped whenever a signature or a by-value struct layout changes       */
 int dtc_version(void);                       /* == DTC_ABI_VERSION of the build; the host binding refuses a mismatch   */
 /* sizeof() of the structs that cross the boundary, in the order DtcGridCfg, DtcObsCfg, DtcRowCopy, DtcSeg, DtcSegMat,
    DtcFwdLayer, DtcWgradJob, DtcPpoCfg, DtcProfRec, DtcWimgJob, DtcH2iWJob, DtcH2iOperand, DtcWgradH2iJob, DtcEnvStep, DtcH2iFwdLayer, DtcH2iDgradLayer, DtcGruFwdItem, DtcGruBwdItem: the binding compares them with its own layouts at load time (a library
@@ -149,8 +149,8 @@ int dtc_compute_observations_where(const float* base_ang_vel, const float* proje
  * = dtc_foothold_plan[_from_table] + dtc_check_termination + dtc_foothold_rewards + dtc_compute_observations with the same
  * arguments, same bits, one launch (each env's height row is read once and stays in LDS for all four).  The reference resets
  * envs (`reset_idx`, simulator state) BETWEEN the rewards and the observations: the observation rows written here are those of
- * the state passed in; after resetting, refresh the rows of the reset envs with dtc_compute_observations_where(..., where =
- * reset_buf).  All pointers are device pointers; optional ones may be NULL where the separate entry points allow it.
+ * the state passed in; after resetting (dtc_env_reset below), refresh the rows of the reset envs with
+ * dtc_compute_observations_where(..., where = reset_buf).  All pointers are device pointers; optional ones may be NULL where the separate entry points allow it.
  * Grids other than 33 x 21 run the separate launches in that order.  `st`, `grid`, `obs` are HOST pointers. */
 typedef struct DtcEnvStep {
     /* planner */
@@ -262,6 +262,119 @@ typedef struct DtcRewardStep {
 } DtcRewardStep;
 /* One launch for all N envs.  Pointers of terms that are off may be NULL.  `st`, `cfg` are HOST pointers. */
 int dtc_env_rewards(const DtcRewardStep* st, const DtcRewardCfg* cfg, int N, void* stream);
+
+/* ---- env reset: LeggedRobot.reset_idx, legged_gym/envs/base/legged_robot.py:200-272, and what it calls ----------------------------
+ * For every env n with reset_buf[n] != 0, on the env's own tensors, in the reference's order (all arithmetic fp32, one rounding per
+ * operation, operands in the reference's order):
+ *   1. _update_terrain_curriculum (legged_robot.py:690-711; when terrain_curriculum and init_done), from the PRE-reset root_states[n,:2],
+ *      the PRE-update env_origins[n,:2] and the PRE-resample commands[n,:2]: distance = |root_xy - origin_xy|; move_up = distance >
+ *      move_up_distance; move_down = distance < |commands_xy| * max_episode_length_s * 0.5 and not move_up; terrain_levels[n] += move_up -
+ *      move_down; then level >= max_terrain_level ? level_draw[n] : max(level, 0); env_origins[n] = terrain_origins[level, terrain_types[n]].
+ *   2. _reset_dofs (:632-641): dof_pos[n] = default_dof_pos * ((1.5 - 0.5) * u + 0.5); dof_vel[n] = 0.
+ *   3. LeggedRobotDTC._reset_root_states (legged_robot_dtc.py:291-311): root_states[n] = base_init_state; [:3] += the NEW env_origins[n];
+ *      with custom_origins [:2] += (hi - lo) * u + lo over origin_xy (DTC: -0.5..0.5; LeggedRobot, legged_robot.py:659: -1..1);
+ *      [7:13] = (0.5 - -0.5) * u + -0.5.
+ *   4. _resample_commands (:567-593): commands[n,0], [n,1] drawn from lin_vel_x / lin_vel_y, then commands[n,3] from heading
+ *      (heading_command) or commands[n,2] from ang_vel_yaw; with play_command 0.5, 0.0 and 0 instead; commands[n,:2] *= (|commands_xy|
+ *      > 0.1); forces[n,:,:] = 0.
+ *   5. _randomize_dof_props (:465-481): motor_strengths / Kp_factors / Kd_factors [n,:] = u * (max - min) + min, one draw per env, for
+ *      each flag that is on.
+ *   6. height_noise_offset[n,:] = old * 0.0 + height_noise (:229-230; the caller draws np.random.normal(0, 0.02) once per call).
+ *   7. the buffer clears of :233-251 and :267-272, table driven: `rows` items are [N, row_bytes] tensors whose row n is zeroed
+ *      (last_actions, ..., episode_length_buf, the lag buffers, the stumble masks or the stumble bits of dtc_env_rewards, contact_filt,
+ *      last_contacts), `time_rows` items are [T, N, row_bytes] tensors whose rows [:, n] are zeroed (lin_vel_buffer, ang_vel_buffer,
+ *      cmd_buffer).  reset_buf[n] = 1 (:238) changes nothing and is not written.
+ *   8. the episode log (:253-259): episode_means[r] = mean over the reset envs of episode_sums[r, n] / max_episode_length_s, read BEFORE
+ *      episode_sums[r, n] = 0; with terrain_curriculum terrain_level_mean = mean over ALL N envs of terrain_levels after step 1.  Sums are
+ *      accumulated in float64 in a fixed order (per 256-env block, then over the blocks in order) and rounded to fp32 once: no
+ *      floating-point atomics, the same bits from run to run.
+ *   9. the hand-over to the simulator: env_ids[0 .. count) = the reset envs in ascending order (what reset_buf.nonzero() gives), count[0]
+ *      their number -- device memory, for the caller of set_dof_state_tensor_indexed / set_actor_root_state_tensor_indexed.
+ * count == 0 is the reference's early return (:210-211): no env tensor is written and episode_means / terrain_level_mean keep their
+ * contents (count[0] = 0 is written).  `force_positions = rb_positions.clone()` (:593) and update_command_curriculum (:717-726) are
+ * host-side decisions and stay with the caller.
+ *
+ * Draws.  u [N, num_dof + 14] fp32 in [0, 1): row n holds the draws env n uses IF it resets (the reference draws one row per reset env,
+ * in env_ids order); slots: [0, D) dof_pos | D, D+1 origin x, y | D+2 .. D+7 root_states[7:13] | D+8, D+9, D+10 command x, y,
+ * heading-or-yaw | D+11, D+12, D+13 motor strength, Kp, Kd.  level_draw [N] int64: torch.randint_like(levels, max_terrain_level).
+ * With u == NULL (level_draw == NULL) the kernel draws them itself: Philox4x32-10 (csrc/philox.hpp, as dtc_randn), key = seed, counter = (n, slot group,
+ * call counter), 24 bits per uniform; level = word % max_terrain_level.  One env's draws do not depend on which other envs reset.  That
+ * stream has torch's distribution, not torch's bits.  A range [lo, hi] enters as float32(hi - lo) (difference in double) and float32(lo).
+ *
+ * N <= 2^18: every 256-env block of launch 1 recounts the reset_buf bytes in front of it (16 KB on average at 32768 envs, the
+ * largest env count the design is meant for); that is quadratic in N, so larger N is refused rather than run slowly.
+ * Two launches per call whatever the mask, both sized by N alone (one workgroup per 256 envs: env_ids, terrain curriculum, episode
+ * sums and their per-block partial sums; then one wavefront per env: the rows of the envs that reset, and the fold of the partials);
+ * the launch function allocates, copies and waits for nothing.  `st`, `cfg` are HOST pointers holding DEVICE pointers. */
+#define DTC_RESET_MAX_ROWS 32
+#define DTC_RESET_MAX_TIME_ROWS 8
+#define DTC_RESET_MAX_SUMS 64
+#define DTC_RESET_FIXED_DRAWS 14               /* u has num_dof + 14 columns */
+
+typedef struct DtcResetRows {
+    void* ptr;                       /* [N, row_bytes] (time_rows: [T, N, row_bytes]), dense */
+    int32_t T;                       /* rows: ignored; time_rows: the leading dimension (10)  */
+    int32_t row_bytes;
+} DtcResetRows;
+
+typedef struct DtcResetCfg {
+    int32_t num_dof;                 /* D: 12 (<= 64)                                                                     */
+    int32_t num_bodies;              /* B: rows of forces[n]                                                              */
+    int32_t num_commands;            /* C: columns of commands (>= 3; >= 4 with heading_command)                          */
+    int32_t num_points;              /* columns of height_noise_offset (693)                                              */
+    int32_t terrain_curriculum;      /* cfg.terrain.curriculum (legged_robot.py:213, :258)                                */
+    int32_t init_done;               /* self.init_done (:697)                                                             */
+    int32_t custom_origins;          /* self.custom_origins (:1206 / :1219)                                               */
+    int32_t heading_command;         /* cfg.commands.heading_command (:575)                                               */
+    int32_t play_command;            /* cfg.env.play_commond (:580)                                                       */
+    int32_t randomize_motor_strength, randomize_kp, randomize_kd;       /* cfg.domain_rand (:466-477)                     */
+    int32_t max_terrain_level;       /* cfg.terrain.num_rows (:1213)                                                      */
+    int32_t terrain_rows, terrain_cols;      /* shape of terrain_origins [rows, cols, 3]                                  */
+    float move_up_distance;          /* float32(terrain.env_length * 0.6) (:702)                                          */
+    double max_episode_length_s;     /* cfg.env.episode_length_s (:704 as fp32, :255 divides the float64 mean by it)      */
+    float base_init_state[13];       /* self.base_init_state (:1132)                                                      */
+    float height_noise;              /* the np.random.normal(0, 0.02) of this call (:230)                                 */
+    double origin_xy[2];             /* [lo, hi] of the xy offset under custom_origins                                    */
+    double lin_vel_x[2], lin_vel_y[2], ang_vel_yaw[2], heading[2];      /* self.command_ranges, as they are at this call  */
+    double motor_strength[2], kp_range[2], kd_range[2];                 /* cfg.domain_rand [min, max]                     */
+    uint64_t seed, counter;          /* generated draws only: key and call counter                                        */
+} DtcResetCfg;
+
+typedef struct DtcResetStep {
+    const uint8_t* reset_buf;        /* [N] bool                                                                          */
+    const float* u;                  /* [N, D + 14] or NULL (generated)                                                   */
+    const int64_t* level_draw;       /* [N] or NULL (generated)                                                           */
+    const float* terrain_origins;    /* [terrain_rows, terrain_cols, 3]                                                   */
+    const int64_t* terrain_types;    /* [N]                                                                               */
+    const float* default_dof_pos;    /* [D]                                                                               */
+    /* read and written */
+    int64_t* terrain_levels;         /* [N]                                                                               */
+    float* env_origins;              /* [N,3]                                                                             */
+    float* root_states;              /* [N,13]                                                                            */
+    float* commands;                 /* [N,C]                                                                             */
+    float *dof_pos, *dof_vel;        /* [N,D], strided: element (n, d) at n * dof_row_stride + d * dof_elem_stride floats.  The
+                                        reference's are the two interleaved views of dof_state [N,D,2] (legged_robot.py:774-775):
+                                        row stride 2 D, element stride 2; a dense [N,D] tensor has D and 1                 */
+    int64_t dof_pos_row_stride, dof_pos_elem_stride, dof_vel_row_stride, dof_vel_elem_stride;
+    float* forces;                   /* [N,B,3] or NULL                                                                   */
+    float *motor_strengths, *Kp_factors, *Kd_factors;   /* [N,D]; needed when their flag is on                             */
+    float* height_noise_offset;      /* [N,num_points] or NULL                                                            */
+    float* episode_sums;             /* [n_sums, N] (the layout of dtc_env_rewards)                                       */
+    int32_t n_sums, n_rows, n_time_rows, pad_;
+    DtcResetRows rows[DTC_RESET_MAX_ROWS];
+    DtcResetRows time_rows[DTC_RESET_MAX_TIME_ROWS];
+    /* outputs */
+    int32_t* env_ids;                /* [N]: entries [0, count) written                                                   */
+    int32_t* count;                  /* [1]                                                                               */
+    float* episode_means;            /* [n_sums]                                                                          */
+    float* terrain_level_mean;       /* [1]; needed with terrain_curriculum                                               */
+    void* workspace;                 /* dtc_env_reset_workspace(N, n_sums) bytes, 8-byte aligned; contents need not be kept */
+} DtcResetStep;
+int64_t dtc_env_reset_workspace(int N, int n_sums);
+/* sizeof() of DtcResetRows, DtcResetCfg, DtcResetStep, as dtc_abi_sizes gives them for the older structs: compared by the binding at
+   load time.  Returns the number of entries (written up to `cap`). */
+int dtc_env_reset_abi_sizes(int64_t* out, int cap);
+int dtc_env_reset(const DtcResetStep* st, const DtcResetCfg* cfg, int N, void* stream);
 
 /* ---- rollout-side store (row f2) ---------------------------------------------------------
  * RolloutStorage.add_transitions, rsl_rl/rsl_rl/storage/rollout_storage.py:99-116: the 13 `copy_` of one env step as
