@@ -13,6 +13,8 @@ Pinning status:
   * GRU actor-critic (config 3) and the GRU + CE-net composite (config 5, build-defined): modules, padding and
     BPTT gradients pinned against the imported reference classes (`gru.npz`, `composite.npz`); the training
     step around them is the ppo.py:288-338 loss block already pinned by `ppo.npz`.
+  * Loss, action and bootstrap kernels one operation at a time: `losses_ref.py`, float64 from the formulas with autograd
+    gradients; its own checks (torch.distributions, hand-computed batches) are in `tests/test_losses_oracle.py`.
   * Foothold scorer: pinned against `LeggedRobotDTC.post_physics_step` run on a mock env,
     EXCEPT for the three Isaac Gym quaternion helpers (`isaacgym.torch_utils`, un-vendored,
     version unpinned by the reference) whose published formulas are restated -> that

@@ -44,6 +44,29 @@ def test_gather_rows_any_width_any_index_multiset(rows, width, n_idx, seed, dtyp
     assert torch.equal(out.cpu(), src[idx])
 
 
+@pytest.mark.parametrize("rows,width,aligned", [(37, 1, True), (37, 3, True), (37, 4, True), (37, 53, True), (37, 512, True), (37, 512, False),
+                                                (9000, 2048, True), (4100, 513, True)])
+def test_scatter_rows_is_the_inverse_gather(rows, width, aligned):
+    """dst[idx[r]] = src[r] bit for bit, every other destination row untouched.  Widths that are multiples of 4 take the 16-byte
+    kernel unless `src` is not 16-byte aligned (a view one float into its buffer: the scalar kernel); 9000 x 2048 is past the
+    16384 x 256 float4 grid of the first, 4100 x 513 past the 8192 x 256 grid of the second (both then stride)."""
+    g = torch.Generator().manual_seed(rows * 1000 + width)
+    base = torch.randn(rows * width + 1, generator=g).to(DEV)
+    src = (base[:-1] if aligned else base[1:]).view(rows, width)
+    assert (src.data_ptr() % 16 == 0) == aligned
+    dst_rows = rows + 37
+    idx = torch.randperm(dst_rows, generator=g)[:rows].contiguous()
+    before = torch.randn(dst_rows, width, generator=g)
+    dst = before.to(DEV)
+    ops.scatter_rows(src, idx.to(DEV), dst)
+    want = before.clone()
+    want[idx] = src.cpu()
+    assert torch.equal(dst.cpu().view(torch.int32), want.view(torch.int32))
+    untouched = torch.ones(dst_rows, dtype=torch.bool)
+    untouched[idx] = False
+    assert torch.equal(dst.cpu()[untouched].view(torch.int32), before[untouched].view(torch.int32))
+
+
 @settings(**{**CFG, "max_examples": 12})
 @given(seed=st.integers(0, 2 ** 16), n=st.integers(1, 97),
        pattern=st.sampled_from(["flat", "all_exceptional", "far_outside", "checker", "one_valid_point", "random"]))
