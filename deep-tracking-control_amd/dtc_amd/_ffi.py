@@ -338,6 +338,17 @@ _SIGS = {
     "dtc_gru_seq_fwd_pair": (C.c_int, [C.POINTER(c_f32p)] * 7 + [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, c_stream]),
     "dtc_gru_fwd_multi": (C.c_int, [C.POINTER(DtcGruFwdItem), C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
     "dtc_gru_bwd_multi": (C.c_int, [C.POINTER(DtcGruBwdItem), C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
+    "dtc_set_gru_h2i": (None, [C.c_int]),
+    "dtc_get_gru_h2i": (C.c_int, []),
+    "dtc_gru_h2i_workspace": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "dtc_gru_h2i_dgh_offset": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "dtc_gru_fwd_h2i": (C.c_int, [c_f32p] * 7 + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, c_stream]),
+    "dtc_gru_bwd_h2i": (C.c_int, [c_f32p] * 7 + [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_int, c_stream]),
+    "dtc_gru_h2i_image_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "dtc_gru_h2i_image": (C.c_int, [c_f32p, C.c_void_p, C.c_int, C.c_int, c_stream]),
+    "dtc_gru_step_fwd_h2i": (C.c_int, [C.c_void_p, c_f32p, C.c_void_p] + [c_f32p] * 5 + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p,
+                                                                                                          C.c_int, C.c_int, c_stream]),
+    "dtc_gru_dgrad_parts_h2i": (C.c_int, [C.c_void_p, C.c_void_p, c_f32p, C.c_int64, C.c_int, C.c_int, C.c_int, c_stream]),
     "dtc_set_concurrency_hint": (None, [C.c_int]),
     "dtc_lstm_workspace": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "dtc_lstm_fwd": (C.c_int, [c_f32p] * 8 + [C.c_void_p, C.c_int, C.c_int, C.c_int, c_stream]),

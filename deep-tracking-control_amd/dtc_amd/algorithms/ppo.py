@@ -227,6 +227,7 @@ class _StepWorkspace(_Lanes):
         super().__init__(dev)
         self.B, self._dev = B, dev
         self._g, self._imgs, self.live_img = {}, {}, set()
+        self.slot_rows = {}                   # padded slot -> valid row maps of the recurrent heads (recurrent_heads.GruHead), by slot name
         self.pad = PaddedBuffers(grow_padded)
         self.wg = self.gws = self.gws2 = self.gws_img = None
         self.pending, self.held = [], []      # queued weight-gradient jobs; operands of flushed jobs (alive until the join)

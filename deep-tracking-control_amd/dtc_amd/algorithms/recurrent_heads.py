@@ -7,6 +7,11 @@ critic's on the `aux` lane, the actor's on main; with DTC_GRU_MULTI=1 the two re
 (ops.gru_fwd_multi / gru_bwd_multi: one launch per time step for both).  Backward: MLP -> row scatter into the padded layout ->
 dtc_gru_bwd -> the recurrence's weight gradients over the valid rows (dgh_all taken from dtc_gru_bwd's workspace, dgi and h_{t-1}
 gathered into images).  Every weight gradient leaves as a job (dZimg, Ximg, gW, wcol0, gb) for the trainer's `sink`.
+
+With DTC_GRU_H2I=1 (dtc_set_gru_h2i; opt-in) the recurrence itself runs on operand images (csrc/gru_h2i.hip: ops.gru_fwd_h2i /
+gru_bwd_h2i) and its kernels write the valid-row images the rest of the step reads -- hx, hp and the gate-gradient images -- through
+`slot_row`, the inverse of `unpad_idx`: none of the packs above is launched.  The two heads then stay on their two lanes:
+DTC_GRU_MULTI and DTC_GRU_SEQ* are ignored.
 """
 from __future__ import annotations
 
@@ -52,9 +57,34 @@ class GruHead:
         ops.scatter_rows(gi_v, self.unpad_idx, self.gi)
         self.hs_all = torch.empty(T + 1, R, H, device=self.dev)
         self.gates, self.hn = torch.empty(T, R, 3 * H, device=self.dev), torch.empty(T, R, H, device=self.dev)
+        self.on_images = ops.gru_h2i_on()
+        if self.on_images:
+            # the forward kernels write h_t straight into the MLP's input image (hs_all[1:] un-padded) and into the h_{t-1} operand of
+            # the W_hh weight gradient (hs_all[:T] un-padded): every one of the M rows, in every step
+            self.ws = ops.workspace(ops.gru_h2i_workspace_bytes(T, R, H), self.dev)
+            self.slot_row = self._slot_row()
+            self.hxi, self.hpi = self._img("hx_", H), self._img("hp_", H)
+            ops.gru_fwd_h2i(*self.fwd_item(), self.slot_row, self.hxi, self.hpi)
+            return
         self.ws = ops.workspace(ops.gru_workspace_bytes(T, R, H), self.dev)
         if run:
             ops.gru_fwd(*self.fwd_item())
+
+    def _img(self, prefix, width):
+        """A valid-row image the recurrence kernels write: exactly M rows, so that no row keeps what an earlier step left there."""
+        im = self.tw.img(prefix + self.name, width)
+        if im.M != self.M:
+            raise _ffi.DtcError(f"image {prefix + self.name} has {im.M} rows, the mini-batch {self.M}: the step workspace must be the mini-batch's")
+        return im
+
+    def _slot_row(self):
+        """int32 [T * R]: the valid row of each padded slot or -1, built on the device once per update and mini-batch slot (the generator
+        yields the same trajectories in every epoch), per head: each head builds and reads its own on its own lane."""
+        name, fresh = self.slots.once("slot_row_" + self.name)
+        cache = self.tw.slot_rows
+        if fresh or name not in cache or cache[name].numel() != self.T * self.R:
+            cache[name] = ops.gru_slot_row(self.unpad_idx, self.T * self.R)
+        return cache[name]
 
     def fwd_item(self):
         return (self.gi.view(self.T, self.R, 3 * self.H), self.h0, self.mem.W_hh, self.mem.b_hh, self.hs_all, self.gates, self.hn, self.ws)
@@ -63,7 +93,7 @@ class GruHead:
         """The MLP on the un-padded recurrence outputs (a row-gathered image); its hidden activations leave as fp32 (ELU derivative) AND
         as images."""
         tw, name, H = self.tw, self.name, self.H
-        hx = tw.img("hx_" + name, H).pack(self._rows(self.hs_all[1:].reshape(self.T * self.R, H), 0, H), self.M)
+        hx = self.hxi if self.on_images else tw.img("hx_" + name, H).pack(self._rows(self.hs_all[1:].reshape(self.T * self.R, H), 0, H), self.M)
         self.outs, self.imgs = [], [hx]
         for li, L in enumerate(self.layers):
             o = tw.g(f"{name}_o{li}", L.n_out)
@@ -91,6 +121,14 @@ class GruHead:
         self.dhs = tw.padded("dhs_" + name, T * R, H, slots=self.slots)
         ops.scatter_rows(d_in, self.unpad_idx, self.dhs)
         self.dgi, self.dh0 = torch.empty(T, R, 3 * H, device=self.dev), torch.empty(R, H, device=self.dev)
+        if self.on_images:
+            # the gate kernel writes the un-padded rows of dgh / dgi as the images recurrence_grads() hands to `sink`
+            if self.dgi_image:
+                self.gimgs = dict(dgh=self._img("dgh_", 3 * H), dgi_img=self._img("dgi_", 3 * H))
+            else:
+                self.gimgs = dict(drz=self._img("drz_", 2 * H), dnh=self._img("dnh_", H), dni=self._img("dni_", H))
+            ops.gru_bwd_h2i(*self.bwd_item(), self.slot_row, **self.gimgs)
+            return
         if run:
             ops.gru_bwd(self.dhs.view(T, R, H), self.hs_all, self.gates, self.hn, self.mem.W_hh, self.dgi, None, None, self.dh0, self.ws)
 
@@ -100,6 +138,18 @@ class GruHead:
     def recurrence_grads(self):
         """Behind the BPTT: the weight-gradient jobs of W_hh and W_ih over the valid rows."""
         tw, mem, name, T, R, H, M, sink = self.tw, self.mem, self.name, self.T, self.R, self.H, self.M, self.sink
+        if self.on_images:
+            hpi, gi = self.hpi, self.gimgs
+            if self.dgi_image:
+                self.dgii = gi["dgi_img"]
+                sink(gi["dgh"], hpi, mem.gW_hh, 0, mem.gb_hh)
+                for i, (xi, c0) in enumerate(zip(self.X, self.cols)):
+                    sink(self.dgii, xi, mem.gW_ih, c0, mem.gb_ih if i == 0 else None)
+                return
+            for X, gW, gb, ni in ((hpi, mem.gW_hh, mem.gb_hh, gi["dnh"]), (self.X, mem.gW_ih, mem.gb_ih, gi["dni"])):
+                sink(gi["drz"], X, gW[:2 * H], 0, gb[:2 * H])
+                sink(ni, X, gW[2 * H:], 0, gb[2 * H:])
+            return
         hpi = tw.img("hp_" + name, H).pack(self._rows(self.hs_all[:T].reshape(T * R, H), 0, H), M)
         dgh, dgi = ops.gru_dgh_all(self.ws, T, R, H), self.dgi.view(T * R, 3 * H)
         if self.dgi_image:
@@ -122,7 +172,10 @@ def forward_backward(tw, critic, actor, critic_input, actor_input, loss, multi, 
     head's input projection, called on its lane (the actor's once the critic's projection is out: the composite runs its encoders
     there); loss(mean, value) -> (dmean, dval), on main between the passes; done(head), if given, on the head's lane once its last
     weight-gradient job is out.  `multi`: DTC_GRU_MULTI."""
-    multi_fwd = multi or seq_pair(actor.T, actor.R, actor.H)
+    if ops.gru_h2i_on():
+        multi = multi_fwd = False                   # the image recurrences run per head, each on its lane
+    else:
+        multi_fwd = multi or seq_pair(actor.T, actor.R, actor.H)
     with tw.lane("aux"):
         critic.project(*critic_input(), run=not multi_fwd)
     actor.project(*actor_input(), run=not multi_fwd)

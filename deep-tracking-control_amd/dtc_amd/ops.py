@@ -807,6 +807,62 @@ def gru_dgh_all(ws, T, R, H):
     return ws.view(torch.float32)[off // 4: off // 4 + T * R * 3 * H].view(T * R, 3 * H)
 
 
+def gru_h2i_on() -> bool:
+    """The recurrent trainers' GRU heads run their recurrence on operand images (DTC_GRU_H2I=1 / dtc_set_gru_h2i)."""
+    return bool(lib().dtc_get_gru_h2i())
+
+
+def gru_h2i_workspace_bytes(T, R, H) -> int:
+    n = int(lib().dtc_gru_h2i_workspace(T, R, H))
+    if n <= 0:
+        raise _ffi.DtcError(f"dtc_gru_h2i_workspace: unsupported shape T={T} R={R} H={H} (H must be a multiple of 128, at most 2048)")
+    return n
+
+
+def gru_slot_row(unpad_idx, n_slots):
+    """int32 [n_slots]: the valid row of every padded slot, or -1 -- the inverse of `unpad_idx` (valid row -> padded slot), built on the
+    device."""
+    slot = torch.full((int(n_slots),), -1, dtype=torch.int32, device=unpad_idx.device)
+    slot[unpad_idx] = torch.arange(unpad_idx.numel(), dtype=torch.int32, device=unpad_idx.device)
+    return slot
+
+
+def _img_ptr(im, M, K):
+    if im is None:
+        return None
+    assert im.M == M and im.K == K, ((im.M, im.K), (M, K))
+    return im.ptr()
+
+
+def gru_fwd_h2i(gi, h0, W_hh, b_hh, hs_all, gates, hn, ws, slot_row=None, hx=None, hp=None):
+    """gru_fwd on operand images (dtc_gru_fwd_h2i; ws: gru_h2i_workspace_bytes).  slot_row (gru_slot_row) with hx / hp (HImage [M, H]):
+    h_t also lands as row slot_row[t, r] of hx (hs_all[1:] un-padded) and h_{t-1} as that row of hp (hs_all[:T] un-padded)."""
+    T, R, H3 = gi.shape
+    H = H3 // 3
+    M = max((im.M for im in (hx, hp) if im is not None), default=0)
+    check(lib().dtc_gru_fwd_h2i(cptr(gi, f32), cptr(h0, f32), cptr(W_hh, f32), cptr(b_hh, f32), cptr(hs_all, f32), cptr(gates, f32),
+                                cptr(hn, f32), ptr(ws), cptr(slot_row, torch.int32), M, _img_ptr(hx, M, H), _img_ptr(hp, M, H), T, R, H,
+                                stream()), "dtc_gru_fwd_h2i")
+
+
+def gru_bwd_h2i(dhs, hs_all, gates, hn, W_hh, dgi, dh0, ws, slot_row=None, drz=None, dnh=None, dni=None, dgh=None, dgi_img=None):
+    """gru_bwd (without the W_hh weight gradient) on operand images (dtc_gru_bwd_h2i; ws: the forward call's).  With slot_row, the
+    un-padded rows of dgh / dgi land in the given HImages: drz [M, 2H], dnh / dni [M, H], dgh / dgi_img [M, 3H]."""
+    T, R, H = dhs.shape
+    imgs = (drz, dnh, dni, dgh, dgi_img)
+    M = max((im.M for im in imgs if im is not None), default=0)
+    check(lib().dtc_gru_bwd_h2i(cptr(dhs, f32), cptr(hs_all, f32), cptr(gates, f32), cptr(hn, f32), cptr(W_hh, f32), cptr(dgi, f32),
+                                cptr(dh0, f32), ptr(ws), cptr(slot_row, torch.int32), M, _img_ptr(drz, M, 2 * H), _img_ptr(dnh, M, H),
+                                _img_ptr(dni, M, H), _img_ptr(dgh, M, 3 * H), _img_ptr(dgi_img, M, 3 * H), T, R, H, stream()),
+          "dtc_gru_bwd_h2i")
+
+
+def gru_dgh_all_h2i(ws, T, R, H):
+    """dgh_all [T * R, 3H] (fp32) inside the workspace of a gru_bwd_h2i call, as gru_dgh_all for gru_bwd."""
+    off = int(lib().dtc_gru_h2i_dgh_offset(T, R, H))
+    return ws.view(torch.float32)[off // 4: off // 4 + T * R * 3 * H].view(T * R, 3 * H)
+
+
 def lstm_workspace_bytes(T, R, H) -> int:
     return int(lib().dtc_lstm_workspace(T, R, H))
 

@@ -867,6 +867,48 @@ int dtc_gru_seq_fwd(const float* gi, const float* h0, const float* W_hh, const f
 int dtc_gru_seq_fwd_pair(const float* const* gi, const float* const* h0, const float* const* W_hh, const float* const* b_hh,
                          float* const* hs_all, float* const* gates, float* const* hn, void* const* seq_ws, int T, int R, int H, void* stream);
 
+/* The recurrence on block-scaled two-term fp16 operand images (csrc/gru_h2i.hip; H a multiple of 128, at most 2048; any R, T >= 1): the
+ * GRU of `Memory` (actor_critic_recurrent.py:92-116) over the padded trajectories of utils/utils.py:33-70, every per-step product from two
+ * images by LDS-DMA (three fp16 MFMA passes, nothing converted in a K loop), and the results the rest of the policy step consumes written
+ * as image rows by the kernels that produce them.  OPT-IN: DTC_GRU_H2I=1 or dtc_set_gru_h2i(1) (0 = off, -1 = back to the environment's
+ * choice, default off); the switch is read by the recurrent trainers (dtc_amd/algorithms/recurrent_heads.py), dtc_gru_fwd / dtc_gru_bwd
+ * never take this path by themselves. */
+void dtc_set_gru_h2i(int on);
+int dtc_get_gru_h2i(void);
+/* Workspace of dtc_gru_fwd_h2i / dtc_gru_bwd_h2i (actor_critic_recurrent.py:92-116, utils/utils.py:33-70), 256-byte aligned; its own
+ * size -- dtc_gru_workspace() does not include it.  dgh_all [T,R,3H] (fp32, the gradient w.r.t. the recurrent pre-activations) sits at
+ * workspace + dtc_gru_h2i_dgh_offset() once the backward call has run, as dtc_gru_dgh_offset() for dtc_gru_bwd. */
+int64_t dtc_gru_h2i_workspace(int T, int R, int H);
+int64_t dtc_gru_h2i_dgh_offset(int T, int R, int H);
+/* Forward pass of the GRU (actor_critic_recurrent.py:92-116) over padded trajectories (utils/utils.py:33-70), operands and outputs as
+ * dtc_gru_fwd.  Row r of h_t carries ONE exponent for the whole call, e_r = min(14, 14 - floor(log2 max|finite h0[r, :]|)): |h_t| <=
+ * max(1, max|h0 row|) for a GRU, so nothing overflows fp16 and no block maximum is needed.  slot_row (int32 [T * R], may be NULL): the
+ * valid row of padded slot (t, r), or -1 -- the inverse of the trainers' unpad_idx.  With it, h_t is also written as row slot_row[t, r]
+ * of hx_img = image(M_valid, H) of hs_all[1:] un-padded, and h_{t-1} (h0 at t = 0) as row slot_row[t, r] of hp_img = image(M_valid, H) of
+ * hs_all[:T] un-padded; either image may be NULL.  Rows no slot names keep what the caller put there (HImage: "nothing here"). */
+int dtc_gru_fwd_h2i(const float* gi, const float* h0, const float* W_hh, const float* b_hh, float* hs_all, float* gates, float* hn,
+                    void* workspace, const int32_t* slot_row, int M_valid, void* hx_img, void* hp_img, int T, int R, int H, void* stream);
+/* BPTT of the same recurrence (actor_critic_recurrent.py:92-116 under the padded layout of utils/utils.py:33-70) without the W_hh weight
+ * gradient: dgi [T,R,3H], dh0 [R,H] and dgh_all in the workspace as dtc_gru_bwd with dW_hh == NULL; same gate arithmetic and summation
+ * order.  With slot_row, the rows of the head's weight-gradient operands are written as images too, true exponents per row and block of 128
+ * columns, each pointer may be NULL: drz_img = image(M_valid, 2H) of dgh[:, :2H] (= dgi[:, :2H]), dnh_img / dni_img = image(M_valid, H) of
+ * dgh[:, 2H:] / dgi[:, 2H:], dgh_img / dgi_img = image(M_valid, 3H) of dgh / dgi. */
+int dtc_gru_bwd_h2i(const float* dhs, const float* hs_all, const float* gates, const float* hn, const float* W_hh, float* dgi, float* dh0,
+                    void* workspace, const int32_t* slot_row, int M_valid, void* drz_img, void* dnh_img, void* dni_img, void* dgh_img,
+                    void* dgi_img, int T, int R, int H, void* stream);
+/* The single steps of the two calls above (actor_critic_recurrent.py:92-116, utils/utils.py:33-70), as dtc_gru_s3_image /
+ * dtc_gru_step_fwd_s3 / dtc_gru_dgrad_parts_s3.  dtc_gru_h2i_image: W_hh -> image with one exponent per image row and block of 128
+ * reduction columns (backward = 0: tiles of 32 units x (r | z | n); 1: W_hh^T, tiles of 128 columns of dh), dtc_gru_h2i_image_bytes() bytes.
+ * dtc_gru_step_fwd_h2i: one time step from hprev_img = image(R, H) of h_{t-1} (any exponents) and hprev (fp32, the z * h_{t-1} term);
+ * hout_img / hx_img / hp_img (each may be NULL) receive h_t with the exponent row_exp[r] -- hout_img's exponent table is the caller's.
+ * dtc_gru_dgrad_parts_h2i: chunk c of dgh_t W_hh from dgh_img = image(R, 3H) -> part + c * part_stride; (3H / nparts) a multiple of 16. */
+int64_t dtc_gru_h2i_image_bytes(int H, int backward);
+int dtc_gru_h2i_image(const float* W_hh, void* img, int H, int backward, void* stream);
+int dtc_gru_step_fwd_h2i(const void* hprev_img, const float* hprev, const void* wimg, const float* b_hh, const float* gi_t, float* hout,
+                         float* gates_t, float* hn_t, void* hout_img, const int32_t* row_exp, const int32_t* slot_x, const int32_t* slot_p,
+                         int M_valid, void* hx_img, void* hp_img, int R, int H, void* stream);
+int dtc_gru_dgrad_parts_h2i(const void* dgh_img, const void* wimg, float* part, int64_t part_stride, int R, int H, int nparts, void* stream);
+
 /* Several recurrences of ONE shape (T, R, H) advanced together -- the actor's and the critic's `Memory` of ActorCriticRecurrent
  * (actor_critic_recurrent.py:45-46: memory_a, memory_c; both are evaluated on the same mini-batch of padded trajectories,
  * ppo.py:265-272): with count == 2 every time step is ONE launch for both (a time step of one recurrence is a latency-bound launch of
