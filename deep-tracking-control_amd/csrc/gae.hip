@@ -233,6 +233,10 @@ extern "C" int dtc_pack_cols(const DtcSegMat* X, float* dst, int64_t ld_dst, int
     int cols = 0;
     for (int i = 0; i < X->nseg; ++i) {
         DTC_REQUIRE(X->seg[i].ptr && X->seg[i].width > 0 && (!X->seg[i].gather || X->idx), "segment %d: null source / gather without idx", i);
+        DTC_REQUIRE(X->seg[i].rows * X->seg[i].ld < (1ll << 29),
+                    "dtc_pack_cols, segment %d: source of %lld x %lld floats is beyond 2^29 elements (2 GiB); only the operand-image path "
+                    "(dtc_h2i_pack, the target of dtc_linear_fwd_mse_h2i) takes sources beyond 2 GiB", i, (long long)X->seg[i].rows,
+                    (long long)X->seg[i].ld);
         cols += X->seg[i].width;
     }
     DTC_REQUIRE(cols == X->cols, "segments cover %d columns, descriptor says %d", cols, X->cols);

@@ -981,7 +981,7 @@ static int linear_fwd_impl(const DtcSegMat* X, const float* W, const float* b, f
     DTC_REQUIRE(act >= 0 && act <= DTC_ACT_SIGMOID, "bad activation %d", act);
     DTC_REQUIRE((long long)N * K <= MAX_ELEMS && (long long)M * ldy <= MAX_ELEMS * 4, "matrix too large");
     SegMatDev xd;
-    int rc = to_dev(X, xd, K, false, M);
+    int rc = to_dev(X, xd, K, false, M, "dtc_linear_fwd");
     if (rc != DTC_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int bn = wide_tiles(M, N) ? 128 : pick_bn_rows(M, N);
@@ -1050,7 +1050,7 @@ extern "C" int dtc_linear_fwd_mse(const DtcSegMat* X, const float* W, const floa
                 tcol0 + N, (long long)ldt);
     DTC_REQUIRE((long long)N * K <= MAX_ELEMS && (long long)M * lddy <= MAX_ELEMS && target_rows * ldt <= MAX_ELEMS, "matrix too large");
     SegMatDev xd;
-    int rc = to_dev(X, xd, K, false, M);
+    int rc = to_dev(X, xd, K, false, M, "dtc_linear_fwd_mse");
     if (rc != DTC_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int grid = grid_for((int)dtc::ceil_div(M, BM), (int)dtc::ceil_div(N, 64));
@@ -1096,7 +1096,7 @@ static int linear_dgrad_impl(const float* dZ, int64_t lddz, const float* W, cons
     DTC_REQUIRE((long long)N * K <= MAX_ELEMS && (long long)M * lddz <= MAX_ELEMS, "matrix too large");
     DTC_REQUIRE(act == DTC_ACT_NONE || (long long)M * ldxs <= MAX_ELEMS, "saved activation matrix too large");
     SegMatDev xd;
-    int rc = to_dev(dX, xd, K, true, 0);
+    int rc = to_dev(dX, xd, K, true, 0, "dtc_linear_dgrad");
     if (rc != DTC_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     int col_skip = 0;

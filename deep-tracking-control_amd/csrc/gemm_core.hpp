@@ -199,7 +199,16 @@ __device__ __forceinline__ f32x4 patch_get(const float* patch, int row, int c4) 
 
 constexpr long long MAX_ELEMS = (1ll << 29) - 1;     // lane byte offsets must stay below 2 GiB (INVALID = 2^31)
 
-int to_dev(const DtcSegMat* h, SegMatDev& d, int expect_cols, bool is_output, long long rows_bound) {
+// a source segment whose matrix the 32-bit lane offsets cannot span: only the kernels with 64-bit lane addresses take it (wide_ok)
+inline bool seg_is_wide(const DtcSeg& hs) { return hs.rows * hs.ld > MAX_ELEMS; }
+inline bool any_wide(const DtcSegMat* h) {
+    for (int i = 0; i < h->nseg; ++i)
+        if (seg_is_wide(h->seg[i])) return true;
+    return false;
+}
+
+// `who`: the entry point (named in the size errors); wide_ok: the caller's kernels address sources of 2 GiB and more (dtc_h2i_pack only)
+int to_dev(const DtcSegMat* h, SegMatDev& d, int expect_cols, bool is_output, long long rows_bound, const char* who, bool wide_ok = false) {
     DTC_REQUIRE(h != nullptr, "segmented matrix is null");
     DTC_REQUIRE(h->nseg >= 1 && h->nseg <= 4, "nseg=%d out of range", h->nseg);
     d.nseg = h->nseg;
@@ -209,13 +218,20 @@ int to_dev(const DtcSegMat* h, SegMatDev& d, int expect_cols, bool is_output, lo
         SegDev& s = d.s[i];
         if (i < h->nseg) {
             const DtcSeg& hs = h->seg[i];
+            const bool wide = wide_ok && !is_output;
             DTC_REQUIRE(hs.width > 0 && hs.col0 >= 0, "segment %d: bad width/col0", i);
             DTC_REQUIRE(is_output || hs.ptr != nullptr, "segment %d: null source", i);
             DTC_REQUIRE(!hs.gather || h->idx != nullptr, "segment %d: gather without idx", i);
             DTC_REQUIRE(!(is_output && hs.gather), "segment %d: gathered destination unsupported", i);
-            DTC_REQUIRE(hs.gather || hs.ld * rows_bound <= MAX_ELEMS, "segment %d: matrix exceeds 2^29 elements (2 GiB)", i);
-            DTC_REQUIRE(is_output || (hs.rows > 0 && hs.rows * hs.ld <= MAX_ELEMS && (hs.gather || hs.rows >= rows_bound)),
-                        "segment %d: rows=%lld (source matrix rows) missing, too small or beyond 2^29 elements", i, (long long)hs.rows);
+            DTC_REQUIRE(hs.gather || wide || hs.ld * rows_bound <= MAX_ELEMS,
+                        "%s, segment %d: matrix exceeds 2^29 elements (2 GiB); only the operand-image path (dtc_h2i_pack, the target of "
+                        "dtc_linear_fwd_mse_h2i) takes sources beyond 2 GiB", who, i);
+            DTC_REQUIRE(is_output || (hs.rows > 0 && (hs.gather || hs.rows >= rows_bound)), "%s, segment %d: rows=%lld (source matrix rows) missing or too small",
+                        who, i, (long long)hs.rows);
+            DTC_REQUIRE(is_output || wide || !seg_is_wide(hs),
+                        "%s, segment %d: source of %lld x %lld floats is beyond 2^29 elements (2 GiB); only the operand-image path (dtc_h2i_pack, "
+                        "the target of dtc_linear_fwd_mse_h2i) takes sources beyond 2 GiB", who, i, (long long)hs.rows, (long long)hs.ld);
+            DTC_REQUIRE(is_output || (hs.rows < (1ll << 31) && hs.ld < (1ll << 31)), "%s, segment %d: rows / row stride beyond 2^31", who, i);
             DTC_REQUIRE(is_output || hs.col0 + hs.width <= hs.ld, "segment %d: columns [%d, %d) outside the %lld-wide source", i,
                         hs.col0, hs.col0 + hs.width, (long long)hs.ld);
             s.ptr = hs.ptr;

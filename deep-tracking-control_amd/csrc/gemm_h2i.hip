@@ -40,6 +40,16 @@ struct PackArgs {
     u32x4* img;
     int* exps;
 };
+// 16 bytes from a dword-aligned address (the rollout's rows are 5556 bytes): one global_load_dwordx4
+typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
+__device__ __forceinline__ f32x4 gload4u(const float* p) {
+    const f32x4u v = *reinterpret_cast<const f32x4u*>(p);
+    return f32x4{v[0], v[1], v[2], v[3]};
+}
+// WIDE: some source segment spans 2 GiB or more -- a lane's byte offset no longer fits the 32-bit offset of a buffer load, and every lane
+// has its own (gathered) row, so no uniform rebase of the descriptor helps: 64-bit lane addresses, the tails and rows outside the source
+// skipped by predicate (they read nothing and yield 0, as the INVALID offset does).  Sources below 2 GiB never take this instantiation.
+template <bool WIDE>
 __global__ __launch_bounds__(256) void h2i_pack_kernel(const PackArgs P) {
     const int tr = blockIdx.x / P.kbs, kb = blockIdx.x - tr * P.kbs;
     const int tid = threadIdx.x, r = tid & 127, h = __builtin_amdgcn_readfirstlane(tid >> 7);
@@ -57,7 +67,17 @@ __global__ __launch_bounds__(256) void h2i_pack_kernel(const PackArgs P) {
         const int sg = find_seg(X, c);
         const SegDev sd = X.s[sg];
         const long long row = sd.gather ? src_row : (long long)m;
-        if (c + 8 <= sd.start + sd.width) {                    // the 8 columns lie in one block: two 16-byte loads (dword-aligned)
+        if (WIDE && c + 8 <= sd.start + sd.width) {            // the same two 16-byte loads through a 64-bit lane address
+            if (m < P.M && (unsigned long long)row < (unsigned long long)sd.rows) {
+                const float* p = sd.ptr + (row * sd.ld + sd.col0 + (c - sd.start));
+                const f32x4 a = gload4u(p), b = gload4u(p + 4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    v[s][e] = a[e];
+                    v[s][4 + e] = b[e];
+                }
+            }
+        } else if (c + 8 <= sd.start + sd.width) {             // the 8 columns lie in one block: two 16-byte loads (dword-aligned)
             const rsrc_t res = make_rsrc_bytes(sd.ptr, (long long)sd.rows * sd.ld * 4);
             const u32 off = m < P.M ? (u32)((row * sd.ld + sd.col0 + (c - sd.start)) * 4) : INVALID;
             const f32x4 a = bload4(res, off, 0u), b = bload4(res, off, 16u);
@@ -360,7 +380,7 @@ struct TileArgs {
 typedef const AS4 TileArgs CTileArgs;
 // TM = 2: 128-row tiles (2 x 2 waves of 64 x 64); TM = 1: 64-row tiles (2 x 2 waves of 32 x 64: half a chunk of the row operand per
 // stage) for the launches whose 128-row tiles would leave CUs without a workgroup (the 128-column layers: 192 tiles on 256 CUs).
-template <int EPI, int TM>
+template <int EPI, int TM, bool WIDE_T = false>
 __device__ __forceinline__ void h2i_tile(CTileArgs& L, const MseEpiH& mse, const int tr, const int tc, const int slot,
                                          unsigned long long* __restrict__ trace) {
     const auto& A = L.A;
@@ -701,8 +721,29 @@ __device__ __forceinline__ void h2i_tile(CTileArgs& L, const MseEpiH& mse, const
                 // e = (acc + bias) - target[tidx[row], tcol0 + col];  dY = e * scale;  partial = sum e^2 (double)
                 const rsrc_t tres = make_rsrc_bytes(mse.target, mse.target_bytes), bres = make_rsrc_bytes(bias, bias ? (long long)N * 4 : 0);
                 const long long src = mse.tidx[row < M ? row : 0];
-                const u32 toff = (u32)((src * mse.ldt + mse.tcol0 + col) * 4) | ((row < M && col < N) ? 0u : INVALID);
-                const f32x4 tg[2] = {bload4(tres, toff, 0u), bload4(tres, toff, 16u)};
+                f32x4 tg[2];
+                if constexpr (WIDE_T) {
+                    // target of 2 GiB or more (WIDE of h2i_pack_kernel): 64-bit lane address; nothing is read behind the row tail, the
+                    // column tail or the target's last element (the buffer loads of the narrow form return 0 there)
+                    tg[0] = tg[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    const unsigned long long e0 = (unsigned long long)(src * mse.ldt + mse.tcol0 + col), te = (unsigned long long)mse.target_bytes >> 2;
+                    if (row < M && col < N && src >= 0) {
+                        const float* tp = mse.target + e0;
+                        if (col + 8 <= N && e0 + 8 <= te) {
+                            tg[0] = gload4u(tp);
+                            tg[1] = gload4u(tp + 4);
+                        } else {
+#pragma unroll
+                            for (int e = 0; e < 8; ++e)
+                                if (col + e < N && e0 + e < te) tg[e >> 2][e & 3] = tp[e];
+                        }
+                    }
+                    (void)tres;
+                } else {
+                    const u32 toff = (u32)((src * mse.ldt + mse.tcol0 + col) * 4) | ((row < M && col < N) ? 0u : INVALID);
+                    tg[0] = bload4(tres, toff, 0u);
+                    tg[1] = bload4(tres, toff, 16u);
+                }
                 const f32x4 bv[2] = {bload4(bres, (u32)col * 4u, 0u), bload4(bres, (u32)col * 4u, 16u)};
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
@@ -907,6 +948,21 @@ __global__ __launch_bounds__(256, 3) void linear_h2i_kernel(const TileArgs L_, c
 #endif
 }
 
+// the loss layer against a target of 2 GiB or more (dtc_linear_fwd_mse_h2i picks it on the host; smaller targets launch
+// linear_h2i_kernel<EPI_MSE, 2> as before)
+__global__ __launch_bounds__(256, 3) void linear_h2i_mse_wide_kernel(const TileArgs L_, const MseEpiH mse, unsigned long long* __restrict__ trace) {
+#ifdef __HIP_DEVICE_COMPILE__
+    CTileArgs& L = *(CTileArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+    (void)L_;
+    int tr, tc;
+    if (!map_tile(blockIdx.x, (L.M + 127) / 128, (L.N + 127) / 128, tr, tc)) {
+        if (threadIdx.x == 0) mse.part[blockIdx.x] = 0.0;
+        return;
+    }
+    h2i_tile<EPI_MSE, 2, true>(L, mse, tr, tc, (int)blockIdx.x, trace);
+#endif
+}
+
 // A chain of up to three layers whose results are at most 128 columns wide (ONE column tile): the workgroup that owns a row tile runs
 // layer after layer on it -- layer l + 1 reads, as its row operand, the image rows this workgroup wrote as layer l's result (global
 // stores ordered by the workgroup barrier between the layers; the rows of other tiles are never touched).  The narrow stacks of the
@@ -1024,18 +1080,24 @@ extern "C" int dtc_h2i_pack(const DtcSegMat* X, int M, void* img, void* stream) 
     int rc = check_img(img, "dtc_h2i_pack");
     if (rc != DTC_OK) return rc;
     PackArgs P;
-    rc = to_dev(X, P.X, X->cols, false, M);
+    rc = to_dev(X, P.X, X->cols, false, M, "dtc_h2i_pack", true);
     if (rc != DTC_OK) return rc;
+    const bool wide = any_wide(X);                       // some source of 2 GiB or more: 64-bit lane addresses
     P.M = M;
     P.K = X->cols;
-    DTC_REQUIRE(hi_bytes(M, P.K) < (1ll << 31), "image beyond 2 GiB");
+    DTC_REQUIRE(hi_bytes(M, P.K) < (1ll << 31), "image of %d x %d beyond 2 GiB: fewer rows per image (more mini-batches)", M, P.K);
     P.stages = (int)hi_stages(P.K);
     P.kbs = (int)hi_kblocks(P.K);
     P.img = (u32x4*)img;
     P.exps = reinterpret_cast<int*>(reinterpret_cast<char*>(img) + hi_data_bytes(M, P.K));
     hipStream_t s = (hipStream_t)stream;
+    if (wide) {
+        dtc::ProfScope prof("h2i_pack_wide", 0.0, s, 8.0 * M * (double)P.K);
+        hipLaunchKernelGGL(h2i_pack_kernel<true>, dim3((unsigned)(hi_rtiles(M) * P.kbs)), dim3(256), 0, s, P);
+        return dtc::check_launch("h2i_pack_wide");
+    }
     dtc::ProfScope prof("h2i_pack", 0.0, s, 8.0 * M * (double)P.K);
-    hipLaunchKernelGGL(h2i_pack_kernel, dim3((unsigned)(hi_rtiles(M) * P.kbs)), dim3(256), 0, s, P);
+    hipLaunchKernelGGL(h2i_pack_kernel<false>, dim3((unsigned)(hi_rtiles(M) * P.kbs)), dim3(256), 0, s, P);
     return dtc::check_launch("h2i_pack");
 }
 
@@ -1202,7 +1264,7 @@ int dgrad_args(const void* dZimg, int N, const void* wimgT, int Kwin, const DtcS
     if (rc != DTC_OK) return rc;
     DgradEpiH& dg = t.dg;
     if (dX) {
-        rc = to_dev(dX, dg.dX, Kwin, true, 0);
+        rc = to_dev(dX, dg.dX, Kwin, true, 0, "dtc_linear_dgrad_h2i");
         if (rc != DTC_OK) return rc;
         dg.has_dx = 1;
         for (int i = 0; i < dg.dX.nseg; ++i) {
@@ -1271,15 +1333,20 @@ extern "C" int dtc_linear_fwd_mse_h2i(const DtcH2iOperand* X, const void* wimg, 
                                       double* sq_part, int M, int N, void* stream) {
     DTC_REQUIRE(target && tidx && sq_part, "null pointer");
     DTC_REQUIRE(tcol0 >= 0 && tcol0 + N <= ldt && target_rows > 0, "target columns [%d, %d) outside its %lld-wide rows", tcol0, tcol0 + N, (long long)ldt);
-    DTC_REQUIRE(target_rows * ldt <= MAX_ELEMS, "matrix too large");
+    DTC_REQUIRE(target_rows < (1ll << 31) && ldt < (1ll << 31), "target rows / row stride beyond 2^31");
+    const bool wide = target_rows * ldt > MAX_ELEMS;     // a target of 2 GiB or more: the epilogue with 64-bit lane addresses
     LayerInfo L;
     int rc = fwd_args(X, wimg, b, dY, lddy, dYimg, nullptr, M, N, (int)DTC_ACT_NONE, L);
     if (rc != DTC_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const MseEpiH mse{target, (const long long*)tidx, (long long)ldt, target_rows * ldt * 4, tcol0, scale, sq_part};
-    dtc::ProfScope prof(dtc::prof_shape_name("linear_fwd", M, N, L.K), L.flop, s, L.bytes + 4.0 * M * N);
-    hipLaunchKernelGGL((linear_h2i_kernel<EPI_MSE, 2>), dim3(grid_for((int)dtc::ceil_div(M, BM), (int)dtc::ceil_div(N, 128))), dim3(256), 0, s, L.t,
-                       mse, g_trace);
+    dtc::ProfScope prof(dtc::prof_shape_name(wide ? "linear_fwd_mse_wide" : "linear_fwd", M, N, L.K), L.flop, s, L.bytes + 4.0 * M * N);
+    if (wide)
+        hipLaunchKernelGGL(linear_h2i_mse_wide_kernel, dim3(grid_for((int)dtc::ceil_div(M, BM), (int)dtc::ceil_div(N, 128))), dim3(256), 0, s, L.t, mse,
+                           g_trace);
+    else
+        hipLaunchKernelGGL((linear_h2i_kernel<EPI_MSE, 2>), dim3(grid_for((int)dtc::ceil_div(M, BM), (int)dtc::ceil_div(N, 128))), dim3(256), 0, s, L.t,
+                           mse, g_trace);
     return dtc::check_launch("linear_fwd_mse_h2i");
 }
 

@@ -829,7 +829,7 @@ int fwd_s3(const DtcSegMat* X, const float* W, const float* b, float* Y, int64_t
     DTC_REQUIRE(act >= 0 && act <= DTC_ACT_SIGMOID, "bad activation %d", act);
     DTC_REQUIRE((long long)N * K <= MAX_ELEMS && (long long)M * ldy <= MAX_ELEMS * 4, "matrix too large");
     SegMatDev xd;
-    int rc = to_dev(X, xd, K, false, M);
+    int rc = to_dev(X, xd, K, false, M, "dtc_linear_fwd_s3 / _h2");
     if (rc != DTC_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int grid = grid_for((int)dtc::ceil_div(M, BM), (int)dtc::ceil_div(N, 128));
@@ -890,7 +890,7 @@ int dgrad_s3(const float* dZ, int64_t lddz, const float* W, const DtcSegMat* dX,
     DTC_REQUIRE((act == DTC_ACT_NONE && !relu_mask) || (dX && dX->nseg == 1), "activation derivative needs a single-segment destination");
     DTC_REQUIRE((long long)N * K <= MAX_ELEMS && (long long)M * lddz <= MAX_ELEMS, "matrix too large");
     DgradEpi dg{};
-    int rc = to_dev(dX, dg.dX, K, true, 0);
+    int rc = to_dev(dX, dg.dX, K, true, 0, "dtc_linear_dgrad_s3 / _h2");
     if (rc != DTC_OK) return rc;
     int col_skip;
     SegMatDev zin;                                    // the row operand of the product: dZ [M, N], one plain segment
@@ -971,7 +971,7 @@ int fwd_mse_s3(const DtcSegMat* X, const float* W, const float* b, const float* 
                 tcol0 + N, (long long)ldt);
     DTC_REQUIRE((long long)N * K <= MAX_ELEMS && (long long)M * lddy <= MAX_ELEMS && target_rows * ldt <= MAX_ELEMS, "matrix too large");
     SegMatDev xd;
-    int rc = to_dev(X, xd, K, false, M);
+    int rc = to_dev(X, xd, K, false, M, "dtc_linear_fwd_mse_s3 / _h2");
     if (rc != DTC_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int grid = grid_for((int)dtc::ceil_div(M, BM), (int)dtc::ceil_div(N, 128));
@@ -1045,7 +1045,7 @@ int wimage_group(const DtcWimgJob* jobs, int count, void* stream, bool h2) {
         SegMatDev xd;
         WimgJobDev& J = G.job[G.count];
         if (h.trans) {
-            int rc = to_dev(h.seg, xd, h.K, true, 0);
+            int rc = to_dev(h.seg, xd, h.K, true, 0, "dtc_wimage_group");
             if (rc != DTC_OK) return rc;
             SegMatDev zin;
             int col_skip;
@@ -1053,7 +1053,7 @@ int wimage_group(const DtcWimgJob* jobs, int count, void* stream, bool h2) {
             DTC_REQUIRE(col_skip < h.K, "job %d: every destination segment is NULL", i);
             wimage_job(J, h.W, h.img, h.K, col_skip, h.K, 1, zin, (int)dtc::ceil_div(h.K - col_skip, 128), h2, (long long)h.N * h.K);
         } else {
-            int rc = to_dev(h.seg, xd, h.K, false, 0);
+            int rc = to_dev(h.seg, xd, h.K, false, 0, "dtc_wimage_group");
             if (rc != DTC_OK) return rc;
             wimage_job(J, h.W, h.img, h.N, 0, h.K, 0, xd, (int)dtc::ceil_div(h.N, 128), h2, (long long)h.N * h.K);
         }
@@ -1093,7 +1093,7 @@ extern "C" int64_t dtc_amax_record_bytes(void) { return AMAX_RECORD_BYTES; }
 extern "C" int dtc_amax(const DtcSegMat* X, int M, uint32_t* slot, void* stream) {
     DTC_REQUIRE(X && slot && M > 0, "null pointer / bad shape");
     SegMatDev xd;
-    int rc = to_dev(X, xd, X->cols, false, M);
+    int rc = to_dev(X, xd, X->cols, false, M, "dtc_amax");
     if (rc != DTC_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     DTC_REQUIRE(hipMemsetAsync(slot, 0, AMAX_RECORD_BYTES, s) == hipSuccess, "hipMemsetAsync failed");

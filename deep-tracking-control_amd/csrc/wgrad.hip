@@ -398,7 +398,7 @@ int plan_group(const DtcWgradJob* jobs, int count, int M, void* workspace, Group
         DTC_REQUIRE(h.dz_rows == 0, "job %d: a row map for dZ (dz_rows) is a feature of the split-precision path (dtc_wgrad_group_s3)", j);
         DTC_REQUIRE((long long)M * h.lddz <= MAX_ELEMS, "job %d: matrix too large", j);
         WJobDev& d = G.job[j];
-        int rc = to_dev(&h.X, d.X, h.K, false, M);
+        int rc = to_dev(&h.X, d.X, h.K, false, M, "dtc_linear_wgrad_group");
         if (rc != DTC_OK) return rc;
         d.dZ = h.dZ;
         d.lddz = h.lddz;
@@ -479,7 +479,7 @@ extern "C" int dtc_linear_wgrad(const float* dZ, int64_t lddz, const DtcSegMat* 
         if (dtc_wgrad_group_s3_workspace(&job, 1, M) <= dtc_linear_wgrad_workspace(M, N, K)) return dtc_wgrad_group_s3(&job, 1, M, workspace, stream);
     }
     SegMatDev xd;
-    int rc = to_dev(X, xd, K, false, M);
+    int rc = to_dev(X, xd, K, false, M, "dtc_linear_wgrad");
     if (rc != DTC_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int bn = pick_bn(K);

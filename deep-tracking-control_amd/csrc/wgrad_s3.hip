@@ -437,7 +437,7 @@ int plan_s3(const DtcWgradJob* jobs, int count, int M, void* workspace, S3Plan& 
         DTC_REQUIRE((h.dz_rows > 0 ? h.dz_rows : (long long)M) * h.lddz <= MAX_ELEMS, "job %d: matrix too large", j);
         DTC_REQUIRE(h.dz_rows >= 0 && (h.dz_rows == 0 || h.X.idx != nullptr), "job %d: dz_rows needs the row map X.idx", j);
         S3Job& d = G.job[j];
-        int rc = to_dev(&h.X, d.X, h.K, false, M);
+        int rc = to_dev(&h.X, d.X, h.K, false, M, "dtc_linear_wgrad_group_s3 / _h2");
         if (rc != DTC_OK) return rc;
         d.dZ = h.dZ;
         d.lddz = h.lddz;

@@ -186,7 +186,7 @@ class DtcProfRec(C.Structure):
 ACT = {None: 0, "none": 0, "relu": 1, "crelu": 1, "elu": 2, "selu": 3, "lrelu": 4, "tanh": 5, "sigmoid": 6}
 MAX_OPERAND_ELEMS = (1 << 29) - 1
 
-ABI_VERSION = 16         # DTC_ABI_VERSION of include/dtc_hip.h this binding was written against
+ABI_VERSION = 17         # DTC_ABI_VERSION of include/dtc_hip.h this binding was written against
 
 _SIGS = {
     "dtc_version": (C.c_int, []),
@@ -435,17 +435,21 @@ def stream() -> int:
 
 
 def seg(t: torch.Tensor | None, col0: int, width: int, gather: bool = False, accumulate: bool = False,
-        ld: int | None = None) -> DtcSeg:
+        ld: int | None = None, wide: bool = False) -> DtcSeg:
     """Column block [col0, col0+width) of a 2-D row-major tensor `t` (row stride = t.stride(0)).  The block remembers `t` (`_keep`):
-    the two-term fp16 path looks the tensor's amax slot up through it (dtc_amd/ops.py: Amax)."""
+    the two-term fp16 path looks the tensor's amax slot up through it (dtc_amd/ops.py: Amax).
+    `wide`: the block is the source of an operand image (h2i.HImage.pack), the one consumer that addresses sources of 2 GiB and
+    more; every other entry point of the library still refuses such a descriptor."""
     s = DtcSeg()
     if t is None:
         s.ptr, s.ld = None, 0
     else:
         assert t.dim() == 2 and t.stride(1) == 1 and t.dtype == torch.float32
-        if t.shape[0] * t.stride(0) > MAX_OPERAND_ELEMS:
+        if t.shape[0] * t.stride(0) > MAX_OPERAND_ELEMS and not wide:
             # the GEMM loaders address an operand with 32-bit byte offsets (buffer loads): a source matrix, gathered
-            # or not, must stay below 2 GiB -- e.g. privileged observations [T*N, 1389]: T*N <= 386 000 rows per GPU
+            # or not, must stay below 2 GiB -- e.g. privileged observations [T*N, 1389]: T*N <= 386 000 rows.  Only the
+            # pack kernel of the operand-image path (and the loss layer's target there) has a 64-bit form: the trainers
+            # pass wide=True where a step runs on images, which lifts the limit to 2^31 rows (32768 envs x 24 steps: 786 432)
             raise DtcError(f"operand of {t.shape[0]} x {t.stride(0)} floats exceeds 2^29 elements (2 GiB); shard the rollout")
         s.ptr, s.ld = ptr(t), (t.stride(0) if ld is None else ld)
         s.rows = t.shape[0]

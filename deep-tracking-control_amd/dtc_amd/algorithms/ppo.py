@@ -856,12 +856,12 @@ class PPO:
             # layer-0 inputs as operand images: the critic's whole input (gathered rollout rows) is packed once; the actor's is the
             # l_t image the terrain encoder just wrote + the packed narrow block [obs | z | mu[:, :3]] (W's columns 72.. and 0..71)
             with tw.lane("aux"):
-                Xc = ac.packed_input(fw, "p_c", ac.critic_input(obs, flat["base_vel"], priv, idx), idx, reuse=True)
+                Xc = ac.packed_input(fw, "p_c", ac.critic_input(obs, flat["base_vel"], priv, idx, wide=True), idx, reuse=True)
             if imn:        # ... as two images: the gathered observations (packed once per update and mini-batch) and the latent kernel's [z | mu[:, :3]]
-                Xa = [fw.img("lt"), ac.packed_input(fw, "p_obs", segmat([seg(obs, 0, ac.num_obs, gather=True)], idx), idx, reuse=True), fw.cur["p_zmu"]]
+                Xa = [fw.img("lt"), ac.packed_input(fw, "p_obs", segmat([seg(obs, 0, ac.num_obs, gather=True, wide=True)], idx), idx, reuse=True), fw.cur["p_zmu"]]
                 a_cols = [ac.num_obs + 19, 0, ac.num_obs]
             else:
-                Xa = [fw.img("lt"), ac.packed_input(fw, "p_a", segmat([seg(obs, 0, ac.num_obs, gather=True), seg(fw.z, 0, 16), seg(fw.mulv, 0, 3)], idx))]
+                Xa = [fw.img("lt"), ac.packed_input(fw, "p_a", segmat([seg(obs, 0, ac.num_obs, gather=True, wide=True), seg(fw.z, 0, 16), seg(fw.mulv, 0, 3)], idx))]
                 a_cols = [ac.num_obs + 19, 0]
         elif self.pack_inputs:                                     # the narrow leading blocks of both layer-0 inputs packed into dense operands
             with tw.lane("aux"):
@@ -1007,11 +1007,13 @@ class PPO:
 
     _AMAX_STATIC = ("observations", "next_observations", "privileged_observations", "observation_histories", "base_vel")
 
-    def _amax_static(self, flat, fw=None):
+    def _amax_static(self, flat, fw=None, images=False):
         """Two-term fp16 GEMM path (ops.H2) on round 4's converting kernels: the rollout tensors that enter GEMMs as gathered operands bring
         the amax of the whole stored tensor -- they do not change during the update, so it is computed once here, before the compute lanes
         fork.  The operand-image chain keeps no amax records at all: where the whole step runs on it (`fw` given and _image_mode(fw), with
-        the narrow layers on images too) the five passes over up to 546 MB are skipped (round 6: 0.33 ms per update)."""
+        the narrow layers on images too) the five passes over up to 546 MB are skipped (round 6: 0.33 ms per update).  `images`: the
+        caller's steps run on operand images; a tensor dtc_amax cannot address (2 GiB and more) is then left without a record, and a
+        kernel that asked for one after all would fail loudly on the tensor's size."""
         if fw is not None and type(self)._ppo_step is PPO._ppo_step and self.narrow_images and self._image_mode(fw):
             ops.amax_static_clear()
             return
@@ -1019,6 +1021,8 @@ class PPO:
             ops.amax_static_clear()
             for k in self._AMAX_STATIC:
                 if k in flat and flat[k].dtype == torch.float32 and flat[k].dim() == 2:
+                    if images and flat[k].shape[0] * flat[k].stride(0) > _ffi.MAX_OPERAND_ELEMS:
+                        continue               # (`images`: the step reads a rollout tensor of 2 GiB and more through image packs only -- no record)
                     ops.amax_static(flat[k])
 
     def _loss_cfg(self):

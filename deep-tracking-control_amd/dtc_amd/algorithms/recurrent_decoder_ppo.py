@@ -255,15 +255,15 @@ class RecurrentDecoderPPO(PPO):
         ha = GruHead(tw, wset, fw.slots, "a", ac.memory_a, ac.A, bt["hid_a"], unpad_idx, T, R, sink, dgi_image=True)
 
         def critic_input():
-            return ac.packed_input(fw, "p_c", ac.critic_input(obs, flat["base_vel"], priv, idx), idx, reuse=True), None
+            return ac.packed_input(fw, "p_c", ac.critic_input(obs, flat["base_vel"], priv, idx, wide=True), idx, reuse=True), None
 
         def actor_input():
             ac.cenet_forward_(fw, flat["observation_histories"], eps, idx, masks=self.relu_masks, split=False, images=imn, wset=wset)
             ac.terrain_encoder_(fw, priv, idx, masks=self.relu_masks, images=True, wset=wset, lt_fp32=False)
             if imn:    # the actor's features as three images: l_t, the gathered observations (packed once), the latent kernel's [z | mu[:, :3]]
-                return ([fw.img("lt"), ac.packed_input(fw, "p_obs", segmat([seg(obs, 0, ac.num_obs, gather=True)], idx), idx, reuse=True),
+                return ([fw.img("lt"), ac.packed_input(fw, "p_obs", segmat([seg(obs, 0, ac.num_obs, gather=True, wide=True)], idx), idx, reuse=True),
                          fw.cur["p_zmu"]], [ac.num_obs + 19, 0, ac.num_obs])
-            return ([fw.img("lt"), ac.packed_input(fw, "p_a", segmat([seg(obs, 0, ac.num_obs, gather=True), seg(fw.z, 0, 16),
+            return ([fw.img("lt"), ac.packed_input(fw, "p_a", segmat([seg(obs, 0, ac.num_obs, gather=True, wide=True), seg(fw.z, 0, 16),
                                                                       seg(fw.mulv, 0, 3)], idx))], [ac.num_obs + 19, 0])
 
         def loss(mean, value):
@@ -304,7 +304,7 @@ class RecurrentDecoderPPO(PPO):
         fw, tw = ac._fwd_ws(B), self._train_ws(B)
         own_gen = fw.slots.gen is None                # outside update(): the packed rollout rows serve this call only
         if own_gen:
-            self._amax_static(flat)                   # (inside update(): once per update -- the storage does not change between mini-batches)
+            self._amax_static(flat, images=self._image_mode(fw) and self._memory_images())      # (inside update(): once per update -- the storage does not change between mini-batches)
         with fw.slots.open() if own_gen else contextlib.nullcontext():
             if own_gen:
                 # (inside update() the device-side learning rate carries the adaptive schedule from mini-batch to mini-batch, ppo.py:301-307:
@@ -341,7 +341,7 @@ class RecurrentDecoderPPO(PPO):
         self.optimizer.set_lr(self.learning_rate)      # once per update: the schedule then lives on the device (lr_dev)
         # amax records of the stored rollout tensors ONCE per update (they were recomputed by every mini-batch: 100 passes over up to
         # 546 MB = 6.5 ms of a 133 ms step)
-        self._amax_static({k: st.flat(k) for k in self._FLAT_NAMES})
+        self._amax_static({k: st.flat(k) for k in self._FLAT_NAMES}, images=self._image_mode(fw) and self._memory_images())
         with fw.slots.open():                    # the slices are the same in every epoch: their packed rollout rows serve all five
             try:
                 for _ in range(epochs):

@@ -43,8 +43,8 @@ class GruHead:
         self.H, self.M, self.dev = mem.hidden_size, unpad_idx.numel(), unpad_idx.device
 
     def _rows(self, t, c0, w):
-        """Columns [c0, c0 + w) of the valid rows of the padded [T * R, .] tensor t, as a row-gathered operand."""
-        return segmat([seg(t, c0, w, gather=True)], self.unpad_idx)
+        """Columns [c0, c0 + w) of the valid rows of the padded [T * R, .] tensor t, as a row-gathered operand (of a pack: it may be wide)."""
+        return segmat([seg(t, c0, w, gather=True, wide=True)], self.unpad_idx)
 
     def project(self, X, cols=None, run=True):
         """Input projection of the valid rows (X: an image or a list of images, `cols`: W_ih's first column for each), scattered into the

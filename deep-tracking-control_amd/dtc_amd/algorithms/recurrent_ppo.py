@@ -276,7 +276,7 @@ class RecurrentPPO:
         once per update into its own buffer; outside an update every call packs."""
         def rows():
             x2 = x.float().contiguous().view(-1, x.shape[-1])     # (the generator's slice of the padded trajectories: copied only here)
-            return segmat([seg(x2, 0, x2.shape[1], gather=True)], unpad_idx)
+            return segmat([seg(x2, 0, x2.shape[1], gather=True, wide=True)], unpad_idx)     # (a pack's source: may span 2 GiB and more)
         return self._slots.packed(self._train_ws(M, dev), name, rows, x.shape[-1], M)
 
     def _wgrad_group(self, tw, jobs):

@@ -27,7 +27,8 @@ class HImage:
         self.M, self.K = int(M), int(K)
         n = int(lib().dtc_h2i_bytes(self.M, self.K))
         if n <= 0 or n >= 1 << 31:
-            raise _ffi.DtcError(f"operand image of a {M} x {K} matrix: {n} bytes (must be in (0, 2 GiB))")
+            raise _ffi.DtcError(f"operand image of a {M} x {K} matrix: {n} bytes (must be in (0, 2 GiB)): {M} rows per mini-batch are "
+                                f"too many for one image, raise num_mini_batches")
         self.buf = torch.zeros((n + 7) // 8, dtype=torch.float64, device=device)      # (zeros: rows behind M read as nothing)
         # exponents start as "nothing here" (HI_EZERO): producers that write only their own rows (the latent / loss kernels) leave the
         # rows behind M of the last row tile marked empty, as the pack kernel and the GEMM epilogues do
@@ -43,7 +44,7 @@ class HImage:
 
     def pack(self, X, M=None):
         """self <- the fp32 operand X (tensor or DtcSegMat: segments side by side, row-gathered where asked)."""
-        Xs = X if isinstance(X, _ffi.DtcSegMat) else segmat([seg(X, 0, X.shape[1])])
+        Xs = X if isinstance(X, _ffi.DtcSegMat) else segmat([seg(X, 0, X.shape[1], wide=True)])
         assert Xs.cols == self.K
         check(lib().dtc_h2i_pack(Xs, self.M if M is None else M, self.ptr(), stream()), "dtc_h2i_pack")
         self._src = Xs                  # the launch reads the descriptor's tensors: keep them until the next pack
@@ -310,6 +311,7 @@ def mse_parts(M, N) -> int:
 
 def linear_fwd_mse(X, W, b, target, tcol0, tidx, dY, dYimg, part, wset=None):
     """The output layer fused with its MSE against target[tidx, tcol0:tcol0 + N]; dL/dY as fp32 `dY` and / or HImage `dYimg`;
+    `target` may span 2 GiB or more (the whole rollout's privileged observations: the library picks its 64-bit target load);
     returns the number of partial sums written to `part` (float64)."""
     op, imgs = _operand(X)
     N = W.shape[0]

@@ -368,7 +368,7 @@ class ActorCriticDecoder(nn.Module):
         update, e1 / e leave as images only (ws.live_img) -- their consumers (next layer, weight gradient) read images --, the heads'
         output as fp32 for the latent kernel."""
         L = self.L
-        X = segmat([seg(hist, 0, hist.shape[1], gather=idx is not None)], idx)
+        X = segmat([seg(hist, 0, hist.shape[1], gather=idx is not None, wide=bool(images and masks))], idx)
         if images and masks:
             pin = self.packed_input(ws, "p_hist", X, idx, reuse=True)
             e1i, ei = ws.img("e1", L["ce0"].n_out), ws.img("e", L["ce1"].n_out)
@@ -410,7 +410,7 @@ class ActorCriticDecoder(nn.Module):
         """`images` (training step, see images_ok): the gathered heights are packed into an operand image once per mini-batch, t1 / t2
         leave as images only (ws.live_img), l_t as an image (+ fp32 for the CE-net decoder: lt_fp32)."""
         L = self.L
-        X = segmat([seg(priv, 0, 693, gather=idx is not None)], idx)
+        X = segmat([seg(priv, 0, 693, gather=idx is not None, wide=bool(images and masks))], idx)     # (wide: an image's source only)
         if images and masks:
             w1, w2 = L["te0"].n_out, L["te1"].n_out
             pin = self.packed_input(ws, "p_te", X, idx, reuse=True)
@@ -429,11 +429,12 @@ class ActorCriticDecoder(nn.Module):
         return segmat([seg(obs, 0, self.num_obs, gather=idx is not None), seg(ws.z, 0, 16), seg(ws.mulv, 0, 3),
                        seg(ws.lt, 0, 512)], idx)
 
-    def critic_input(self, obs, base_vel, priv, idx=None):
+    def critic_input(self, obs, base_vel, priv, idx=None, wide=False):
+        """`wide`: the operand is packed into an operand image (packed_input), whose kernel takes rollouts of 2 GiB and more."""
         g = idx is not None
         # cat[obs, base_vel, priv[:, 693:696], priv[:, 696:]] -- the last two are adjacent columns of `priv`
-        return segmat([seg(obs, 0, self.num_obs, gather=g), seg(base_vel, 0, 3, gather=g),
-                       seg(priv, 693, 696, gather=g)], idx)
+        return segmat([seg(obs, 0, self.num_obs, gather=g, wide=wide), seg(base_vel, 0, 3, gather=g, wide=wide),
+                       seg(priv, 693, 696, gather=g, wide=wide)], idx)
 
     def actor_input_packed(self, ws, obs, idx, buf):
         """The same operand with its three narrow blocks [obs | z | mu[:, :3]] packed into `buf` [B, 72] (one launch): two

@@ -38,7 +38,7 @@ extern "C" {
 #define DTC_ACT_SIGMOID 6
 
 /* library / device info ------------------------------------------------------------------ */
-#define DTC_ABI_VERSION 16                   /* bumped whenever a signature or a by-value struct layout changes       */
+#define DTC_ABI_VERSION 17                   /* bumped whenever a signature or a by-value struct layout changes       */
 int dtc_version(void);                       /* == DTC_ABI_VERSION of the build; the host binding refuses a mismatch   */
 /* sizeof() of the structs that cross the boundary, in the order DtcGridCfg, DtcObsCfg, DtcRowCopy, DtcSeg, DtcSegMat,
    DtcFwdLayer, DtcWgradJob, DtcPpoCfg, DtcProfRec, DtcWimgJob, DtcH2iWJob, DtcH2iOperand, DtcWgradH2iJob, DtcEnvStep, DtcH2iFwdLayer, DtcH2iDgradLayer, DtcGruFwdItem, DtcGruBwdItem: the binding compares them with its own layouts at load time (a library
@@ -432,7 +432,9 @@ typedef struct DtcSeg {
     int32_t accumulate;  /* outputs only: 1 = add into the destination instead of overwriting   */
     int64_t rows;        /* inputs: number of rows of the source matrix (rows*ld floats behind ptr are readable: the
                           * loaders read 16 bytes at a time and bound their buffer descriptor with it -- reads past
-                          * the last row return 0); outputs: unused                                              */
+                          * the last row return 0); outputs: unused.  rows * ld must stay below 2^29 floats (2 GiB) for
+                          * every entry point but dtc_h2i_pack, whose wide-source kernel addresses larger sources with
+                          * 64-bit lane addresses (as does the target of dtc_linear_fwd_mse_h2i)                          */
     uint32_t* amax;      /* two-term fp16 path (dtc_*_h2) only, device pointer.  Inputs: slot that holds the bit pattern of the
                           * largest |x| of the source tensor (or of any superset of the block: an upper bound costs precision only
                           * when it is more than ~2^10 too large), written by dtc_amax or by the kernel that produced the tensor.
