@@ -21,6 +21,9 @@ struct ProfScope {
 
 const char* prof_shape_name(const char* base, int M, int N, int K);
 
+// the logistic function of every gate kernel (one rounding sequence: results of the recurrence kernels are compared bit for bit)
+__device__ __forceinline__ float sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

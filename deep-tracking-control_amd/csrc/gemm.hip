@@ -415,8 +415,6 @@ __global__ __launch_bounds__(256, DEEP ? 3 : (BN == 128 ? 2 : DTC_FWD_WAVES)) vo
 // the same units), so every lane holds the three pre-activations of its (row, unit) pairs.  Same K loop as
 // linear_fwd_kernel (plain single-segment operands).
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 __global__ __launch_bounds__(256, 3) void gru_step_fwd_kernel(const float* __restrict__ hprev, const float* __restrict__ Whh,
                                                            const float* __restrict__ bhh, const float* __restrict__ gi,
                                                            float* __restrict__ hout, float* __restrict__ gates,
@@ -520,8 +518,8 @@ __global__ __launch_bounds__(256, 3) void gru_step_fwd_kernel(const float* __res
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int row = row0 + (r & 3) + 8 * (r >> 2);
-        const float rg = sigmoid_f(gr[r] + (acc[0][r] + br));
-        const float zg = sigmoid_f(gz[r] + (acc[1][r] + bz));
+        const float rg = dtc::sigmoid(gr[r] + (acc[0][r] + br));
+        const float zg = dtc::sigmoid(gz[r] + (acc[1][r] + bz));
         const float ghn = acc[2][r] + bn;
         const float ng = tanhf(gn[r] + rg * ghn);
         if (row < R) {
@@ -646,10 +644,10 @@ __global__ __launch_bounds__(256, 3) void lstm_step_fwd_kernel(const float* __re
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int row = row0 + (r & 3) + 8 * (r >> 2);
-        const float ig = sigmoid_f(gvi[r] + (acc[0][r] + bi));
-        const float fg = sigmoid_f(gvf[r] + (acc[1][r] + bf));
+        const float ig = dtc::sigmoid(gvi[r] + (acc[0][r] + bi));
+        const float fg = dtc::sigmoid(gvf[r] + (acc[1][r] + bf));
         const float gg = tanhf(gvg[r] + (acc[2][r] + bg));
-        const float og = sigmoid_f(gvo[r] + (acc[3][r] + bo));
+        const float og = dtc::sigmoid(gvo[r] + (acc[3][r] + bo));
         const float c = fg * cp[r] + ig * gg;
         if (row < R) {
             const long long e = (long long)row * H + j;

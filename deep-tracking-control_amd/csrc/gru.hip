@@ -20,11 +20,9 @@
 // gradients are zero, so every quantity flowing backwards through them is zero as well.
 #include <stdlib.h>
 
-#include "common.hpp"
+#include "gru_internal.hpp"
 
 namespace {
-
-__device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // one thread per (row, hidden unit)
 __global__ __launch_bounds__(256) void gru_gate_fwd_kernel(const float* __restrict__ gi, const float* __restrict__ gh,
@@ -37,8 +35,8 @@ __global__ __launch_bounds__(256) void gru_gate_fwd_kernel(const float* __restri
     const int j = (int)(e - row * H);
     const float* gir = gi + row * 3 * H;
     const float* ghr = gh + row * 3 * H;
-    const float r = sigmoidf(gir[j] + ghr[j]);
-    const float z = sigmoidf(gir[H + j] + ghr[H + j]);
+    const float r = dtc::sigmoid(gir[j] + ghr[j]);
+    const float z = dtc::sigmoid(gir[H + j] + ghr[H + j]);
     const float ghn = ghr[2 * H + j];
     const float n = tanhf(gir[2 * H + j] + r * ghn);
     const float hp = hprev[e];
@@ -145,7 +143,7 @@ __global__ __launch_bounds__(256) void gru_gate_bwd4_kernel(const GateBwdPtrs p0
     *reinterpret_cast<f4*>(dh + e) = dz4;
 }
 
-// dh0 <- dh0 + the three chunks of the last W_hh product
+// dh0 <- dh0 + the chunks of the last W_hh product
 __global__ __launch_bounds__(256) void gru_add_parts_kernel(float* __restrict__ dh, const float* __restrict__ part, long long rh, int nparts) {
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= rh) return;
@@ -154,206 +152,106 @@ __global__ __launch_bounds__(256) void gru_add_parts_kernel(float* __restrict__ 
     dh[e] = d;
 }
 
-DtcSegMat plain(const float* p, int64_t ld, int cols, int64_t rows) {
-    DtcSegMat m;
-    m.nseg = 1;
-    m.cols = cols;
-    m.idx = nullptr;
-    m.seg[0] = DtcSeg{const_cast<float*>(p), ld, 0, cols, 0, 0, rows};
-    return m;
-}
-
 }  // namespace
 
-// workspace layout: [ gh / the chunks of the W_hh data gradient: MAX_PARTS * R * H floats | dgh_all: T*R*3H floats | wgrad partials |
-// the image of W_hh^T (split-precision path) ]
-constexpr int MAX_PARTS = 6;
+// The dtc_gru_workspace() buffer, as byte offsets from its start -- the only statement of the layout:
+//   part     : gh of the GEMM + gate-kernel forward step / the chunks of the W_hh data gradient, GRU_MAX_PARTS * R * H floats
+//   dgh_all  : [T, R, 3H] floats (dtc_gru_dgh_offset: the trainers read it there)
+//   wgrad_ws : partial sums of the W_hh weight gradient, on a 16-byte boundary
+//   wimage   : the image of W_hh / W_hh^T of the split-precision steps (csrc/gru_s3.hip), on a 16-byte boundary
+//   seq      : the persistent kernels' exchange buffers (csrc/gru_seq.hip), on a 256-byte boundary
+// wgrad_ws and wimage are aligned as ADDRESSES: a `workspace` that itself starts off a 16-byte boundary shifts them inside the
+// 16 spare bytes that `total` counts (workspace == NULL: the offsets inside an aligned buffer).
 namespace {
-// chunks of the 3H-long reduction of dh += dgh W_hh that run side by side: 3 on the single-pass path; the split path runs 128 x 128
-// tiles (4 column tiles for H = 512), so it takes 6 to put ~290 workgroups on the chip (DTC_GRU_S3_PARTS = 1, 2, 3 or 6)
-int gru_parts(int H, bool s3) {
-    if (!s3) return 3;
-    constexpr int env = 6;
-    const int p = (env == 1 || env == 2 || env == 3 || env == 6) ? env : 6;
-    return (3 * H / p) % 16 == 0 ? p : 3;
+using dtc::GRU_MAX_PARTS;
+using dtc::gru_parts;
+using dtc::plain;
+
+struct GruLayout {
+    int64_t part, dgh_all, wgrad_ws, wimage, seq, total;
+};
+GruLayout gru_layout(int T, int R, int H, const void* workspace = nullptr) {
+    const int64_t off = (int64_t)((uintptr_t)workspace & 15), wgrad = (dtc_linear_wgrad_workspace(T * R, 3 * H, H) + 15) & ~(int64_t)15;
+    const int64_t img = dtc_s3_planes_bytes(H, 3 * H) > dtc_gru_s3_image_bytes(H) ? dtc_s3_planes_bytes(H, 3 * H) : dtc_gru_s3_image_bytes(H);
+    GruLayout L;
+    L.part = 0;
+    L.dgh_all = (int64_t)GRU_MAX_PARTS * R * H * sizeof(float);
+    const int64_t end = L.dgh_all + (int64_t)T * R * 3 * H * sizeof(float);
+    L.wgrad_ws = ((off + end + 15) & ~(int64_t)15) - off;
+    L.wimage = L.wgrad_ws + wgrad;
+    L.seq = (end + 16 + wgrad + img + 255) & ~(int64_t)255;
+    L.total = L.seq + dtc_gru_seq_workspace(R, H);
+    return L;
 }
-bool gru_s3(int H) {
-    static const bool on = !(getenv("DTC_S3_WIMG") && atoi(getenv("DTC_S3_WIMG")) == 0) && !(getenv("DTC_GRU_S3") && atoi(getenv("DTC_GRU_S3")) == 0);
-    return dtc_get_gemm_split() && on && H % 128 == 0;
+
+// the environment's switches, each read once (at the first call that asks)
+struct GruSwitches {
+    static bool zero(const char* name) { return getenv(name) && atoi(getenv(name)) == 0; }
+    const bool unfused = getenv("DTC_GRU_UNFUSED") != nullptr;        // set: two-kernel forward step (GEMM + gate kernel)
+    const bool gate_vec = !zero("DTC_GRU_GATE_VEC");                  // 0: one hidden unit per thread in the gate backward
+    const bool multi = !zero("DTC_GRU_MULTI");                        // 0: the *_multi calls never advance two recurrences together
+    const bool s3 = !zero("DTC_S3_WIMG") && !zero("DTC_GRU_S3");      // 0 (either): no split-precision time steps
+};
+const GruSwitches& switches() {
+    static const GruSwitches sw;
+    return sw;
 }
-void* gru_image_slot(void* workspace, int T, int R, int H) {
-    float* dgh_all = (float*)workspace + (size_t)MAX_PARTS * R * H;
-    void* wg_ws = (void*)(((uintptr_t)(dgh_all + (size_t)T * R * 3 * H) + 15) & ~(uintptr_t)15);
-    return (char*)wg_ws + ((dtc_linear_wgrad_workspace(T * R, 3 * H, H) + 15) & ~(int64_t)15);
-}
+bool gru_s3(int H) { return dtc_get_gemm_split() && switches().s3 && H % 128 == 0; }
 }  // namespace
+
 extern "C" int64_t dtc_gru_workspace(int T, int R, int H) {
     if (T <= 0 || R <= 0 || H <= 0) return 0;
-    const int64_t a = (int64_t)R * MAX_PARTS * H * sizeof(float);
-    const int64_t b = (int64_t)T * R * 3 * H * sizeof(float);
-    const int64_t img = dtc_s3_planes_bytes(H, 3 * H) > dtc_gru_s3_image_bytes(H) ? dtc_s3_planes_bytes(H, 3 * H) : dtc_gru_s3_image_bytes(H);
-    const int64_t per_step = a + b + 16 + ((dtc_linear_wgrad_workspace(T * R, 3 * H, H) + 15) & ~(int64_t)15) + img;     // +16: 16-byte alignment
-    return ((per_step + 255) & ~(int64_t)255) + dtc_gru_seq_workspace(R, H);            // + the persistent kernels' exchange buffers (csrc/gru_seq.hip)
+    return gru_layout(T, R, H).total;
 }
-namespace {
-// the persistent kernels' region of a dtc_gru_workspace() buffer (its tail), 256-byte aligned inside the buffer's own alignment
-void* gru_seq_slot(void* workspace, int T, int R, int H) {
-    const int64_t total = dtc_gru_workspace(T, R, H), seq = dtc_gru_seq_workspace(R, H);
-    return (char*)workspace + ((total - seq) & ~(int64_t)255);
-}
-}  // namespace
 
 // byte offset of dgh_all [T, R, 3H] (the gradient w.r.t. the recurrent pre-activations, written by dtc_gru_bwd) inside the workspace
 extern "C" int64_t dtc_gru_dgh_offset(int T, int R, int H) {
-    (void)T;
     if (R <= 0 || H <= 0) return -1;
-    return (int64_t)MAX_PARTS * R * H * (int64_t)sizeof(float);
+    return gru_layout(T, R, H).dgh_all;
 }
 
-extern "C" int dtc_gru_fwd(const float* gi, const float* h0, const float* W_hh, const float* b_hh, float* hs_all,
-                           float* gates, float* hn, void* workspace, int T, int R, int H, void* stream) {
-    DTC_REQUIRE(T > 0 && R > 0 && H > 0, "bad shape T=%d R=%d H=%d", T, R, H);
-    DTC_REQUIRE(gi && h0 && W_hh && b_hh && hs_all && gates && hn && workspace, "null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    float* gh = (float*)workspace;
-    const size_t RH = (size_t)R * H;
-    static const bool unfused = getenv("DTC_GRU_UNFUSED") != nullptr;      // two-kernel step (GEMM + gate kernel)
-    // the whole recurrence as ONE persistent launch (csrc/gru_seq.hip) where the shape is served and the buffers allow 16-byte accesses
-    if (!unfused && dtc_get_gemm_split() && dtc_gru_seq_supported(T, R, H, 0) && dtc::aligned16(gi) && dtc::aligned16(h0) && dtc::aligned16(hs_all) &&
-        dtc::aligned16(gates) && dtc::aligned16(hn) && dtc::aligned16(workspace))
-        return dtc_gru_seq_fwd(gi, h0, W_hh, b_hh, hs_all, gates, hn, gru_seq_slot(workspace, T, R, H), T, R, H, stream);
-    if (hipMemcpyAsync(hs_all, h0, RH * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) {
-        dtc::set_error("gru_fwd: h0 copy failed");
-        return DTC_ERR_LAUNCH;
-    }
-    const unsigned grid = (unsigned)dtc::ceil_div((int64_t)RH, 256);
-    // split-precision steps (csrc/gru_s3.hip) for the passes of the update (T time steps share ONE image of W_hh); the one-step
-    // calls of the rollout keep the single-pass kernel
-    const bool s3 = !unfused && T >= 4 && gru_s3(H);
-    void* img = s3 ? gru_image_slot(workspace, T, R, H) : nullptr;
-    if (s3) {
-        int rc = dtc_gru_s3_image(W_hh, img, H, 0, stream);
-        if (rc != DTC_OK) return rc;
-    }
-    for (int t = 0; t < T; ++t) {
-        const float* hprev = hs_all + (size_t)t * RH;
-        if (s3) {
-            int rc = dtc_gru_step_fwd_s3(hprev, img, b_hh, gi + (size_t)t * R * 3 * H, hs_all + (size_t)(t + 1) * RH,
-                                         gates + (size_t)t * R * 3 * H, hn + (size_t)t * RH, R, H, stream);
-            if (rc != DTC_OK) return rc;
-            continue;
-        }
-        if (!unfused && H % 32 == 0) {
-            int rc = dtc_gru_step_fwd(hprev, W_hh, b_hh, gi + (size_t)t * R * 3 * H, hs_all + (size_t)(t + 1) * RH,
-                                      gates + (size_t)t * R * 3 * H, hn + (size_t)t * RH, R, H, stream);
-            if (rc != DTC_OK) return rc;
-            continue;
-        }
-        const DtcSegMat X = plain(hprev, H, H, R);
-        int rc = dtc_linear_fwd(&X, W_hh, b_hh, gh, 3 * H, R, 3 * H, H, DTC_ACT_NONE, stream);
-        if (rc != DTC_OK) return rc;
-        dtc::ProfScope prof("gru_gate_fwd", (double)RH * 4.0 * 12, s);
-        hipLaunchKernelGGL(gru_gate_fwd_kernel, dim3(grid), dim3(256), 0, s, gi + (size_t)t * R * 3 * H, gh, hprev,
-                           hs_all + (size_t)(t + 1) * RH, gates + (size_t)t * R * 3 * H, hn + (size_t)t * RH, R, H);
-    }
-    return dtc::check_launch("gru_fwd");
+// ---- the two drivers: `count` recurrences of ONE shape, one launch per time step for all of them (count == 2: the actor's and the
+// critic's GRU of ActorCriticRecurrent / ActorCriticDecoderRecurrent: rsl_rl/rsl_rl/modules/actor_critic_recurrent.py:45-46, 92-116).
+// A time step of one recurrence is a latency-bound launch of ~190-290 workgroups; two of them on two streams overlap by ~20 %
+// (tools/gru_pair_probe.py: 1.12 ms for two forward passes against 0.72 for one).  The same two as ONE launch: 1.09 ms -- a launch with
+// twice the workgroups takes 1.5 x as long, and in the trainers the merged chain is slower than two chains on two lanes (DESIGN.md
+// 4.3c): an option, not the default.  Results are bit-identical to the single calls (same kernels, same tiles).  Only the split-path
+// step kernels (and the persistent kernel) take two recurrences: where the shape or a switch rules them out, two recurrences run as
+// the single calls, one after the other.  `who`: the public entry point, for its error messages (which name an item only where the caller
+// passed several).
+namespace {
+int null_pointer(int i, int count) {
+    count == 1 ? dtc::set_error("null pointer") : dtc::set_error("item %d: null pointer", i);
+    return DTC_ERR_ARG;
 }
-
-extern "C" int dtc_gru_bwd(const float* dhs, const float* hs_all, const float* gates, const float* hn, const float* W_hh,
-                           float* dgi, float* dW_hh, float* db_hh, float* dh0, void* workspace, const int64_t* valid_rows, int n_valid,
-                           int T, int R, int H, void* stream) {
+int gru_fwd_run(const char* who, const DtcGruFwdItem* items, int count, int T, int R, int H, void* stream) {
     DTC_REQUIRE(T > 0 && R > 0 && H > 0, "bad shape T=%d R=%d H=%d", T, R, H);
-    DTC_REQUIRE(dhs && hs_all && gates && hn && W_hh && dgi && dh0 && workspace, "null pointer");
-    DTC_REQUIRE((dW_hh == nullptr) == (db_hh == nullptr), "dW_hh and db_hh: both or neither");
+    const GruSwitches& sw = switches();
     hipStream_t s = (hipStream_t)stream;
     const size_t RH = (size_t)R * H, R3H = (size_t)R * 3 * H;
-    float* dgh_all = (float*)workspace + (size_t)MAX_PARTS * RH;
-    void* wg_ws = (void*)(((uintptr_t)(dgh_all + (size_t)T * R3H) + 15) & ~(uintptr_t)15);
-    void* wimage = gru_image_slot(workspace, T, R, H);
-    const bool s3 = gru_s3(H);
-    const int nparts = gru_parts(H, s3);
-    if (s3) {
-        int rc = dtc_gru_s3_image(W_hh, wimage, H, 1, stream);
-        if (rc != DTC_OK) return rc;
+    bool a16 = true;
+    GruLayout L[DTC_GRU_MULTI_MAX];
+    for (int i = 0; i < count; ++i) {
+        const DtcGruFwdItem& it = items[i];
+        if (!(it.gi && it.h0 && it.W_hh && it.b_hh && it.hs_all && it.gates && it.hn && it.workspace)) return null_pointer(i, count);
+        L[i] = gru_layout(T, R, H, it.workspace);
+        a16 = a16 && dtc::aligned16(it.gi) && dtc::aligned16(it.h0) && dtc::aligned16(it.hs_all) && dtc::aligned16(it.gates) &&
+              dtc::aligned16(it.hn) && dtc::aligned16(it.workspace);
     }
-    if (hipMemsetAsync(dh0, 0, RH * sizeof(float), s) != hipSuccess) {
-        dtc::set_error("gru_bwd: memset failed");
-        return DTC_ERR_LAUNCH;
+    // the whole recurrence as ONE persistent launch (csrc/gru_seq.hip) where the shape is served and the buffers allow 16-byte accesses;
+    // two recurrences one after the other inside it -- it may then take every CU
+    if (!sw.unfused && dtc_get_gemm_split() && dtc_gru_seq_supported(T, R, H, count == 2) && a16) {
+        const DtcGruFwdItem &x = items[0], &y = items[count - 1];
+        void* const seq[2] = {(char*)x.workspace + L[0].seq, (char*)y.workspace + L[count - 1].seq};
+        if (count == 1) return dtc_gru_seq_fwd(x.gi, x.h0, x.W_hh, x.b_hh, x.hs_all, x.gates, x.hn, seq[0], T, R, H, stream);
+        const float *gi[2] = {x.gi, y.gi}, *h0[2] = {x.h0, y.h0}, *W[2] = {x.W_hh, y.W_hh}, *b[2] = {x.b_hh, y.b_hh};
+        float *hs[2] = {x.hs_all, y.hs_all}, *gt[2] = {x.gates, y.gates}, *hn[2] = {x.hn, y.hn};
+        return dtc_gru_seq_fwd_pair(gi, h0, W, b, hs, gt, hn, seq, T, R, H, stream);
     }
-    const unsigned grid = (unsigned)dtc::ceil_div((int64_t)RH, 256);
-    float* part = (float*)workspace;              // [nparts][R][H]: the region dtc_gru_fwd uses for gh
-    // four units per thread when every row of every operand starts on a 16-byte boundary (DTC_GRU_GATE_VEC=0: one unit per thread)
-    static const bool vec_on = !(getenv("DTC_GRU_GATE_VEC") && atoi(getenv("DTC_GRU_GATE_VEC")) == 0);
-    auto a16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    const bool vec4 = vec_on && H % 4 == 0 && a16(dhs) && a16(dh0) && a16(part) && a16(gates) && a16(hn) && a16(hs_all) && a16(dgi) && a16(dgh_all);
-    const unsigned grid4 = (unsigned)dtc::ceil_div((int64_t)RH / 4, 256);
-    for (int t = T - 1; t >= 0; --t) {
-        float* dgh_t = dgh_all + (size_t)t * R3H;
-        {
-            dtc::ProfScope prof("gru_gate_bwd", (double)RH * 4.0 * 17, s);
-            if (vec4) {
-                const GateBwdPtrs gp{dhs + (size_t)t * RH, dh0, t == T - 1 ? (const float*)nullptr : (const float*)part, gates + (size_t)t * R3H,
-                                     hn + (size_t)t * RH, hs_all + (size_t)t * RH, dgi + (size_t)t * R3H, dgh_t};
-                hipLaunchKernelGGL(gru_gate_bwd4_kernel, dim3(grid4), dim3(256), 0, s, gp, gp, R, H, nparts);
-            } else
-                hipLaunchKernelGGL(gru_gate_bwd_kernel, dim3(grid), dim3(256), 0, s, dhs + (size_t)t * RH, dh0,
-                                   t == T - 1 ? (const float*)nullptr : (const float*)part, gates + (size_t)t * R3H,
-                                   hn + (size_t)t * RH, hs_all + (size_t)t * RH, dgi + (size_t)t * R3H, dgh_t, R, H, nparts);
-        }
-        // split path: ONE image of W_hh^T serves all T steps
-        int rc = s3 ? dtc_gru_dgrad_parts_s3(dgh_t, wimage, part, (int64_t)RH, R, H, nparts, stream)
-                    : dtc_linear_dgrad_split(dgh_t, 3 * H, W_hh, part, H, (int64_t)RH, R, 3 * H, H, nparts, stream);
-        if (rc != DTC_OK) return rc;
-    }
-    hipLaunchKernelGGL(gru_add_parts_kernel, dim3(grid), dim3(256), 0, s, dh0, part, (long long)RH, nparts);
-    // dW_hh == NULL: the caller forms the W_hh weight gradient itself from dgh_all (workspace + dtc_gru_dgh_offset: the operand-image
-    // trainers pack it with the other operands of their grouped weight-gradient launch)
-    if (dW_hh == nullptr) return dtc::check_launch("gru_bwd");
-    // the padding slots of the padded trajectory layout have dgh = 0: with the caller's list of valid slots the product skips them
-    if (valid_rows && n_valid >= 1024 && n_valid < T * R && dtc_get_gemm_split() && 3ll * H * H >= 128 * 128)
-        return dtc_linear_wgrad_rows(dgh_all, 3 * H, (int64_t)T * R, hs_all, H, (int64_t)T * R, valid_rows, dW_hh, db_hh, wg_ws, n_valid, 3 * H, H,
-                                     stream);
-    const DtcSegMat Hprev = plain(hs_all, H, H, (int64_t)T * R);
-    int rc = dtc_linear_wgrad(dgh_all, 3 * H, &Hprev, dW_hh, db_hh, wg_ws, T * R, 3 * H, H, stream);
-    if (rc != DTC_OK) return rc;
-    return dtc::check_launch("gru_bwd");
-}
-
-// ---- several recurrences of ONE shape, one launch per time step (the actor's and the critic's GRU of ActorCriticRecurrent /
-// ActorCriticDecoderRecurrent: rsl_rl/rsl_rl/modules/actor_critic_recurrent.py:45-46, 92-116).  A time step of one recurrence is a
-// latency-bound launch of ~190-290 workgroups; two of them on two streams overlap by ~20 % (tools/gru_pair_probe.py: 1.12 ms for two
-// forward passes against 0.72 for one).  The same two as ONE launch: 1.09 ms -- a launch with twice the workgroups takes 1.5 x as long,
-// and in the trainers the merged chain is slower than two chains on two lanes: an option, not the default.  Results
-// are bit-identical to the single calls (same kernels, same tiles).  A shape / setting without the split-path step kernels, and
-// count == 1: the single calls, one after the other.
-int dtc_gru_step_fwd_s3_pair(const float* const* hprev, const void* const* img, const float* const* b_hh, const float* const* gi_t,
-                             float* const* hout, float* const* gates_t, float* const* hn_t, int R, int H, void* stream);
-int dtc_gru_dgrad_parts_s3_pair(const float* const* dgh_t, const void* const* img, float* const* part, int64_t part_stride, int R, int H,
-                                int nparts, void* stream);
-
-extern "C" int dtc_gru_fwd_multi(const DtcGruFwdItem* items, int count, int T, int R, int H, void* stream) {
-    DTC_REQUIRE(items != nullptr && count >= 1 && count <= DTC_GRU_MULTI_MAX, "count = %d out of range (1..%d)", count, DTC_GRU_MULTI_MAX);
-    DTC_REQUIRE(T > 0 && R > 0 && H > 0, "bad shape T=%d R=%d H=%d", T, R, H);
-    static const bool off = getenv("DTC_GRU_MULTI") && atoi(getenv("DTC_GRU_MULTI")) == 0;
-    static const bool unfused = getenv("DTC_GRU_UNFUSED") != nullptr;
-    // both recurrences as ONE persistent launch (csrc/gru_seq.hip), one after the other inside it -- it may take every CU
-    if (count == 2 && !unfused && dtc_get_gemm_split() && dtc_gru_seq_supported(T, R, H, 1)) {
-        const float *gi[2], *h0[2], *W[2], *b[2];
-        float *hs[2], *gt[2], *hn[2];
-        void* sw[2];
-        bool ok = true;
-        for (int i = 0; i < 2; ++i) {
-            const DtcGruFwdItem& it = items[i];
-            DTC_REQUIRE(it.gi && it.h0 && it.W_hh && it.b_hh && it.hs_all && it.gates && it.hn && it.workspace, "item %d: null pointer", i);
-            gi[i] = it.gi; h0[i] = it.h0; W[i] = it.W_hh; b[i] = it.b_hh; hs[i] = it.hs_all; gt[i] = it.gates; hn[i] = it.hn;
-            sw[i] = gru_seq_slot(it.workspace, T, R, H);
-            ok = ok && dtc::aligned16(it.gi) && dtc::aligned16(it.h0) && dtc::aligned16(it.hs_all) && dtc::aligned16(it.gates) &&
-                 dtc::aligned16(it.hn) && dtc::aligned16(it.workspace);
-        }
-        if (ok) return dtc_gru_seq_fwd_pair(gi, h0, W, b, hs, gt, hn, sw, T, R, H, stream);
-    }
-    const bool pair = count == 2 && !off && !unfused && T >= 4 && gru_s3(H);
-    if (!pair) {
+    // split-precision steps (csrc/gru_s3.hip) for the passes of the update (T time steps share ONE image of W_hh); the one-step
+    // calls of the rollout keep the single-pass kernel
+    const bool s3 = !sw.unfused && T >= 4 && gru_s3(H);
+    if (count == 2 && !(sw.multi && s3)) {
         for (int i = 0; i < count; ++i) {
             const DtcGruFwdItem& it = items[i];
             int rc = dtc_gru_fwd(it.gi, it.h0, it.W_hh, it.b_hh, it.hs_all, it.gates, it.hn, it.workspace, T, R, H, stream);
@@ -361,56 +259,79 @@ extern "C" int dtc_gru_fwd_multi(const DtcGruFwdItem* items, int count, int T, i
         }
         return DTC_OK;
     }
-    hipStream_t s = (hipStream_t)stream;
-    const size_t RH = (size_t)R * H, R3H = (size_t)R * 3 * H;
-    const void* img[2];
-    for (int i = 0; i < 2; ++i) {
+    DTC_REQUIRE(count == 1 || s3, "%s: %d recurrences without the split-path step", who, count);        // (the steps below take items[0])
+    const void* img[DTC_GRU_MULTI_MAX] = {};
+    for (int i = 0; i < count; ++i) {
         const DtcGruFwdItem& it = items[i];
-        DTC_REQUIRE(it.gi && it.h0 && it.W_hh && it.b_hh && it.hs_all && it.gates && it.hn && it.workspace, "item %d: null pointer", i);
         if (hipMemcpyAsync(it.hs_all, it.h0, RH * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) {
-            dtc::set_error("gru_fwd_multi: h0 copy failed");
+            dtc::set_error("%s: h0 copy failed", who);
             return DTC_ERR_LAUNCH;
         }
-        void* im = gru_image_slot(it.workspace, T, R, H);
+        if (!s3) continue;
+        void* im = (char*)it.workspace + L[i].wimage;
+        img[i] = im;
         int rc = dtc_gru_s3_image(it.W_hh, im, H, 0, stream);
         if (rc != DTC_OK) return rc;
-        img[i] = im;
     }
+    const DtcGruFwdItem& one = items[0];             // without the split-path step there is one recurrence here
+    float* gh = (float*)((char*)one.workspace + L[0].part);
     for (int t = 0; t < T; ++t) {
-        const float *hprev[2], *bhh[2], *gi_t[2];
-        float *hout[2], *gates_t[2], *hn_t[2];
-        for (int i = 0; i < 2; ++i) {
-            const DtcGruFwdItem& it = items[i];
-            hprev[i] = it.hs_all + (size_t)t * RH;
-            bhh[i] = it.b_hh;
-            gi_t[i] = it.gi + (size_t)t * R3H;
-            hout[i] = it.hs_all + (size_t)(t + 1) * RH;
-            gates_t[i] = it.gates + (size_t)t * R3H;
-            hn_t[i] = it.hn + (size_t)t * RH;
+        if (s3) {
+            dtc::GruStepFwd st[DTC_GRU_MULTI_MAX];
+            for (int i = 0; i < count; ++i) {
+                const DtcGruFwdItem& it = items[i];
+                st[i] = dtc::GruStepFwd{it.hs_all + t * RH, img[i], it.b_hh, it.gi + t * R3H, it.hs_all + (t + 1) * RH, it.gates + t * R3H, it.hn + t * RH};
+            }
+            int rc = dtc::gru_s3_step_fwd(st, count, R, H, stream);
+            if (rc != DTC_OK) return rc;
+            continue;
         }
-        int rc = dtc_gru_step_fwd_s3_pair(hprev, img, bhh, gi_t, hout, gates_t, hn_t, R, H, stream);
+        const float* hprev = one.hs_all + t * RH;
+        if (!sw.unfused && H % 32 == 0) {
+            int rc = dtc_gru_step_fwd(hprev, one.W_hh, one.b_hh, one.gi + t * R3H, one.hs_all + (t + 1) * RH, one.gates + t * R3H, one.hn + t * RH, R, H, stream);
+            if (rc != DTC_OK) return rc;
+            continue;
+        }
+        const DtcSegMat X = plain(hprev, H, H, R);
+        int rc = dtc_linear_fwd(&X, one.W_hh, one.b_hh, gh, 3 * H, R, 3 * H, H, DTC_ACT_NONE, stream);
         if (rc != DTC_OK) return rc;
+        dtc::ProfScope prof("gru_gate_fwd", (double)RH * 4.0 * 12, s);
+        hipLaunchKernelGGL(gru_gate_fwd_kernel, dim3((unsigned)dtc::ceil_div((int64_t)RH, 256)), dim3(256), 0, s, one.gi + t * R3H, gh, hprev,
+                           one.hs_all + (t + 1) * RH, one.gates + t * R3H, one.hn + t * RH, R, H);
     }
-    return dtc::check_launch("gru_fwd_multi");
+    return dtc::check_launch(who);
 }
 
-// BPTT of `count` recurrences without their W_hh weight gradients (dgh_all of item i at its workspace + dtc_gru_dgh_offset, as
-// dtc_gru_bwd with dW_hh = NULL leaves it)
-extern "C" int dtc_gru_bwd_multi(const DtcGruBwdItem* items, int count, int T, int R, int H, void* stream) {
-    DTC_REQUIRE(items != nullptr && count >= 1 && count <= DTC_GRU_MULTI_MAX, "count = %d out of range (1..%d)", count, DTC_GRU_MULTI_MAX);
+// BPTT: dgi, dh0 and dgh_all (at the layout's offset) of every item; `wg` (one recurrence only, may be NULL): its W_hh weight gradient
+struct GruWgrad {
+    float *dW_hh, *db_hh;
+    const int64_t* valid_rows;
+    int n_valid;
+};
+int gru_bwd_run(const char* who, const DtcGruBwdItem* items, int count, const GruWgrad* wg, int T, int R, int H, void* stream) {
     DTC_REQUIRE(T > 0 && R > 0 && H > 0, "bad shape T=%d R=%d H=%d", T, R, H);
-    static const bool off = getenv("DTC_GRU_MULTI") && atoi(getenv("DTC_GRU_MULTI")) == 0;
-    static const bool vec_on = !(getenv("DTC_GRU_GATE_VEC") && atoi(getenv("DTC_GRU_GATE_VEC")) == 0);
-    auto a16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+    const GruSwitches& sw = switches();
+    hipStream_t s = (hipStream_t)stream;
     const size_t RH = (size_t)R * H, R3H = (size_t)R * 3 * H;
-    bool pair = count == 2 && !off && vec_on && gru_s3(H) && H % 4 == 0;
-    for (int i = 0; pair && i < count; ++i) {
+    const bool s3 = gru_s3(H);
+    const int nparts = gru_parts(H, s3);
+    // four units per thread when every row of every operand starts on a 16-byte boundary
+    bool vec4 = sw.gate_vec && H % 4 == 0;
+    float *part[DTC_GRU_MULTI_MAX], *dgh_all[DTC_GRU_MULTI_MAX];
+    void *wimage[DTC_GRU_MULTI_MAX], *wgrad_ws = nullptr;
+    for (int i = 0; i < count; ++i) {
         const DtcGruBwdItem& it = items[i];
-        DTC_REQUIRE(it.dhs && it.hs_all && it.gates && it.hn && it.W_hh && it.dgi && it.dh0 && it.workspace, "item %d: null pointer", i);
-        pair = a16(it.dhs) && a16(it.dh0) && a16(it.workspace) && a16(it.gates) && a16(it.hn) && a16(it.hs_all) && a16(it.dgi) &&
-               a16((float*)it.workspace + (size_t)MAX_PARTS * RH);
+        if (!(it.dhs && it.hs_all && it.gates && it.hn && it.W_hh && it.dgi && it.dh0 && it.workspace)) return null_pointer(i, count);
+        const GruLayout L = gru_layout(T, R, H, it.workspace);
+        wgrad_ws = (char*)it.workspace + L.wgrad_ws;
+        part[i] = (float*)((char*)it.workspace + L.part);              // [nparts][R][H]: the region the forward pass uses for gh
+        dgh_all[i] = (float*)((char*)it.workspace + L.dgh_all);
+        wimage[i] = (char*)it.workspace + L.wimage;
+        vec4 = vec4 && dtc::aligned16(it.dhs) && dtc::aligned16(it.dh0) && dtc::aligned16(part[i]) && dtc::aligned16(it.gates) &&
+               dtc::aligned16(it.hn) && dtc::aligned16(it.hs_all) && dtc::aligned16(it.dgi) && dtc::aligned16(dgh_all[i]);
     }
-    if (!pair) {
+    DTC_REQUIRE(!wg || (wg->dW_hh == nullptr) == (wg->db_hh == nullptr), "dW_hh and db_hh: both or neither");
+    if (count == 2 && !(sw.multi && s3 && vec4)) {
         for (int i = 0; i < count; ++i) {
             const DtcGruBwdItem& it = items[i];
             int rc = dtc_gru_bwd(it.dhs, it.hs_all, it.gates, it.hn, it.W_hh, it.dgi, nullptr, nullptr, it.dh0, it.workspace, nullptr, 0, T, R, H, stream);
@@ -418,41 +339,81 @@ extern "C" int dtc_gru_bwd_multi(const DtcGruBwdItem* items, int count, int T, i
         }
         return DTC_OK;
     }
-    hipStream_t s = (hipStream_t)stream;
-    const int nparts = gru_parts(H, true);
-    const void* img[2];
-    float *part[2], *dgh_all[2];
-    for (int i = 0; i < 2; ++i) {
-        const DtcGruBwdItem& it = items[i];
-        part[i] = (float*)it.workspace;
-        dgh_all[i] = (float*)it.workspace + (size_t)MAX_PARTS * RH;
-        void* im = gru_image_slot(it.workspace, T, R, H);
-        int rc = dtc_gru_s3_image(it.W_hh, im, H, 1, stream);
-        if (rc != DTC_OK) return rc;
-        img[i] = im;
-        if (hipMemsetAsync(it.dh0, 0, RH * sizeof(float), s) != hipSuccess) {
-            dtc::set_error("gru_bwd_multi: memset failed");
+    DTC_REQUIRE(count == 1 || (s3 && vec4), "%s: %d recurrences without the split-path step", who, count);   // (the steps below take items[0])
+    for (int i = 0; i < count; ++i) {
+        if (s3) {               // split path: ONE image of W_hh^T serves all T steps
+            int rc = dtc_gru_s3_image(items[i].W_hh, wimage[i], H, 1, stream);
+            if (rc != DTC_OK) return rc;
+        }
+        if (hipMemsetAsync(items[i].dh0, 0, RH * sizeof(float), s) != hipSuccess) {
+            dtc::set_error("%s: memset failed", who);
             return DTC_ERR_LAUNCH;
         }
     }
     const unsigned grid = (unsigned)dtc::ceil_div((int64_t)RH, 256), grid4 = (unsigned)dtc::ceil_div((int64_t)RH / 4, 256);
     for (int t = T - 1; t >= 0; --t) {
-        GateBwdPtrs gp[2];
-        const float* dgh_t[2];
-        for (int i = 0; i < 2; ++i) {
+        GateBwdPtrs gp[DTC_GRU_MULTI_MAX];
+        dtc::GruDgradParts dp[DTC_GRU_MULTI_MAX];
+        for (int i = 0; i < count; ++i) {
             const DtcGruBwdItem& it = items[i];
-            dgh_t[i] = dgh_all[i] + (size_t)t * R3H;
-            gp[i] = GateBwdPtrs{it.dhs + (size_t)t * RH, it.dh0, t == T - 1 ? (const float*)nullptr : (const float*)part[i], it.gates + (size_t)t * R3H,
-                                it.hn + (size_t)t * RH, it.hs_all + (size_t)t * RH, it.dgi + (size_t)t * R3H, dgh_all[i] + (size_t)t * R3H};
+            gp[i] = GateBwdPtrs{it.dhs + t * RH, it.dh0, t == T - 1 ? nullptr : part[i], it.gates + t * R3H,
+                                it.hn + t * RH, it.hs_all + t * RH, it.dgi + t * R3H, dgh_all[i] + t * R3H};
+            dp[i] = dtc::GruDgradParts{gp[i].dgh, wimage[i], part[i]};
         }
         {
-            dtc::ProfScope prof("gru_gate_bwd", 2.0 * (double)RH * 4.0 * 17, s);
-            hipLaunchKernelGGL(gru_gate_bwd4_kernel, dim3(grid4, 2), dim3(256), 0, s, gp[0], gp[1], R, H, nparts);
+            dtc::ProfScope prof("gru_gate_bwd", count * ((double)RH * 4.0 * 17), s);
+            const GateBwdPtrs& g = gp[0];
+            if (vec4)           // blockIdx.y = the recurrence
+                hipLaunchKernelGGL(gru_gate_bwd4_kernel, dim3(grid4, (unsigned)count), dim3(256), 0, s, g, gp[count - 1], R, H, nparts);
+            else                // (one recurrence: two advance together on the vec4 kernel only)
+                hipLaunchKernelGGL(gru_gate_bwd_kernel, dim3(grid), dim3(256), 0, s, g.dhs_t, g.dh, g.part, g.gates, g.hn, g.hprev, g.dgi, g.dgh, R, H, nparts);
         }
-        int rc = dtc_gru_dgrad_parts_s3_pair(dgh_t, img, part, (int64_t)RH, R, H, nparts, stream);
+        int rc = s3 ? dtc::gru_s3_dgrad_parts(dp, count, (int64_t)RH, R, H, nparts, stream)
+                    : dtc_linear_dgrad_split(dp[0].dgh_t, 3 * H, items[0].W_hh, part[0], H, (int64_t)RH, R, 3 * H, H, nparts, stream);
         if (rc != DTC_OK) return rc;
     }
-    for (int i = 0; i < 2; ++i)
-        hipLaunchKernelGGL(gru_add_parts_kernel, dim3(grid), dim3(256), 0, s, items[i].dh0, part[i], (long long)RH, nparts);
-    return dtc::check_launch("gru_bwd_multi");
+    for (int i = 0; i < count; ++i) dtc::gru_add_parts(items[i].dh0, part[i], (int64_t)RH, nparts, s);
+    // no dW_hh: the caller forms the W_hh weight gradient itself from dgh_all (workspace + dtc_gru_dgh_offset: the operand-image
+    // trainers pack it with the other operands of their grouped weight-gradient launch)
+    if (!wg || !wg->dW_hh) return dtc::check_launch(who);
+    const float* hs_all = items[0].hs_all;
+    // the padding slots of the padded trajectory layout have dgh = 0: with the caller's list of valid slots the product skips them
+    if (wg->valid_rows && wg->n_valid >= 1024 && wg->n_valid < T * R && dtc_get_gemm_split() && 3ll * H * H >= 128 * 128)
+        return dtc_linear_wgrad_rows(dgh_all[0], 3 * H, (int64_t)T * R, hs_all, H, (int64_t)T * R, wg->valid_rows, wg->dW_hh, wg->db_hh, wgrad_ws,
+                                     wg->n_valid, 3 * H, H, stream);
+    const DtcSegMat Hprev = plain(hs_all, H, H, (int64_t)T * R);
+    int rc = dtc_linear_wgrad(dgh_all[0], 3 * H, &Hprev, wg->dW_hh, wg->db_hh, wgrad_ws, T * R, 3 * H, H, stream);
+    if (rc != DTC_OK) return rc;
+    return dtc::check_launch(who);
+}
+}  // namespace
+
+void dtc::gru_add_parts(float* dh, const float* part, int64_t rh, int nparts, hipStream_t s) {
+    hipLaunchKernelGGL(gru_add_parts_kernel, dim3((unsigned)dtc::ceil_div(rh, 256)), dim3(256), 0, s, dh, part, (long long)rh, nparts);
+}
+
+extern "C" int dtc_gru_fwd(const float* gi, const float* h0, const float* W_hh, const float* b_hh, float* hs_all,
+                           float* gates, float* hn, void* workspace, int T, int R, int H, void* stream) {
+    const DtcGruFwdItem it{gi, h0, W_hh, b_hh, hs_all, gates, hn, workspace};
+    return gru_fwd_run("gru_fwd", &it, 1, T, R, H, stream);
+}
+
+extern "C" int dtc_gru_fwd_multi(const DtcGruFwdItem* items, int count, int T, int R, int H, void* stream) {
+    DTC_REQUIRE(items != nullptr && count >= 1 && count <= DTC_GRU_MULTI_MAX, "count = %d out of range (1..%d)", count, DTC_GRU_MULTI_MAX);
+    return gru_fwd_run("gru_fwd_multi", items, count, T, R, H, stream);
+}
+
+extern "C" int dtc_gru_bwd(const float* dhs, const float* hs_all, const float* gates, const float* hn, const float* W_hh,
+                           float* dgi, float* dW_hh, float* db_hh, float* dh0, void* workspace, const int64_t* valid_rows, int n_valid,
+                           int T, int R, int H, void* stream) {
+    const DtcGruBwdItem it{dhs, hs_all, gates, hn, W_hh, dgi, dh0, workspace};
+    const GruWgrad wg{dW_hh, db_hh, valid_rows, n_valid};
+    return gru_bwd_run("gru_bwd", &it, 1, &wg, T, R, H, stream);
+}
+
+// BPTT of `count` recurrences without their W_hh weight gradients (dgh_all of item i at its workspace + dtc_gru_dgh_offset, as
+// dtc_gru_bwd with dW_hh = NULL leaves it)
+extern "C" int dtc_gru_bwd_multi(const DtcGruBwdItem* items, int count, int T, int R, int H, void* stream) {
+    DTC_REQUIRE(items != nullptr && count >= 1 && count <= DTC_GRU_MULTI_MAX, "count = %d out of range (1..%d)", count, DTC_GRU_MULTI_MAX);
+    return gru_bwd_run("gru_bwd_multi", items, count, nullptr, T, R, H, stream);
 }

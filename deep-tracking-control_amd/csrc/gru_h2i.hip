@@ -29,13 +29,14 @@
 
 #include <type_traits>
 
+#include "gru_internal.hpp"
 #include "h2i_core.hpp"
 
 namespace {
 
 constexpr int MODE_FWD = 0, MODE_BWD = 1;
 constexpr int GH_MAX_TB = 48;        // exponent blocks of one reduction: 3H / 128 <= 48, i.e. H <= 2048
-constexpr int GH_MAX_PARTS = 6;
+constexpr int GH_MAX_PARTS = dtc::GRU_MAX_PARTS;
 
 __host__ __device__ inline long long gh_wimage_bytes(int H, int backward) {
     const long long tiles = backward ? H / 128 : H / 32, K = backward ? 3ll * H : H;
@@ -160,8 +161,6 @@ struct GruH2iArgs {
     float* part;
     long long part_stride;
 };
-
-__device__ __forceinline__ float sigmoid_h2i(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // stage ring: separate objects per buffer (an LDS-DMA into one cannot alias the fragment reads of another, see linear_s3_kernel)
 __shared__ __attribute__((aligned(16))) u32x2 GAs0[2][128 * 4];
@@ -348,8 +347,8 @@ __global__ __launch_bounds__(256, 2) void gru_h2i_kernel(const GruH2iArgs a) {
                 f32x4 rg, zg, ng, ghn, ho;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    rg[e] = sigmoid_h2i(gr[e] + (acc[0][0][4 * g + e] + br[e]));
-                    zg[e] = sigmoid_h2i(gz[e] + (acc[0][1][4 * g + e] + bz[e]));
+                    rg[e] = dtc::sigmoid(gr[e] + (acc[0][0][4 * g + e] + br[e]));
+                    zg[e] = dtc::sigmoid(gz[e] + (acc[0][1][4 * g + e] + bz[e]));
                     ghn[e] = acc[0][2][4 * g + e] + bn[e];
                     ng[e] = tanhf(gn[e] + rg[e] * ghn[e]);
                     ho[e] = (1.0f - zg[e]) * ng[e] + zg[e] * hp[e];
@@ -515,15 +514,6 @@ __global__ __launch_bounds__(256) void gru_h2i_gate_bwd_kernel(const GateH2iArgs
             gh_store_exp(P.dgi_img, M, 3 * H, s, 2 * hb + kb, e_n);
         }
     }
-}
-
-// dh0 <- dh0 + the chunks of the last W_hh product, in the gate kernel's order
-__global__ __launch_bounds__(256) void gru_h2i_add_parts_kernel(float* __restrict__ dh, const float* __restrict__ part, long long rh, int nparts) {
-    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= rh) return;
-    float d = dh[e];
-    for (int c = 0; c < nparts; ++c) d += part[c * rh + e];
-    dh[e] = d;
 }
 
 bool gh_shapes_ok(int R, int H) {
@@ -707,7 +697,7 @@ extern "C" int dtc_gru_bwd_h2i(const float* dhs, const float* hs_all, const floa
     void* dimg = ws + L.dimg;
     void* wimg = ws + L.wimg;
     const size_t RH = (size_t)R * H, R3H = 3 * RH;
-    const int nparts = (3 * H / GH_MAX_PARTS) % 16 == 0 ? GH_MAX_PARTS : 3;
+    const int nparts = dtc::gru_parts(H, true);
     int rc = dtc_gru_h2i_image(W_hh, wimg, H, 1, stream);
     if (rc != DTC_OK) return rc;
     if (hipMemsetAsync(dh0, 0, RH * sizeof(float), s) != hipSuccess) {
@@ -743,6 +733,6 @@ extern "C" int dtc_gru_bwd_h2i(const float* dhs, const float* hs_all, const floa
         rc = dtc_gru_dgrad_parts_h2i(dimg, wimg, part, (int64_t)RH, R, H, nparts, stream);
         if (rc != DTC_OK) return rc;
     }
-    hipLaunchKernelGGL(gru_h2i_add_parts_kernel, dim3((unsigned)dtc::ceil_div((int64_t)RH, 256)), dim3(256), 0, s, dh0, part, (long long)RH, nparts);
+    dtc::gru_add_parts(dh0, part, (int64_t)RH, nparts, s);
     return dtc::check_launch("gru_bwd_h2i");
 }

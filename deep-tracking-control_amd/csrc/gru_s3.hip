@@ -14,6 +14,7 @@
 //   * the K loop is unrolled by two, so stage buffers and register sets have constant indices.
 #include <type_traits>
 
+#include "gru_internal.hpp"
 #include "s3_core.hpp"
 
 namespace {
@@ -74,8 +75,6 @@ __global__ __launch_bounds__(256) void gru_wimage_kernel(const float* __restrict
 #pragma unroll
     for (int p = 0; p < 3; ++p) dst[p * (G::PLANE / 16) + rslot(r, h)] = u32x4{s0.p[p].x, s0.p[p].y, s1.p[p].x, s1.p[p].y};
 }
-
-__device__ __forceinline__ float sigmoid_s3(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 
@@ -285,8 +284,8 @@ __global__ __launch_bounds__(256, 2) void gru_s3_kernel(const GruS3Args a0, cons
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int row = row0 + (r & 3) + 8 * (r >> 2);
-            const float rg = sigmoid_s3(gr[r] + (acc[0][0][r] + br));
-            const float zg = sigmoid_s3(gz[r] + (acc[0][1][r] + bz));
+            const float rg = dtc::sigmoid(gr[r] + (acc[0][0][r] + br));
+            const float zg = dtc::sigmoid(gz[r] + (acc[0][1][r] + bz));
             const float ghn = acc[0][2][r] + bn;
             const float ng = tanhf(gn[r] + rg * ghn);
             if (row < R) {
@@ -350,99 +349,86 @@ int gru_colmap() {
     constexpr int on = 1;
     return on;
 }
-int fwd_args(GruS3Args& a, const float* hprev, const void* img, const float* b_hh, const float* gi_t, float* hout, float* gates_t,
-             float* hn_t, int R, int H) {
+int fwd_args(GruS3Args& a, const dtc::GruStepFwd& it, int R, int H) {
     DTC_REQUIRE(shapes_ok(R, H), "bad shape R=%d H=%d (H must be a multiple of 128)", R, H);
-    DTC_REQUIRE(hprev && img && b_hh && gi_t && hout && gates_t && hn_t, "null pointer");
+    DTC_REQUIRE(it.hprev && it.img && it.b_hh && it.gi_t && it.hout && it.gates_t && it.hn_t, "null pointer");
     a = GruS3Args{};
-    a.A = hprev;
+    a.A = it.hprev;
     a.lda = H;
-    a.img = (const u32x4*)img;
+    a.img = (const u32x4*)it.img;
     a.img_bytes = (long long)Geo<MODE_FWD>::CHUNK * (H / 32) * (H / BK);
     a.R = R;
     a.H = H;
     a.stages = a.stages_tile = H / BK;
-    a.bhh = b_hh;
-    a.gi = gi_t;
-    a.hout = hout;
-    a.gates = gates_t;
-    a.hn = hn_t;
+    a.bhh = it.b_hh;
+    a.gi = it.gi_t;
+    a.hout = it.hout;
+    a.gates = it.gates_t;
+    a.hn = it.hn_t;
     a.colmap = gru_colmap();
     a.nparts = 1;
     return DTC_OK;
 }
-int launch_fwd(const GruS3Args& a0, const GruS3Args& a1, int count, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    const int R = a0.R, H = a0.H;
-    dtc::ProfScope prof(dtc::prof_shape_name("gru_step_fwd", R, 3 * H, H), count * 2.0 * R * 3.0 * H * H, s);
-    const unsigned gx = a0.colmap ? (unsigned)(8 * dtc::ceil_div(H / 32, 8) * dtc::ceil_div(R, BM)) : (unsigned)grid_for((int)dtc::ceil_div(R, BM), H / 32);
-    hipLaunchKernelGGL(gru_s3_kernel<MODE_FWD>, dim3(gx, 1, (unsigned)count), dim3(256), 0, s, a0, a1);
-    return dtc::check_launch("gru_step_fwd_s3");
-}
 }  // namespace
-extern "C" int dtc_gru_step_fwd_s3(const float* hprev, const void* img, const float* b_hh, const float* gi_t, float* hout, float* gates_t,
-                                   float* hn_t, int R, int H, void* stream) {
-    GruS3Args a;
-    int rc = fwd_args(a, hprev, img, b_hh, gi_t, hout, gates_t, hn_t, R, H);
-    if (rc != DTC_OK) return rc;
-    return launch_fwd(a, a, 1, stream);
-}
-// the same time step of TWO recurrences of one shape in one launch (dtc_gru_fwd_multi)
-int dtc_gru_step_fwd_s3_pair(const float* const* hprev, const void* const* img, const float* const* b_hh, const float* const* gi_t,
-                             float* const* hout, float* const* gates_t, float* const* hn_t, int R, int H, void* stream) {
-    GruS3Args a[2];
-    for (int i = 0; i < 2; ++i) {
-        int rc = fwd_args(a[i], hprev[i], img[i], b_hh[i], gi_t[i], hout[i], gates_t[i], hn_t[i], R, H);
+// blockIdx.z = the recurrence; with count == 1 the kernel's second argument block is a copy of the first
+int dtc::gru_s3_step_fwd(const GruStepFwd* items, int count, int R, int H, void* stream) {
+    DTC_REQUIRE(items && count >= 1 && count <= DTC_GRU_MULTI_MAX, "count = %d out of range (1..%d)", count, DTC_GRU_MULTI_MAX);
+    GruS3Args a[DTC_GRU_MULTI_MAX];
+    for (int i = 0; i < count; ++i) {
+        int rc = fwd_args(a[i], items[i], R, H);
         if (rc != DTC_OK) return rc;
     }
-    return launch_fwd(a[0], a[1], 2, stream);
+    hipStream_t s = (hipStream_t)stream;
+    dtc::ProfScope prof(dtc::prof_shape_name("gru_step_fwd", R, 3 * H, H), count * 2.0 * R * 3.0 * H * H, s);
+    const unsigned gx = a[0].colmap ? (unsigned)(8 * dtc::ceil_div(H / 32, 8) * dtc::ceil_div(R, BM)) : (unsigned)grid_for((int)dtc::ceil_div(R, BM), H / 32);
+    hipLaunchKernelGGL(gru_s3_kernel<MODE_FWD>, dim3(gx, 1, (unsigned)count), dim3(256), 0, s, a[0], a[count - 1]);
+    return dtc::check_launch("gru_step_fwd_s3");
+}
+extern "C" int dtc_gru_step_fwd_s3(const float* hprev, const void* img, const float* b_hh, const float* gi_t, float* hout, float* gates_t,
+                                   float* hn_t, int R, int H, void* stream) {
+    const dtc::GruStepFwd it{hprev, img, b_hh, gi_t, hout, gates_t, hn_t};
+    return dtc::gru_s3_step_fwd(&it, 1, R, H, stream);
 }
 
 // the `nparts` chunks of dgh_t [R, 3H] W_hh [3H, H] side by side: chunk c -> part + c * part_stride ([R, H]); the caller adds
 // them in a fixed order; `img` = dtc_gru_s3_image(W_hh, backward = 1); (3H / nparts) must be a multiple of 64
 namespace {
-int bwd_args(GruS3Args& a, const float* dgh_t, const void* img, float* part, int64_t part_stride, int R, int H, int nparts) {
+int bwd_args(GruS3Args& a, const dtc::GruDgradParts& it, int64_t part_stride, int R, int H, int nparts) {
     DTC_REQUIRE(shapes_ok(R, H) && nparts >= 1 && (3 * H) % nparts == 0 && (3 * H / nparts) % (4 * BK) == 0, "bad shape R=%d H=%d nparts=%d", R, H, nparts);
-    DTC_REQUIRE(dgh_t && img && part && part_stride >= (int64_t)R * H, "null pointer / overlapping chunks");
+    DTC_REQUIRE(it.dgh_t && it.img && it.part && part_stride >= (int64_t)R * H, "null pointer / overlapping chunks");
     a = GruS3Args{};
-    a.A = dgh_t;
+    a.A = it.dgh_t;
     a.lda = 3 * H;
-    a.img = (const u32x4*)img;
+    a.img = (const u32x4*)it.img;
     a.img_bytes = (long long)Geo<MODE_BWD>::CHUNK * (H / 128) * (3 * H / BK);
     a.R = R;
     a.H = H;
     a.stages = 3 * H / nparts / BK;
     a.stages_tile = 3 * H / BK;
-    a.part = part;
+    a.part = it.part;
     a.part_stride = part_stride;
     a.colmap = gru_colmap();
     a.nparts = nparts;
     return DTC_OK;
 }
-int launch_bwd(const GruS3Args& a0, const GruS3Args& a1, int count, int nparts, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    const int R = a0.R, H = a0.H;
-    dtc::ProfScope prof(dtc::prof_shape_name("linear_dgrad", R, 3 * H, H), count * 2.0 * R * 3.0 * H * H, s,
-                        count * 4.0 * ((double)R * 3 * H + 3.0 * H * H + (double)nparts * R * H));
-    const dim3 grid = a0.colmap ? dim3((unsigned)(8 * dtc::ceil_div((H / 128) * nparts, 8) * dtc::ceil_div(R, BM)), 1, (unsigned)count)
-                                : dim3((unsigned)grid_for((int)dtc::ceil_div(R, BM), H / 128), (unsigned)nparts, (unsigned)count);
-    hipLaunchKernelGGL(gru_s3_kernel<MODE_BWD>, grid, dim3(256), 0, s, a0, a1);
-    return dtc::check_launch("gru_dgrad_parts_s3");
-}
 }  // namespace
-extern "C" int dtc_gru_dgrad_parts_s3(const float* dgh_t, const void* img, float* part, int64_t part_stride, int R, int H, int nparts,
-                                      void* stream) {
-    GruS3Args a;
-    int rc = bwd_args(a, dgh_t, img, part, part_stride, R, H, nparts);
-    if (rc != DTC_OK) return rc;
-    return launch_bwd(a, a, 1, nparts, stream);
-}
-int dtc_gru_dgrad_parts_s3_pair(const float* const* dgh_t, const void* const* img, float* const* part, int64_t part_stride, int R, int H,
-                                int nparts, void* stream) {
-    GruS3Args a[2];
-    for (int i = 0; i < 2; ++i) {
-        int rc = bwd_args(a[i], dgh_t[i], img[i], part[i], part_stride, R, H, nparts);
+int dtc::gru_s3_dgrad_parts(const GruDgradParts* items, int count, int64_t part_stride, int R, int H, int nparts, void* stream) {
+    DTC_REQUIRE(items && count >= 1 && count <= DTC_GRU_MULTI_MAX, "count = %d out of range (1..%d)", count, DTC_GRU_MULTI_MAX);
+    GruS3Args a[DTC_GRU_MULTI_MAX];
+    for (int i = 0; i < count; ++i) {
+        int rc = bwd_args(a[i], items[i], part_stride, R, H, nparts);
         if (rc != DTC_OK) return rc;
     }
-    return launch_bwd(a[0], a[1], 2, nparts, stream);
+    hipStream_t s = (hipStream_t)stream;
+    dtc::ProfScope prof(dtc::prof_shape_name("linear_dgrad", R, 3 * H, H), count * 2.0 * R * 3.0 * H * H, s,
+                        count * 4.0 * ((double)R * 3 * H + 3.0 * H * H + (double)nparts * R * H));
+    const dim3 grid = a[0].colmap ? dim3((unsigned)(8 * dtc::ceil_div((H / 128) * nparts, 8) * dtc::ceil_div(R, BM)), 1, (unsigned)count)
+                                  : dim3((unsigned)grid_for((int)dtc::ceil_div(R, BM), H / 128), (unsigned)nparts, (unsigned)count);
+    hipLaunchKernelGGL(gru_s3_kernel<MODE_BWD>, grid, dim3(256), 0, s, a[0], a[count - 1]);
+    return dtc::check_launch("gru_dgrad_parts_s3");
+}
+extern "C" int dtc_gru_dgrad_parts_s3(const float* dgh_t, const void* img, float* part, int64_t part_stride, int R, int H, int nparts,
+                                      void* stream) {
+    const dtc::GruDgradParts it{dgh_t, img, part};
+    return dtc::gru_s3_dgrad_parts(&it, 1, part_stride, R, H, nparts, stream);
 }

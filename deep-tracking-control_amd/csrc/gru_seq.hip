@@ -58,8 +58,6 @@ struct SeqFwd {
     int T, R, RB, NRB, rows_pad;
 };
 
-__device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 // (hi, lo) of four values times 2^e, as the two 8-byte words of the planes
 __device__ __forceinline__ void split4(const f32x4 v, int e, u64& hi, u64& lo) {
     h16x4 h, l;
@@ -265,8 +263,8 @@ __global__ __launch_bounds__(MAXT) void gru_seq_fwd_kernel(const SeqFwdPair P) {
             f32x4 hnew;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                rg[rt][i] = sigmoid_f(gin[rt][0][i] + (acc[rt][0][i] * back + bias[0][i]));
-                zg[rt][i] = sigmoid_f(gin[rt][1][i] + (acc[rt][1][i] * back + bias[1][i]));
+                rg[rt][i] = dtc::sigmoid(gin[rt][0][i] + (acc[rt][0][i] * back + bias[0][i]));
+                zg[rt][i] = dtc::sigmoid(gin[rt][1][i] + (acc[rt][1][i] * back + bias[1][i]));
                 ghn[rt][i] = acc[rt][2][i] * back + bias[2][i];
                 ng[rt][i] = tanhf(gin[rt][2][i] + rg[rt][i] * ghn[rt][i]);
                 hnew[i] = (1.0f - zg[rt][i]) * ng[rt][i] + zg[rt][i] * hp[rt][i];

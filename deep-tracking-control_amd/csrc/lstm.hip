@@ -16,11 +16,9 @@
 // by the caller.  Padded steps need no masks: their output gradients are zero.
 #include <stdlib.h>
 
-#include "common.hpp"
+#include "gru_internal.hpp"
 
 namespace {
-
-__device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // one thread per (row, hidden unit)
 __global__ __launch_bounds__(256) void lstm_gate_fwd_kernel(const float* __restrict__ gi, const float* __restrict__ gh,
@@ -32,10 +30,10 @@ __global__ __launch_bounds__(256) void lstm_gate_fwd_kernel(const float* __restr
     const int j = (int)(e - row * H);
     const float* a = gi + row * 4 * H;
     const float* b = gh + row * 4 * H;
-    const float i = sigmoidf(a[j] + b[j]);
-    const float f = sigmoidf(a[H + j] + b[H + j]);
+    const float i = dtc::sigmoid(a[j] + b[j]);
+    const float f = dtc::sigmoid(a[H + j] + b[H + j]);
     const float g = tanhf(a[2 * H + j] + b[2 * H + j]);
-    const float o = sigmoidf(a[3 * H + j] + b[3 * H + j]);
+    const float o = dtc::sigmoid(a[3 * H + j] + b[3 * H + j]);
     const float c = f * cprev[e] + i * g;
     cout[e] = c;
     hout[e] = o * tanhf(c);
@@ -79,21 +77,28 @@ __global__ __launch_bounds__(256) void lstm_sum_parts_kernel(float* __restrict__
     if (e < rh) dh[e] = ((part[e] + part[rh + e]) + part[2 * rh + e]) + part[3 * rh + e];
 }
 
-DtcSegMat plain(const float* p, int64_t ld, int cols, int64_t rows) {
-    DtcSegMat m;
-    m.nseg = 1;
-    m.cols = cols;
-    m.idx = nullptr;
-    m.seg[0] = DtcSeg{const_cast<float*>(p), ld, 0, cols, 0, 0, rows};
-    return m;
+using dtc::plain;
+
+// The dtc_lstm_workspace() buffer, as byte offsets from its start: gh of the forward pass / the four dh chunks of the backward
+// pass (R * 4H floats), then the weight gradient's partial sums on a 16-byte boundary -- aligned as an ADDRESS, inside the 16 spare
+// bytes of `total`, where `workspace` itself starts off such a boundary (NULL: the offsets inside an aligned buffer)
+struct LstmLayout {
+    int64_t gh, wgrad_ws, total;
+};
+LstmLayout lstm_layout(int T, int R, int H, const void* workspace = nullptr) {
+    const int64_t off = (int64_t)((uintptr_t)workspace & 15), end = (int64_t)R * 4 * H * sizeof(float);
+    LstmLayout L;
+    L.gh = 0;
+    L.wgrad_ws = ((off + end + 15) & ~(int64_t)15) - off;
+    L.total = end + 16 + dtc_linear_wgrad_workspace(T * R, 4 * H, H);
+    return L;
 }
 
 }  // namespace
 
-// workspace layout: [ gh (forward) / the four dh chunks (backward): R*4H floats | wgrad partials ]
 extern "C" int64_t dtc_lstm_workspace(int T, int R, int H) {
     if (T <= 0 || R <= 0 || H <= 0) return 0;
-    return (int64_t)R * 4 * H * sizeof(float) + 16 + dtc_linear_wgrad_workspace(T * R, 4 * H, H);
+    return lstm_layout(T, R, H).total;
 }
 
 // fused: one dtc_lstm_step_fwd launch per step where H % 32 == 0 (else, and always for dtc_lstm_fwd, the GEMM + gate pair)
@@ -102,7 +107,7 @@ static int lstm_fwd_impl(const float* gi, const float* h0, const float* c0, cons
     DTC_REQUIRE(T > 0 && R > 0 && H > 0, "bad shape T=%d R=%d H=%d", T, R, H);
     DTC_REQUIRE(gi && h0 && c0 && W_hh && b_hh && hs_all && cs_all && gates && workspace, "null pointer");
     hipStream_t s = (hipStream_t)stream;
-    float* gh = (float*)workspace;
+    float* gh = (float*)((char*)workspace + lstm_layout(T, R, H).gh);
     const size_t RH = (size_t)R * H, R4H = 4 * RH;
     if (hipMemcpyAsync(hs_all, h0, RH * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess ||
         hipMemcpyAsync(cs_all, c0, RH * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) {
@@ -145,8 +150,9 @@ extern "C" int dtc_lstm_bwd(const float* dhs, const float* hs_all, const float* 
     DTC_REQUIRE(dhs && hs_all && cs_all && gates && W_hh && dgi && dW_hh && db_hh && dh0 && dc0 && workspace, "null pointer");
     hipStream_t s = (hipStream_t)stream;
     const size_t RH = (size_t)R * H, R4H = 4 * RH;
-    float* part = (float*)workspace;              // [4][R][H]
-    void* wg_ws = (void*)(((uintptr_t)(part + R4H) + 15) & ~(uintptr_t)15);
+    const LstmLayout L = lstm_layout(T, R, H, workspace);
+    float* part = (float*)((char*)workspace + L.gh);              // [4][R][H]
+    void* wg_ws = (char*)workspace + L.wgrad_ws;
     if (hipMemsetAsync(dc0, 0, RH * sizeof(float), s) != hipSuccess) {
         dtc::set_error("lstm_bwd: memset failed");
         return DTC_ERR_LAUNCH;

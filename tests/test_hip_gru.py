@@ -8,7 +8,10 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
-@pytest.mark.parametrize("T,R,I,H", [(24, 13, 53, 512), (24, 300, 1389, 512), (1, 64, 53, 512), (5, 7, 20, 64)])
+# (3, 5, 20, 36): H % 32 != 0 -- the GEMM + gate-kernel forward step, four units per thread in the gate backward; (3, 5, 20, 37): H % 4 != 0 --
+# one unit per thread; (3, 130, 20, 128): T < 4 -- the fused fp32 step although the split path serves H, two row tiles with a tail
+@pytest.mark.parametrize("T,R,I,H", [(24, 13, 53, 512), (24, 300, 1389, 512), (1, 64, 53, 512), (5, 7, 20, 64), (3, 5, 20, 36), (3, 5, 20, 37),
+                                     (3, 130, 20, 128)])
 def test_gru_forward_backward_vs_torch(T, R, I, H):
     from dtc_amd import ops
     g = torch.Generator().manual_seed(T * 1000 + R)
@@ -108,7 +111,7 @@ def test_split_precision_step_kernels_vs_fp64(R):
         assert es3 <= 2.0 * e32 + 2e-7, (nparts, e32, es3)
 
 
-@pytest.mark.parametrize("T,R,H", [(24, 1473, 512), (6, 77, 128), (2, 40, 128), (5, 7, 64)])
+@pytest.mark.parametrize("T,R,H", [(24, 1473, 512), (6, 77, 128), (2, 40, 128), (5, 7, 64), (5, 130, 128)])
 def test_two_recurrences_in_one_launch_per_time_step_equal_the_single_calls_bit_for_bit(T, R, H):
     from dtc_amd import _ffi
     _ffi.lib().dtc_set_gru_seq(0)            # (the per-step kernels: the persistent launches have tests of their own below)
@@ -150,6 +153,89 @@ def _multi_equals_single(T, R, H):
             assert torch.equal(a[k], b[k]), (i, k)
         assert torch.equal(ops.gru_dgh_all(a["ws"], T, R, H), ops.gru_dgh_all(b["ws"], T, R, H)), (i, "dgh_all")
     assert not torch.equal(single[0]["hs"], single[1]["hs"])      # (the two recurrences are different problems)
+
+
+def _run_recurrences(T, R, H, multi_and_lstm=True):
+    """One call of dtc_gru_fwd and dtc_gru_bwd (with its W_hh weight gradient) and, with multi_and_lstm, of dtc_gru_fwd_multi and
+    dtc_gru_bwd_multi (two recurrences) and of dtc_lstm_fwd, dtc_lstm_fwd_fused and dtc_lstm_bwd, on seeded inputs.  Returns every
+    output by name."""
+    from dtc_amd import ops
+    g = torch.Generator().manual_seed(T * 10000 + R * 10 + H)
+    rn = lambda *s: torch.randn(*s, generator=g).to(DEV)
+    new = lambda *s: torch.empty(*s, device=DEV)
+    out = {}
+
+    def gru(tag, n):
+        x = [dict(gi=rn(T, R, 3 * H), h0=0.5 * rn(R, H), W=rn(3 * H, H) / H ** 0.5, b=0.2 * rn(3 * H), dhs=0.01 * rn(T, R, H)) for _ in range(n)]
+        o = [dict(hs_all=new(T + 1, R, H), gates=new(T, R, 3 * H), hn=new(T, R, H), dgi=new(T, R, 3 * H), dh0=new(R, H),
+                  ws=ops.workspace(ops.gru_workspace_bytes(T, R, H), DEV).zero_()) for _ in range(n)]
+        if n == 1:
+            (x0,), (o0,) = x, o
+            o0.update(dW_hh=new(3 * H, H), db_hh=new(3 * H))
+            ops.gru_fwd(x0["gi"], x0["h0"], x0["W"], x0["b"], o0["hs_all"], o0["gates"], o0["hn"], o0["ws"])
+            ops.gru_bwd(x0["dhs"], o0["hs_all"], o0["gates"], o0["hn"], x0["W"], o0["dgi"], o0["dW_hh"], o0["db_hh"], o0["dh0"], o0["ws"])
+        else:
+            ops.gru_fwd_multi([(a["gi"], a["h0"], a["W"], a["b"], b["hs_all"], b["gates"], b["hn"], b["ws"]) for a, b in zip(x, o)])
+            ops.gru_bwd_multi([(a["dhs"], b["hs_all"], b["gates"], b["hn"], a["W"], b["dgi"], b["dh0"], b["ws"]) for a, b in zip(x, o)])
+        for i, b in enumerate(o):
+            b["dgh_all"] = ops.gru_dgh_all(b.pop("ws"), T, R, H)
+            out.update({f"{tag}{i}.{k}": v for k, v in b.items()})
+
+    gru("gru", 1)
+    if multi_and_lstm:
+        gru("gru_multi", 2)
+        gi, h0, c0, W, b, dhs = rn(T, R, 4 * H), 0.5 * rn(R, H), 0.5 * rn(R, H), rn(4 * H, H) / H ** 0.5, 0.2 * rn(4 * H), 0.01 * rn(T, R, H)
+        ws = ops.workspace(ops.lstm_workspace_bytes(T, R, H), DEV)
+        for tag, fwd in (("lstm", ops.lstm_fwd), ("lstm_fused", ops.lstm_fwd_fused)):
+            o = dict(hs_all=new(T + 1, R, H), cs_all=new(T + 1, R, H), gates=new(T, R, 4 * H))
+            fwd(gi, h0, c0, W, b, o["hs_all"], o["cs_all"], o["gates"], ws)
+            out.update({f"{tag}.{k}": v for k, v in o.items()})
+        d = dict(dgi=new(T, R, 4 * H), dW_hh=new(4 * H, H), db_hh=new(4 * H), dh0=new(R, H), dc0=new(R, H))
+        ops.lstm_bwd(dhs, o["hs_all"], o["cs_all"], o["gates"], W, d["dgi"], d["dW_hh"], d["db_hh"], d["dh0"], d["dc0"], ws)
+        out.update({f"lstm_bwd.{k}": v for k, v in d.items()})
+    torch.cuda.synchronize()
+    return out
+
+
+def _launch_census():
+    from dtc_amd import _ffi
+    lib = _ffi.lib()
+    lib.dtc_set_gru_seq(0)
+    lib.dtc_prof_enable(1)
+    lib.dtc_prof_reset()
+    try:
+        _run_recurrences(5, 130, 128)
+        _run_recurrences(3, 5, 36, multi_and_lstm=False)
+        return sorted((r["name"], r["launches"], r["work"]) for r in _ffi.prof_report())
+    finally:
+        lib.dtc_prof_enable(0)
+        lib.dtc_prof_reset()
+        lib.dtc_set_gru_seq(-1)
+
+
+# (kernel class, launches, algorithmic work) as the library's own launch profile (dtc_prof_report) counts them
+CENSUS = [
+    ('gru_gate_bwd', 13, 17009520.0),
+    ('gru_gate_fwd', 3, 25920.0),
+    ('gru_step_fwd', 10, 191692800.0),
+    ('linear_dgrad', 18, 277006240.0),
+    ('linear_fwd', 8, 85313440.0),
+    ('linear_wgrad', 3, 149211040.0),
+    ('lstm_gate_bwd', 5, 5324800.0),
+    ('lstm_gate_fwd', 5, 4992000.0),
+    ('lstm_step_fwd', 5, 85196800.0),
+    ('wgrad_reduce', 3, 4413312.0),
+    ('wimage', 6, 0.0),
+]
+
+
+def test_the_recurrence_entry_points_issue_the_recorded_launches():
+    """Which kernels the host drivers of csrc/gru.hip and csrc/lstm.hip launch, how often and on how much work: the four GRU entry points
+    (dtc_gru_bwd with its W_hh weight gradient) and the three LSTM ones at (T, R, H) = (5, 130, 128) -- split-path steps, two
+    recurrences per launch in the *_multi calls -- and dtc_gru_fwd / dtc_gru_bwd at (3, 5, 36) -- GEMM + gate kernel forward, single-pass
+    data gradient.  The table was recorded before the drivers were merged into one time-step loop per pass: the loop must issue what the
+    four separate ones did."""
+    assert _launch_census() == CENSUS
 
 
 def _gru_ref64(gi, h0, W, b):
