@@ -34,6 +34,7 @@
 // fetched from HBM into ONE L2 and shared there.
 #include "amax.hpp"
 #include "gemm_core.hpp"
+#include "gru_internal.hpp"
 
 namespace {
 
@@ -408,18 +409,17 @@ __global__ __launch_bounds__(256, DEEP ? 3 : (BN == 128 ? 2 : DTC_FWD_WAVES)) vo
 }
 
 // ------------------------------------------------------------------------------------------
-// One fused GRU time step (forward): gh = h_{t-1} W_hh^T + b_hh for the three gates of 32 hidden units,
-// then the gate math of torch.nn.GRU in the epilogue -- the [R,3H] recurrent pre-activations never touch HBM:
-//   r = sigmoid(gi_r + gh_r), z = sigmoid(gi_z + gh_z), n = tanh(gi_n + r * gh_n), h_t = (1 - z) * n + z * h_{t-1}
-// Block tile: 128 rows x (32 units x 3 gates); wave w owns rows 32w..32w+31 and three 32x32 MFMA tiles (r, z, n of
-// the same units), so every lane holds the three pre-activations of its (row, unit) pairs.  Same K loop as
-// linear_fwd_kernel (plain single-segment operands).
+// One fused recurrent time step (forward): gh = h_{t-1} W_hh^T for the NG gates of 32 hidden units, then the cell's gate math in
+// the epilogue -- the [R, NG * H] recurrent pre-activations never touch HBM.
+// Block tile: 128 rows x (32 units x NG gates): the loader reads rows j, H + j, .. of W_hh in place (no repacked weights); wave w
+// owns rows 32w..32w+31 and NG 32x32 MFMA tiles (the gates of the same units), so every lane holds all pre-activations of its
+// (row, unit) pairs.  Same K loop as linear_fwd_kernel (plain single-segment operands).
+// epilogue(acc, row0, j): the lane's unit j and its 16 rows row0 + (r & 3) + 8 * (r >> 2) of acc[gate][r] (bias not yet added).
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256, 3) void gru_step_fwd_kernel(const float* __restrict__ hprev, const float* __restrict__ Whh,
-                                                           const float* __restrict__ bhh, const float* __restrict__ gi,
-                                                           float* __restrict__ hout, float* __restrict__ gates,
-                                                           float* __restrict__ hn, int R, int H) {
-    constexpr int GB = 96, LDAg = BM + PAD, LDBg = GB + PAD;
+template <int NG, class Epilogue>
+__device__ __forceinline__ void rnn_step_fwd_body(const float* __restrict__ hprev, const float* __restrict__ Whh, int R, int H,
+                                                  Epilogue epilogue) {
+    constexpr int GB = 32 * NG, LDAg = BM + PAD, LDBg = GB + PAD;
     __shared__ float As[2][BK][LDAg];
     __shared__ float Bs[2][BK][LDBg];
     int tr, tc;
@@ -437,7 +437,7 @@ __global__ __launch_bounds__(256, 3) void gru_step_fwd_kernel(const float* __res
     }
 #pragma unroll
     for (int i = 0; i < NB; ++i) {
-        const int n = rbase + RP * i;                       // 0..95: gate n / 32, unit j0 + n % 32
+        const int n = rbase + RP * i;                       // 0..GB-1: gate n / 32, unit j0 + n % 32
         woff[i] = (u32)(((n >> 5) * H + j0 + (n & 31)) * H + kk) * 4u;
     }
     const rsrc_t ares = make_rsrc(hprev), wres = make_rsrc(Whh);
@@ -460,9 +460,9 @@ __global__ __launch_bounds__(256, 3) void gru_step_fwd_kernel(const float* __res
 #pragma unroll
         for (int i = 0; i < NB; ++i) Bs[buf][kk][rbase + RP * i] = rb[S][i];
     };
-    f32x16 acc[3];
+    f32x16 acc[NG];
 #pragma unroll
-    for (int g = 0; g < 3; ++g)
+    for (int g = 0; g < NG; ++g)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[g][r] = 0.f;
     const int half = lane >> 5, l31 = lane & 31;
@@ -473,7 +473,7 @@ __global__ __launch_bounds__(256, 3) void gru_step_fwd_kernel(const float* __res
         for (int kp = 0; kp < BK / 2; ++kp) {
             const float a = ap[2 * kp * LDAg];
 #pragma unroll
-            for (int g = 0; g < 3; ++g)
+            for (int g = 0; g < NG; ++g)
                 acc[g] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bp[2 * kp * LDBg + 32 * g], acc[g], 0, 0, 0);
         }
     };
@@ -499,167 +499,55 @@ __global__ __launch_bounds__(256, 3) void gru_step_fwd_kernel(const float* __res
     store_tile(S1{}, buf ^ 1);
     __syncthreads();
     mfma(buf ^ 1);
-
-    // epilogue: gate math; gi / h_{t-1} come in through unconditional buffer loads (rows >= R read 0)
-    const int j = j0 + l31;
-    const float br = bhh[j], bz = bhh[H + j], bn = bhh[2 * H + j];
-    const rsrc_t gres = make_rsrc_bytes(gi, (long long)R * 3 * H * 4), hres = make_rsrc_bytes(hprev, (long long)R * H * 4);
-    const int row0 = m0 + wm_off + 4 * half;
-    float gr[16], gz[16], gn[16], hp[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int ro = (r & 3) + 8 * (r >> 2);
-        const u32 go = (u32)((row0 + ro) * 3 * H + j) * 4u;
-        gr[r] = bload(gres, go, 0u);
-        gz[r] = bload(gres, go, (u32)H * 4u);
-        gn[r] = bload(gres, go, (u32)H * 8u);
-        hp[r] = bload(hres, (u32)((row0 + ro) * H + j) * 4u, 0u);
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int row = row0 + (r & 3) + 8 * (r >> 2);
-        const float rg = dtc::sigmoid(gr[r] + (acc[0][r] + br));
-        const float zg = dtc::sigmoid(gz[r] + (acc[1][r] + bz));
-        const float ghn = acc[2][r] + bn;
-        const float ng = tanhf(gn[r] + rg * ghn);
-        if (row < R) {
-            const long long e = (long long)row * H + j;
-            float* gp = gates + (long long)row * 3 * H + j;
-            hout[e] = (1.0f - zg) * ng + zg * hp[r];
-            gp[0] = rg;
-            gp[H] = zg;
-            gp[2 * H] = ng;
-            hn[e] = ghn;
-        }
-    }
+    epilogue(acc, m0 + wm_off + 4 * half, j0 + l31);
 }
 
-// ------------------------------------------------------------------------------------------
-// One fused LSTM time step (forward): a = gi_t + h_{t-1} W_hh^T + b_hh for the four gates of 32 hidden units, then the
-// gate math of torch.nn.LSTM (gate order i, f, g, o) in the epilogue -- the [R,4H] recurrent pre-activations never
-// touch HBM:
-//   i, f, o = sigmoid(a_i, a_f, a_o), g = tanh(a_g), c_t = f * c_{t-1} + i * g, h_t = o * tanh(c_t)
-// Block tile: 128 rows x (32 units x 4 gates): the loader reads rows j, H+j, 2H+j, 3H+j of W_hh in place (no repacked
-// weights); wave w owns rows 32w..32w+31 and four 32x32 MFMA tiles (i, f, g, o of the same units).  K loop of
-// gru_step_fwd_kernel (loads two K steps ahead of the MFMAs).
-// ------------------------------------------------------------------------------------------
+// torch.nn.GRU's step: three gates, the cell on the 32 x 32 accumulator layout (gru_epilogue_32x32, gru_internal.hpp)
+__global__ __launch_bounds__(256, 3) void gru_step_fwd_kernel(const float* __restrict__ hprev, const float* __restrict__ Whh,
+                                                           const float* __restrict__ bhh, const float* __restrict__ gi,
+                                                           float* __restrict__ hout, float* __restrict__ gates,
+                                                           float* __restrict__ hn, int R, int H) {
+    rnn_step_fwd_body<3>(hprev, Whh, R, H, [&](const f32x16 (&acc)[3], int row0, int j) {
+        gru_epilogue_32x32(acc[0], acc[1], acc[2], row0, j, hprev, H, bhh, gi, hout, gates, hn, R, H);
+    });
+}
+
+// torch.nn.LSTM's step: four gates (i, f, g, o), the cell of rnn_cells.hpp
 __global__ __launch_bounds__(256, 3) void lstm_step_fwd_kernel(const float* __restrict__ hprev, const float* __restrict__ cprev,
                                                             const float* __restrict__ Whh, const float* __restrict__ bhh,
                                                             const float* __restrict__ gi, float* __restrict__ hout,
                                                             float* __restrict__ cout, float* __restrict__ gates, int R, int H) {
-    constexpr int GB = 128, LDAg = BM + PAD, LDBg = GB + PAD;
-    __shared__ float As[2][BK][LDAg];
-    __shared__ float Bs[2][BK][LDBg];
-    int tr, tc;
-    if (!map_tile(blockIdx.x, (R + BM - 1) / BM, H / 32, tr, tc)) return;
-    const int m0 = tr * BM, j0 = tc * 32;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm_off = wave * 32;
-    const int kk = tid & (BK - 1), rbase = tid / BK;
-    constexpr int NA = BM / RP, NB = GB / RP;
-    u32 aoff[NA], woff[NB];
+    rnn_step_fwd_body<4>(hprev, Whh, R, H, [&](const f32x16 (&acc)[4], int row0, int j) {
+        // gi / c_{t-1} come in through unconditional buffer loads (rows >= R read 0)
+        const float bi = bhh[j], bf = bhh[H + j], bg = bhh[2 * H + j], bo = bhh[3 * H + j];
+        const rsrc_t gres = make_rsrc_bytes(gi, (long long)R * 4 * H * 4), cres = make_rsrc_bytes(cprev, (long long)R * H * 4);
+        float gvi[16], gvf[16], gvg[16], gvo[16], cp[16];
 #pragma unroll
-    for (int i = 0; i < NA; ++i) {
-        const int m = m0 + rbase + RP * i;
-        aoff[i] = m < R ? (u32)(m * H + kk) * 4u : INVALID;
-    }
-#pragma unroll
-    for (int i = 0; i < NB; ++i) {
-        const int n = rbase + RP * i;                       // 0..127: gate n / 32, unit j0 + n % 32
-        woff[i] = (u32)(((n >> 5) * H + j0 + (n & 31)) * H + kk) * 4u;
-    }
-    const rsrc_t ares = make_rsrc(hprev), wres = make_rsrc(Whh);
-    float ra[2][NA], rb[2][NB];
-    auto load_tile = [&](auto set, int kt) {
-        constexpr int S = decltype(set)::value;
-        const u32 ko = (u32)(kt * BK) * 4u;
-#pragma unroll
-        for (int i = 0; i < NA; ++i) ra[S][i] = bload(ares, aoff[i], ko);
-#pragma unroll
-        for (int i = 0; i < NB; ++i) rb[S][i] = bload(wres, woff[i], ko);
-    };
-    auto store_tile = [&](auto set, int buf) {
-        constexpr int S = decltype(set)::value;
-#pragma unroll
-        for (int i = 0; i < NA; ++i) As[buf][kk][rbase + RP * i] = ra[S][i];
-#pragma unroll
-        for (int i = 0; i < NB; ++i) Bs[buf][kk][rbase + RP * i] = rb[S][i];
-    };
-    f32x16 acc[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[g][r] = 0.f;
-    const int half = lane >> 5, l31 = lane & 31;
-    auto mfma = [&](int buf) {
-        const float* ap = &As[buf][0][0] + half * LDAg + wm_off + l31;
-        const float* bp = &Bs[buf][0][0] + half * LDBg + l31;
-#pragma unroll
-        for (int kp = 0; kp < BK / 2; ++kp) {
-            const float a = ap[2 * kp * LDAg];
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-                acc[g] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bp[2 * kp * LDBg + 32 * g], acc[g], 0, 0, 0);
+        for (int r = 0; r < 16; ++r) {
+            const int ro = (r & 3) + 8 * (r >> 2);
+            const u32 go = (u32)((row0 + ro) * 4 * H + j) * 4u;
+            gvi[r] = bload(gres, go, 0u);
+            gvf[r] = bload(gres, go, (u32)H * 4u);
+            gvg[r] = bload(gres, go, (u32)H * 8u);
+            gvo[r] = bload(gres, go, (u32)H * 12u);
+            cp[r] = bload(cres, (u32)((row0 + ro) * H + j) * 4u, 0u);
         }
-    };
-    const int KT = H / BK;                                  // even: H is a multiple of 32
-    int buf = 0;
-    load_tile(S0{}, 0);
-    store_tile(S0{}, 0);
-    __syncthreads();
-    load_tile(S1{}, 1);                                     // invariant: LDS[buf] = tile kt, set 1 = tile kt+1 in flight
-    for (int kt = 0; kt + 2 < KT; kt += 2) {
-        load_tile(S0{}, kt + 2);
-        mfma(buf);
-        store_tile(S1{}, buf ^ 1);
-        __syncthreads();
-        buf ^= 1;
-        load_tile(S1{}, kt + 3);
-        mfma(buf);
-        store_tile(S0{}, buf ^ 1);
-        __syncthreads();
-        buf ^= 1;
-    }
-    mfma(buf);
-    store_tile(S1{}, buf ^ 1);
-    __syncthreads();
-    mfma(buf ^ 1);
-
-    // epilogue: gate math; gi / c_{t-1} come in through unconditional buffer loads (rows >= R read 0)
-    const int j = j0 + l31;
-    const float bi = bhh[j], bf = bhh[H + j], bg = bhh[2 * H + j], bo = bhh[3 * H + j];
-    const rsrc_t gres = make_rsrc_bytes(gi, (long long)R * 4 * H * 4), cres = make_rsrc_bytes(cprev, (long long)R * H * 4);
-    const int row0 = m0 + wm_off + 4 * half;
-    float gvi[16], gvf[16], gvg[16], gvo[16], cp[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int ro = (r & 3) + 8 * (r >> 2);
-        const u32 go = (u32)((row0 + ro) * 4 * H + j) * 4u;
-        gvi[r] = bload(gres, go, 0u);
-        gvf[r] = bload(gres, go, (u32)H * 4u);
-        gvg[r] = bload(gres, go, (u32)H * 8u);
-        gvo[r] = bload(gres, go, (u32)H * 12u);
-        cp[r] = bload(cres, (u32)((row0 + ro) * H + j) * 4u, 0u);
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int row = row0 + (r & 3) + 8 * (r >> 2);
-        const float ig = dtc::sigmoid(gvi[r] + (acc[0][r] + bi));
-        const float fg = dtc::sigmoid(gvf[r] + (acc[1][r] + bf));
-        const float gg = tanhf(gvg[r] + (acc[2][r] + bg));
-        const float og = dtc::sigmoid(gvo[r] + (acc[3][r] + bo));
-        const float c = fg * cp[r] + ig * gg;
-        if (row < R) {
-            const long long e = (long long)row * H + j;
-            float* gp = gates + (long long)row * 4 * H + j;
-            cout[e] = c;
-            hout[e] = og * tanhf(c);
-            gp[0] = ig;
-            gp[H] = fg;
-            gp[2 * H] = gg;
-            gp[3 * H] = og;
+        for (int r = 0; r < 16; ++r) {
+            const int row = row0 + (r & 3) + 8 * (r >> 2);
+            const dtc::LstmCell c = dtc::lstm_cell_fwd(gvi[r], gvf[r], gvg[r], gvo[r], acc[0][r] + bi, acc[1][r] + bf, acc[2][r] + bg, acc[3][r] + bo, cp[r]);
+            if (row < R) {
+                const long long e = (long long)row * H + j;
+                float* gp = gates + (long long)row * 4 * H + j;
+                cout[e] = c.c;
+                hout[e] = c.h;
+                gp[0] = c.i;
+                gp[H] = c.f;
+                gp[2 * H] = c.g;
+                gp[3 * H] = c.o;
+            }
         }
-    }
+    });
 }
 
 // ------------------------------------------------------------------------------------------

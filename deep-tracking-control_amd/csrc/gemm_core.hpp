@@ -196,7 +196,6 @@ __device__ __forceinline__ f32x4 patch_get(const float* patch, int row, int c4) 
     return *reinterpret_cast<const f32x4*>(&patch[row * LDW + 4 * c4]);
 }
 
-
 constexpr long long MAX_ELEMS = (1ll << 29) - 1;     // lane byte offsets must stay below 2 GiB (INVALID = 2^31)
 
 // a source segment whose matrix the 32-bit lane offsets cannot span: only the kernels with 64-bit lane addresses take it (wide_ok)

@@ -5,6 +5,8 @@
 // padded trajectories [T, n_traj, .] with saved initial hidden states during the policy update (BPTT) and
 // over [1, N, .] during the rollout.
 //
+// The gate arithmetic of every kernel here and in the other recurrence sources is the cell of rnn_cells.hpp.
+//
 // Structure (all launches are issued from this C++ loop -- no Python between time steps):
 //   forward  t = 0..T-1 : gh = h_{t-1} W_hh^T + b_hh and the gate math in its epilogue: ONE kernel per step
 //                         (dtc_gru_step_fwd in gemm.hip; saves r,z,n and gh_n; DTC_GRU_UNFUSED=1 selects the older
@@ -21,6 +23,7 @@
 #include <stdlib.h>
 
 #include "gru_internal.hpp"
+#include "rnn_cells.hpp"
 
 namespace {
 
@@ -35,16 +38,13 @@ __global__ __launch_bounds__(256) void gru_gate_fwd_kernel(const float* __restri
     const int j = (int)(e - row * H);
     const float* gir = gi + row * 3 * H;
     const float* ghr = gh + row * 3 * H;
-    const float r = dtc::sigmoid(gir[j] + ghr[j]);
-    const float z = dtc::sigmoid(gir[H + j] + ghr[H + j]);
     const float ghn = ghr[2 * H + j];
-    const float n = tanhf(gir[2 * H + j] + r * ghn);
-    const float hp = hprev[e];
-    hout[e] = (1.0f - z) * n + z * hp;
+    const dtc::GruCell c = dtc::gru_cell_fwd(gir[j], gir[H + j], gir[2 * H + j], ghr[j], ghr[H + j], ghn, hprev[e]);
+    hout[e] = c.h;
     float* g = gates + row * 3 * H;
-    g[j] = r;
-    g[H + j] = z;
-    g[2 * H + j] = n;
+    g[j] = c.r;
+    g[H + j] = c.z;
+    g[2 * H + j] = c.n;
     hn[e] = ghn;
 }
 
@@ -60,27 +60,21 @@ __global__ __launch_bounds__(256) void gru_gate_bwd_kernel(const float* __restri
     const long long row = e / H;
     const int j = (int)(e - row * H);
     const float* g = gates + row * 3 * H;
-    const float r = g[j], z = g[H + j], n = g[2 * H + j];
     float d = dhs_t[e] + dh[e];
     if (part) {
         const long long rh = (long long)R * H;
         for (int c = 0; c < nparts; ++c) d += part[c * rh + e];              // fixed order
     }
-    const float ghn = hn[e];
-    const float dn = d * (1.0f - z);
-    const float dz = d * (hprev[e] - n);
-    const float da_n = dn * (1.0f - n * n);
-    const float da_z = dz * (z * (1.0f - z));
-    const float da_r = (da_n * ghn) * (r * (1.0f - r));
+    const dtc::GruCellGrad c = dtc::gru_cell_bwd(d, g[j], g[H + j], g[2 * H + j], hn[e], hprev[e]);
     float* gi_o = dgi + row * 3 * H;
     float* gh_o = dgh + row * 3 * H;
-    gi_o[j] = da_r;
-    gi_o[H + j] = da_z;
-    gi_o[2 * H + j] = da_n;
-    gh_o[j] = da_r;
-    gh_o[H + j] = da_z;
-    gh_o[2 * H + j] = da_n * r;
-    dh[e] = d * z;
+    gi_o[j] = c.da_r;
+    gi_o[H + j] = c.da_z;
+    gi_o[2 * H + j] = c.da_n;
+    gh_o[j] = c.da_r;
+    gh_o[H + j] = c.da_z;
+    gh_o[2 * H + j] = c.da_nr;
+    dh[e] = c.dh_z;
 }
 
 // the same with four consecutive hidden units per thread (H % 4 == 0, 16-byte aligned rows): 16-byte loads / stores -- the kernel moves
@@ -123,14 +117,13 @@ __global__ __launch_bounds__(256) void gru_gate_bwd4_kernel(const GateBwdPtrs p0
     const f4 ghn = *reinterpret_cast<const f4*>(hn + e), hp = *reinterpret_cast<const f4*>(hprev + e);
     f4 da_r, da_z, da_n, da_nr, dz4;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {                       // the scalar kernel's arithmetic, element by element (same rounding)
-        const float dn = d[k] * (1.0f - z[k]);
-        const float dz = d[k] * (hp[k] - n[k]);
-        da_n[k] = dn * (1.0f - n[k] * n[k]);
-        da_z[k] = dz * (z[k] * (1.0f - z[k]));
-        da_r[k] = (da_n[k] * ghn[k]) * (r[k] * (1.0f - r[k]));
-        da_nr[k] = da_n[k] * r[k];
-        dz4[k] = d[k] * z[k];
+    for (int k = 0; k < 4; ++k) {
+        const dtc::GruCellGrad c = dtc::gru_cell_bwd(d[k], r[k], z[k], n[k], ghn[k], hp[k]);
+        da_r[k] = c.da_r;
+        da_z[k] = c.da_z;
+        da_n[k] = c.da_n;
+        da_nr[k] = c.da_nr;
+        dz4[k] = c.dh_z;
     }
     float* gi_o = dgi + row * 3 * H;
     float* gh_o = dgh + row * 3 * H;

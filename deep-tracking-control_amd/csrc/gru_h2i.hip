@@ -15,7 +15,7 @@
 //   gru_h2i_kernel<FWD>     gh = h_{t-1} W_hh^T from the two images + torch.nn.GRU's gate math; writes fp32 h_t / gates / gh_n, h_t as the
 //                           image rows of step t + 1 and, with a slot map, as rows of the head's valid-row images hx (MLP input) and hp
 //                           (h_{t-1} operand of the W_hh weight gradient)
-//   gru_h2i_gate_bwd_kernel the gate derivatives (twin of gru_gate_bwd4_kernel, same arithmetic and summation order); writes fp32 dgi_t /
+//   gru_h2i_gate_bwd_kernel the gate derivatives (the cell of rnn_cells.hpp, gru_gate_bwd4_kernel's summation order); writes fp32 dgi_t /
 //                           dgh_t, dgh_t as image rows with per-row, per-block exponents and, with a slot map, the rows of the head's
 //                           weight-gradient images
 //   gru_h2i_kernel<BWD>     the chunks of dh_{t-1} += dgh_t W_hh from the dgh_t image and the W_hh^T image -> fp32 part[c]
@@ -24,13 +24,15 @@
 // batch row and four CONSECUTIVE columns per register group -- 16-byte fp32 and 8-byte image stores straight from the accumulators.
 // Accumulator (weight row w, batch row m) carries the scale 2^(ew(w, block) + ea(m, block)); it is rescaled (v_ldexp_f32, exact) at the
 // borders of the 128-column blocks: the weight part from a table in LDS, the row part from the lane's exponent.
-// Launch shape as gru_s3.hip: one workgroup per CU, a column tile (and chunk) per XCD for all row tiles, operands two stages ahead.
+// Launch shape as gru_s3.hip: one workgroup per CU, a column tile (and chunk) per XCD for all row tiles (gru_xcd_tile, gru_internal.hpp),
+// operands two stages ahead.  The gate arithmetic is the cell of rnn_cells.hpp; what is about the image format is in h2i_core.hpp.
 #include <stdlib.h>
 
 #include <type_traits>
 
 #include "gru_internal.hpp"
 #include "h2i_core.hpp"
+#include "rnn_cells.hpp"
 
 namespace {
 
@@ -80,18 +82,6 @@ __global__ __launch_bounds__(256) void gru_h2i_wimage_kernel(const float* __rest
     }
 }
 
-// exponent of (row, block kb) of image(M, K)
-__device__ __forceinline__ void gh_store_exp(void* img, long long M, int K, int row, int kb, int e) {
-    int* exps = reinterpret_cast<int*>(static_cast<char*>(img) + hi_data_bytes(M, K));
-    exps[((long long)(row >> 7) * hi_kblocks(K) + kb) * 128 + (row & 127)] = e;
-}
-// 8 consecutive columns (col0 % 8 == 0) of one row: one 16-byte piece per plane
-__device__ __forceinline__ void gh_store8(void* img, int K, int row, int col0, const HiPiece& pc) {
-    u32x4* chunk = static_cast<u32x4*>(img) + ((long long)(row >> 7) * hi_stages(K) + (col0 >> 4)) * (HI_CHUNK / 16);
-    chunk[rslot(row & 127, (col0 >> 3) & 1)] = pc.p[0];
-    chunk[256 + rslot(row & 127, (col0 >> 3) & 1)] = pc.p[1];
-}
-
 // one wave per row: the row's exponent for the call, h0 as the image rows of step 0 (and of hp where slot0 names a valid row), h0 as
 // hs_all[0]; the exponent tables of both step images (every block of a row carries e_r)
 __global__ __launch_bounds__(256) void gru_h2i_h0_kernel(const float* __restrict__ h0, float* __restrict__ hs0, void* img0, void* img1,
@@ -120,13 +110,13 @@ __global__ __launch_bounds__(256) void gru_h2i_h0_kernel(const float* __restrict
         *reinterpret_cast<f32x4*>(hs0 + (long long)row * H + c) = q[0];
         *reinterpret_cast<f32x4*>(hs0 + (long long)row * H + c + 4) = q[1];
         const HiPiece pc = hi_split8(q, e);
-        gh_store8(img0, H, row, c, pc);
-        if (to_hp) gh_store8(hp_img, H, s, c, pc);
+        hi_store8(img0, H, row, c, pc);
+        if (to_hp) hi_store8(hp_img, H, s, c, pc);
     }
     for (int kb = lane; kb < H / 128; kb += 64) {
-        gh_store_exp(img0, R, H, row, kb, e);
-        gh_store_exp(img1, R, H, row, kb, e);
-        if (to_hp) gh_store_exp(hp_img, M_valid, H, s, kb, e);
+        hi_store_exp(img0, R, H, row, kb, e);
+        hi_store_exp(img1, R, H, row, kb, e);
+        if (to_hp) hi_store_exp(hp_img, M_valid, H, s, kb, e);
     }
     if (lane == 0) erow[row] = e;
 }
@@ -178,14 +168,9 @@ __global__ __launch_bounds__(256, 2) void gru_h2i_kernel(const GruH2iArgs a) {
     constexpr int TW = MODE == MODE_FWD ? 3 : 2;             // 32-row weight tiles per wave
 #define GAS(b) ((b) == 0 ? GAs0 : (b) == 1 ? GAs1 : GAs2)
 #define GWS(b) ((b) == 0 ? GWs0 : (b) == 1 ? GWs1 : GWs2)
-    // XCD x (= blockIdx.x & 7) owns a fixed set of (column tile, chunk) pairs for ALL row tiles: its slice of the W_hh image stays in its L2
-    // over the time steps (gru_s3_kernel)
-    const int col_tiles = MODE == MODE_FWD ? a.H / 32 : a.H / 128;
-    const int row_tiles = (a.R + 127) >> 7, combos = col_tiles * a.nparts, per_xcd = (combos + 7) >> 3;
-    const int xcd = blockIdx.x & 7, jb = blockIdx.x >> 3, cl = jb / row_tiles;
-    const int tr = jb - cl * row_tiles, combo = xcd * per_xcd + cl;
-    if (cl >= per_xcd || combo >= combos) return;
-    const int chunk = combo / col_tiles, tc = combo - chunk * col_tiles;
+    const dtc::GruXcdTile tile = dtc::gru_xcd_tile(blockIdx.x, (a.R + 127) >> 7, MODE == MODE_FWD ? a.H / 32 : a.H / 128, a.nparts);
+    if (!tile.valid) return;
+    const int tr = tile.tr, tc = tile.tc, chunk = tile.chunk;
     const int m0 = tr * 128;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -322,8 +307,8 @@ __global__ __launch_bounds__(256, 2) void gru_h2i_kernel(const GruH2iArgs a) {
 
     const int R = a.R, H = a.H;
     if constexpr (MODE == MODE_FWD) {
-        // gate math of torch.nn.GRU (gru_step_fwd_kernel): r = sigmoid(gi_r + gh_r), z = sigmoid(gi_z + gh_z), n = tanh(gi_n + r * gh_n),
-        // h_t = (1 - z) * n + z * h_{t-1}; the lane holds the three pre-activations of batch row `row`, units u0 + 8 g + 4 half + (0..3)
+        // gate math of torch.nn.GRU (rnn_cells.hpp); the lane holds the three pre-activations of batch row `row`, units
+        // 32 tc + 8 g + 4 half + (0..3)
         const int row = m0 + wb_off + l31;
         if (row < R) {
             const int er = a.erow ? a.erow[row] : 0;
@@ -347,11 +332,12 @@ __global__ __launch_bounds__(256, 2) void gru_h2i_kernel(const GruH2iArgs a) {
                 f32x4 rg, zg, ng, ghn, ho;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    rg[e] = dtc::sigmoid(gr[e] + (acc[0][0][4 * g + e] + br[e]));
-                    zg[e] = dtc::sigmoid(gz[e] + (acc[0][1][4 * g + e] + bz[e]));
                     ghn[e] = acc[0][2][4 * g + e] + bn[e];
-                    ng[e] = tanhf(gn[e] + rg[e] * ghn[e]);
-                    ho[e] = (1.0f - zg[e]) * ng[e] + zg[e] * hp[e];
+                    const dtc::GruCell c = dtc::gru_cell_fwd(gr[e], gz[e], gn[e], acc[0][0][4 * g + e] + br[e], acc[0][1][4 * g + e] + bz[e], ghn[e], hp[e]);
+                    rg[e] = c.r;
+                    zg[e] = c.z;
+                    ng[e] = c.n;
+                    ho[e] = c.h;
                 }
                 *reinterpret_cast<f32x4*>(a.hout + (long long)row * H + u) = ho;
                 *reinterpret_cast<f32x4*>(gtr + u) = rg;
@@ -363,8 +349,8 @@ __global__ __launch_bounds__(256, 2) void gru_h2i_kernel(const GruH2iArgs a) {
                 if (to_p) hi_store4(a.hp_img, H, sp, u, ho, er);
             }
             if ((tc & 3) == 0 && half == 0) {            // the first lane of the row's 128-column block: its exponent in the valid-row images
-                if (to_x) gh_store_exp(a.hx_img, a.M_valid, H, sx, tc >> 2, er);
-                if (to_p) gh_store_exp(a.hp_img, a.M_valid, H, sp, tc >> 2, er);
+                if (to_x) hi_store_exp(a.hx_img, a.M_valid, H, sx, tc >> 2, er);
+                if (to_p) hi_store_exp(a.hp_img, a.M_valid, H, sp, tc >> 2, er);
             }
         }
     } else {
@@ -409,23 +395,6 @@ struct GateH2iArgs {
     void* dgi_img;              // [M, 3H]
     int R, H, nparts;
 };
-__device__ __forceinline__ u32 max4_bits(f32x4 v) {
-    u32 m = finite_bits(v[0]);
-#pragma unroll
-    for (int k = 1; k < 4; ++k) {
-        const u32 b = finite_bits(v[k]);
-        m = b > m ? b : m;
-    }
-    return m;
-}
-__device__ __forceinline__ int half_wave_exp(u32 m) {
-#pragma unroll
-    for (int off = 16; off >= 1; off >>= 1) {
-        const u32 o = (u32)__shfl_xor((int)m, off, 64);
-        m = o > m ? o : m;
-    }
-    return hi_exp(m);
-}
 __global__ __launch_bounds__(256) void gru_h2i_gate_bwd_kernel(const GateH2iArgs P) {
     const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;      // group of four units
     const int H = P.H, hq = H >> 2;
@@ -443,14 +412,13 @@ __global__ __launch_bounds__(256) void gru_h2i_gate_bwd_kernel(const GateH2iArgs
     const f32x4 ghn = *reinterpret_cast<const f32x4*>(P.hn + e), hp = *reinterpret_cast<const f32x4*>(P.hprev + e);
     f32x4 da_r, da_z, da_n, da_nr, dz4;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {                       // gru_gate_bwd_kernel's arithmetic, element by element (same rounding)
-        const float dn = d[k] * (1.0f - z[k]);
-        const float dz = d[k] * (hp[k] - n[k]);
-        da_n[k] = dn * (1.0f - n[k] * n[k]);
-        da_z[k] = dz * (z[k] * (1.0f - z[k]));
-        da_r[k] = (da_n[k] * ghn[k]) * (r[k] * (1.0f - r[k]));
-        da_nr[k] = da_n[k] * r[k];
-        dz4[k] = d[k] * z[k];
+    for (int k = 0; k < 4; ++k) {
+        const dtc::GruCellGrad c = dtc::gru_cell_bwd(d[k], r[k], z[k], n[k], ghn[k], hp[k]);
+        da_r[k] = c.da_r;
+        da_z[k] = c.da_z;
+        da_n[k] = c.da_n;
+        da_nr[k] = c.da_nr;
+        dz4[k] = c.dh_z;
     }
     float* gi_o = P.dgi + (long long)row * 3 * H;
     float* gh_o = P.dgh + (long long)row * 3 * H;
@@ -463,17 +431,17 @@ __global__ __launch_bounds__(256) void gru_h2i_gate_bwd_kernel(const GateH2iArgs
     *reinterpret_cast<f32x4*>(P.dh + e) = dz4;
 
     // image rows: true exponents per row and block of 128 columns (gradients span many octaves)
-    const int e_r = half_wave_exp(max4_bits(da_r)), e_z = half_wave_exp(max4_bits(da_z)), e_n = half_wave_exp(max4_bits(da_n)),
-              e_nr = half_wave_exp(max4_bits(da_nr));
+    const int e_r = hi_half_wave_exp(hi_max4_bits(da_r)), e_z = hi_half_wave_exp(hi_max4_bits(da_z)), e_n = hi_half_wave_exp(hi_max4_bits(da_n)),
+              e_nr = hi_half_wave_exp(hi_max4_bits(da_nr));
     const int kb = j >> 7, hb = H >> 7;
     const bool first = (threadIdx.x & 31) == 0;
     hi_store4(P.step_img, 3 * H, row, j, da_r, e_r);
     hi_store4(P.step_img, 3 * H, row, H + j, da_z, e_z);
     hi_store4(P.step_img, 3 * H, row, 2 * H + j, da_nr, e_nr);
     if (first) {
-        gh_store_exp(P.step_img, P.R, 3 * H, row, kb, e_r);
-        gh_store_exp(P.step_img, P.R, 3 * H, row, hb + kb, e_z);
-        gh_store_exp(P.step_img, P.R, 3 * H, row, 2 * hb + kb, e_nr);
+        hi_store_exp(P.step_img, P.R, 3 * H, row, kb, e_r);
+        hi_store_exp(P.step_img, P.R, 3 * H, row, hb + kb, e_z);
+        hi_store_exp(P.step_img, P.R, 3 * H, row, 2 * hb + kb, e_nr);
     }
     const int s = P.slot ? P.slot[row] : -1;
     if (s < 0 || s >= P.M_valid) return;
@@ -482,26 +450,26 @@ __global__ __launch_bounds__(256) void gru_h2i_gate_bwd_kernel(const GateH2iArgs
         hi_store4(P.drz_img, 2 * H, s, j, da_r, e_r);
         hi_store4(P.drz_img, 2 * H, s, H + j, da_z, e_z);
         if (first) {
-            gh_store_exp(P.drz_img, M, 2 * H, s, kb, e_r);
-            gh_store_exp(P.drz_img, M, 2 * H, s, hb + kb, e_z);
+            hi_store_exp(P.drz_img, M, 2 * H, s, kb, e_r);
+            hi_store_exp(P.drz_img, M, 2 * H, s, hb + kb, e_z);
         }
     }
     if (P.dnh_img) {
         hi_store4(P.dnh_img, H, s, j, da_nr, e_nr);
-        if (first) gh_store_exp(P.dnh_img, M, H, s, kb, e_nr);
+        if (first) hi_store_exp(P.dnh_img, M, H, s, kb, e_nr);
     }
     if (P.dni_img) {
         hi_store4(P.dni_img, H, s, j, da_n, e_n);
-        if (first) gh_store_exp(P.dni_img, M, H, s, kb, e_n);
+        if (first) hi_store_exp(P.dni_img, M, H, s, kb, e_n);
     }
     if (P.dgh_img) {
         hi_store4(P.dgh_img, 3 * H, s, j, da_r, e_r);
         hi_store4(P.dgh_img, 3 * H, s, H + j, da_z, e_z);
         hi_store4(P.dgh_img, 3 * H, s, 2 * H + j, da_nr, e_nr);
         if (first) {
-            gh_store_exp(P.dgh_img, M, 3 * H, s, kb, e_r);
-            gh_store_exp(P.dgh_img, M, 3 * H, s, hb + kb, e_z);
-            gh_store_exp(P.dgh_img, M, 3 * H, s, 2 * hb + kb, e_nr);
+            hi_store_exp(P.dgh_img, M, 3 * H, s, kb, e_r);
+            hi_store_exp(P.dgh_img, M, 3 * H, s, hb + kb, e_z);
+            hi_store_exp(P.dgh_img, M, 3 * H, s, 2 * hb + kb, e_nr);
         }
     }
     if (P.dgi_img) {
@@ -509,9 +477,9 @@ __global__ __launch_bounds__(256) void gru_h2i_gate_bwd_kernel(const GateH2iArgs
         hi_store4(P.dgi_img, 3 * H, s, H + j, da_z, e_z);
         hi_store4(P.dgi_img, 3 * H, s, 2 * H + j, da_n, e_n);
         if (first) {
-            gh_store_exp(P.dgi_img, M, 3 * H, s, kb, e_r);
-            gh_store_exp(P.dgi_img, M, 3 * H, s, hb + kb, e_z);
-            gh_store_exp(P.dgi_img, M, 3 * H, s, 2 * hb + kb, e_n);
+            hi_store_exp(P.dgi_img, M, 3 * H, s, kb, e_r);
+            hi_store_exp(P.dgi_img, M, 3 * H, s, hb + kb, e_z);
+            hi_store_exp(P.dgi_img, M, 3 * H, s, 2 * hb + kb, e_n);
         }
     }
 }
@@ -538,8 +506,6 @@ GhLayout gh_layout(int T, int R, int H) {
 }
 
 int g_h2i_mode = -1;                 // -1: DTC_GRU_H2I decides (default off), 0 / 1: dtc_set_gru_h2i
-
-unsigned grid_of(int R, int col_tiles, int nparts) { return (unsigned)(8 * dtc::ceil_div((int64_t)col_tiles * nparts, 8) * dtc::ceil_div(R, 128)); }
 
 }  // namespace
 
@@ -619,7 +585,7 @@ extern "C" int dtc_gru_step_fwd_h2i(const void* hprev_img, const float* hprev, c
     a.M_valid = M_valid;
     hipStream_t s = (hipStream_t)stream;
     dtc::ProfScope prof(dtc::prof_shape_name("gru_step_fwd_h2i", R, 3 * H, H), 2.0 * R * 3.0 * H * H, s);
-    hipLaunchKernelGGL(gru_h2i_kernel<MODE_FWD>, dim3(grid_of(R, H / 32, 1)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(gru_h2i_kernel<MODE_FWD>, dim3(dtc::gru_xcd_grid((int)dtc::ceil_div(R, 128), H / 32, 1)), dim3(256), 0, s, a);
     return dtc::check_launch("gru_step_fwd_h2i");
 }
 
@@ -639,7 +605,7 @@ extern "C" int dtc_gru_dgrad_parts_h2i(const void* dgh_img, const void* wimg, fl
     a.part_stride = part_stride;
     hipStream_t s = (hipStream_t)stream;
     dtc::ProfScope prof(dtc::prof_shape_name("gru_dgrad_h2i", R, 3 * H, H), 2.0 * R * 3.0 * H * H, s);
-    hipLaunchKernelGGL(gru_h2i_kernel<MODE_BWD>, dim3(grid_of(R, H / 128, nparts)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(gru_h2i_kernel<MODE_BWD>, dim3(dtc::gru_xcd_grid((int)dtc::ceil_div(R, 128), H / 128, nparts)), dim3(256), 0, s, a);
     return dtc::check_launch("gru_dgrad_parts_h2i");
 }
 

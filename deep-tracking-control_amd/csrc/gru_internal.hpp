@@ -1,6 +1,50 @@
-// What the recurrence sources (gru.hip, gru_s3.hip, gru_h2i.hip, lstm.hip) share on the host side.  Not part of the C ABI.
+// What the recurrence sources (gru.hip, gru_s3.hip, gru_h2i.hip, lstm.hip and the fused steps of gemm.hip) share besides the cells of
+// rnn_cells.hpp: host helpers of the drivers, and two pieces of device code with more than one user -- the GRU epilogue on the 32 x 32
+// accumulator layout and the workgroup -> tile map of the per-step GRU kernels, with the grid size that goes with it.  Not part of the
+// C ABI.
 #pragma once
-#include "common.hpp"
+#include "gemm_core.hpp"      // f32x16 and the buffer loads of the epilogue below (gru.hip / lstm.hip use only the host helpers)
+#include "rnn_cells.hpp"
+
+namespace {
+
+// torch.nn.GRU's gate math on the 32 x 32 accumulator layout: the epilogue of the fused forward steps (gru_step_fwd_kernel in gemm.hip,
+// gru_s3_kernel<FWD> in gru_s3.hip).  The lane holds unit j and the 16 rows row0 + (r & 3) + 8 * (r >> 2) of acc_*[r] = the three
+// gates' h_{t-1} W_hh^T (bias not yet added); ldh = row stride of hprev.  gi / h_{t-1} come in through unconditional buffer loads
+// (rows >= R read 0); saves r, z, n and gh_n.
+__device__ __forceinline__ void gru_epilogue_32x32(const f32x16& acc_r, const f32x16& acc_z, const f32x16& acc_n, int row0, int j,
+                                                   const float* hprev, long long ldh, const float* bhh, const float* gi, float* hout,
+                                                   float* gates, float* hn, int R, int H) {
+    const float br = bhh[j], bz = bhh[H + j], bn = bhh[2 * H + j];
+    const rsrc_t gres = make_rsrc_bytes(gi, (long long)R * 3 * H * 4), hres = make_rsrc_bytes(hprev, (long long)R * ldh * 4);
+    float gr[16], gz[16], gn[16], hp[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int ro = (r & 3) + 8 * (r >> 2);
+        const u32 go = (u32)((row0 + ro) * 3 * H + j) * 4u;
+        gr[r] = bload(gres, go, 0u);
+        gz[r] = bload(gres, go, (u32)H * 4u);
+        gn[r] = bload(gres, go, (u32)H * 8u);
+        hp[r] = bload(hres, (u32)((long long)(row0 + ro) * ldh + j) * 4u, 0u);
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int row = row0 + (r & 3) + 8 * (r >> 2);
+        const float ghn = acc_n[r] + bn;
+        const dtc::GruCell c = dtc::gru_cell_fwd(gr[r], gz[r], gn[r], acc_r[r] + br, acc_z[r] + bz, ghn, hp[r]);
+        if (row < R) {
+            const long long e = (long long)row * H + j;
+            float* gp = gates + (long long)row * 3 * H + j;
+            hout[e] = c.h;
+            gp[0] = c.r;
+            gp[H] = c.z;
+            gp[2 * H] = c.n;
+            hn[e] = ghn;
+        }
+    }
+}
+
+}  // namespace
 
 namespace dtc {
 
@@ -18,6 +62,31 @@ inline DtcSegMat plain(const float* p, int64_t ld, int cols, int64_t rows) {
     m.idx = nullptr;
     m.seg[0] = DtcSeg{const_cast<float*>(p), ld, 0, cols, 0, 0, rows};
     return m;
+}
+
+// The workgroup -> tile map of the per-step GRU kernels (gru_s3_kernel, gru_h2i_kernel) and the grid that goes with it.
+// XCD x (= blockIdx.x & 7: workgroups go round-robin over the XCDs) owns a fixed set of (column tile, chunk) pairs and runs them for ALL
+// row tiles: its slice of the W_hh image (1/8 of 4.7 MB at H = 512) stays in its 4 MiB L2 over the time steps of a pass, and what it
+// fetches from the Infinity Cache per step is the row operand.  With the row-tile map of the general GEMM kernels every XCD walks the
+// WHOLE image once per step -- more than its L2 holds -- and a time step's time follows the bytes that miss: two recurrences in one
+// launch took 1.6 x the time of one (tools/gru_pair_probe.py).
+struct GruXcdTile {
+    int tr, tc, chunk;          // row tile, column tile, chunk of the reduction (0 .. nparts - 1)
+    bool valid;                 // false: a padding workgroup
+};
+__device__ __forceinline__ GruXcdTile gru_xcd_tile(int b, int row_tiles, int col_tiles, int nparts) {
+    const int combos = col_tiles * nparts, per_xcd = (combos + 7) >> 3;
+    const int xcd = b & 7, j = b >> 3, cl = j / row_tiles;
+    const int combo = xcd * per_xcd + cl;
+    GruXcdTile t;
+    t.tr = j - cl * row_tiles;
+    t.chunk = combo / col_tiles;
+    t.tc = combo - t.chunk * col_tiles;
+    t.valid = cl < per_xcd && combo < combos;
+    return t;
+}
+inline unsigned gru_xcd_grid(int row_tiles, int col_tiles, int nparts) {
+    return (unsigned)(8 * ceil_div((int64_t)col_tiles * nparts, 8) * row_tiles);
 }
 
 // One time step of `count` (1 .. DTC_GRU_MULTI_MAX) recurrences of one shape on the split-precision path as ONE launch (gru_s3.hip);

@@ -1,8 +1,8 @@
 // GRU recurrence on the split-precision path (gfx950): the two per-time-step products of torch.nn.GRU's BPTT
 // (rsl_rl/rsl_rl/modules/actor_critic_recurrent.py:92-116 under ppo.py:265-335) with every fp32 operand as three bf16 terms and six
 // v_mfma_f32_32x32x16_bf16 passes per product (csrc/gemm_s3.hip explains the arithmetic and its accuracy):
-//   forward  : gh = h_{t-1} W_hh^T for the three gates of 32 hidden units + the gate math in the epilogue (the split twin of
-//              gru_step_fwd_kernel in gemm.hip) -- block tile 128 rows x (3 gates x 32 units), wave = 32 rows x 96 columns;
+//   forward  : gh = h_{t-1} W_hh^T for the three gates of 32 hidden units + the gate math in the epilogue (gru_epilogue_32x32 of
+//              gru_internal.hpp, shared with gru_step_fwd_kernel) -- block tile 128 rows x (3 gates x 32 units), wave = 32 rows x 96 columns;
 //   backward : the chunks of dh_{t-1} += dgh_t W_hh (the split twin of dtc_linear_dgrad_split) -- block tile 128 x 128, 2 x 2 waves.
 // One time step has R ~ 1500 rows: 12 row tiles, 150-300 workgroups, ONE workgroup per CU and one wave per SIMD -- nothing hides a
 // load behind another wave, and the general kernels of gemm_s3.hip (loads one stage ahead, built for three workgroups per CU) spend
@@ -12,6 +12,7 @@
 //   * the row operand (h_{t-1} resp. dgh_t, L2-resident: the previous kernel wrote it) is loaded TWO stages ahead into two register
 //     sets, converted one stage ahead (between the MFMAs of the stage in flight) -- registers are free at one wave per SIMD;
 //   * the K loop is unrolled by two, so stage buffers and register sets have constant indices.
+// Workgroup -> tile map: a column tile (and chunk) per XCD for all row tiles (gru_xcd_tile, gru_internal.hpp).
 #include <type_traits>
 
 #include "gru_internal.hpp"
@@ -50,8 +51,7 @@ struct GruS3Args {
     // backward epilogue: chunk c -> part + c * part_stride, [R, H]
     float* part;
     long long part_stride;
-    int colmap;                 // workgroup -> tile map by COLUMN tile (and chunk) per XCD: see gru_map
-    int nparts;
+    int nparts;                 // chunks of the reduction side by side (forward: 1)
 };
 
 // forward image: tile tc = units [32 tc, 32 tc + 32), row n of the tile = gate n / 32 of unit 32 tc + n % 32, reduction = hidden
@@ -95,23 +95,10 @@ __global__ __launch_bounds__(256, 2) void gru_s3_kernel(const GruS3Args a0, cons
     __shared__ __attribute__((aligned(16))) u32x2 Bs2[3][128 * 4];
     __shared__ __attribute__((aligned(16))) u32x2 Bs3[3][128 * 4];
 #define GBS(b) ((b) == 0 ? Bs0 : (b) == 1 ? Bs1 : (b) == 2 ? Bs2 : Bs3)
-    int tr, tc, chunk = MODE == MODE_BWD ? blockIdx.y : 0;
-    const int col_tiles = MODE == MODE_FWD ? a.H / 32 : a.H / 128;
-    if (a.colmap) {
-        // XCD x (= blockIdx.x & 7: workgroups go round-robin over the XCDs) owns a fixed set of (column tile, chunk) pairs and runs them
-        // for ALL row tiles: its slice of the W_hh image (1/8 of 4.7 MB) stays in its 4 MiB L2 over the 24 time steps, and what it
-        // fetches from the Infinity Cache per step is the row operand.  With the row-tile map every XCD walks the WHOLE image once per
-        // step -- more than its L2 holds -- and a time step's time follows the bytes that miss: two recurrences in one launch took 1.6 x
-        // the time of one (tools/gru_pair_probe.py).
-        const int row_tiles = (a.R + BM - 1) / BM, combos = col_tiles * a.nparts, per_xcd = (combos + 7) >> 3;
-        const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3, cl = j / row_tiles;
-        tr = j - cl * row_tiles;
-        const int combo = xcd * per_xcd + cl;
-        if (combo >= combos) return;
-        chunk = combo / col_tiles;
-        tc = combo - chunk * col_tiles;
-    } else if (!map_tile(blockIdx.x, (a.R + BM - 1) / BM, col_tiles, tr, tc)) return;
-    const int m0 = tr * BM;
+    const dtc::GruXcdTile tile = dtc::gru_xcd_tile(blockIdx.x, (a.R + BM - 1) / BM, MODE == MODE_FWD ? a.H / 32 : a.H / 128, a.nparts);
+    if (!tile.valid) return;
+    const int tc = tile.tc, chunk = tile.chunk;
+    const int m0 = tile.tr * BM;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     const int wm_off = (wave / G::WN) * (32 * TM), wn_off = (wave % G::WN) * (32 * TN);
@@ -264,40 +251,8 @@ __global__ __launch_bounds__(256, 2) void gru_s3_kernel(const GruS3Args a0, cons
     asm volatile("" ::: "memory");                   // and registers are given back
 
     if constexpr (MODE == MODE_FWD) {
-        // gate math of torch.nn.GRU (gru_step_fwd_kernel): r = sigmoid(gi_r + gh_r), z = sigmoid(gi_z + gh_z),
-        // n = tanh(gi_n + r * gh_n), h_t = (1 - z) * n + z * h_{t-1}; every lane holds the three pre-activations of its (row, unit) pairs
-        const int H = a.H, R = a.R;
-        const int j = tc * 32 + l31;
-        const float br = a.bhh[j], bz = a.bhh[H + j], bn = a.bhh[2 * H + j];
-        const rsrc_t gres = make_rsrc_bytes(a.gi, (long long)R * 3 * H * 4), hres = make_rsrc_bytes(a.A, (long long)R * a.lda * 4);
-        const int row0 = m0 + wm_off + 4 * half;
-        float gr[16], gz[16], gn[16], hp[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int ro = (r & 3) + 8 * (r >> 2);
-            const u32 go = (u32)((row0 + ro) * 3 * H + j) * 4u;
-            gr[r] = bload(gres, go, 0u);
-            gz[r] = bload(gres, go, (u32)H * 4u);
-            gn[r] = bload(gres, go, (u32)H * 8u);
-            hp[r] = bload(hres, (u32)((long long)(row0 + ro) * a.lda + j) * 4u, 0u);
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = row0 + (r & 3) + 8 * (r >> 2);
-            const float rg = dtc::sigmoid(gr[r] + (acc[0][0][r] + br));
-            const float zg = dtc::sigmoid(gz[r] + (acc[0][1][r] + bz));
-            const float ghn = acc[0][2][r] + bn;
-            const float ng = tanhf(gn[r] + rg * ghn);
-            if (row < R) {
-                const long long e = (long long)row * H + j;
-                float* gp = a.gates + (long long)row * 3 * H + j;
-                a.hout[e] = (1.0f - zg) * ng + zg * hp[r];
-                gp[0] = rg;
-                gp[H] = zg;
-                gp[2 * H] = ng;
-                a.hn[e] = ghn;
-            }
-        }
+        gru_epilogue_32x32(acc[0][0], acc[0][1], acc[0][2], m0 + wm_off + 4 * half, tc * 32 + l31, a.A, a.lda, a.bhh, a.gi, a.hout, a.gates,
+                           a.hn, a.R, a.H);
     } else {
         float* P = a.part + (long long)chunk * a.part_stride;
 #pragma unroll
@@ -344,11 +299,6 @@ extern "C" int dtc_gru_s3_image(const float* W_hh, void* img, int H, int backwar
 
 // dtc_gru_step_fwd on the split-precision path; `img` = dtc_gru_s3_image(W_hh, backward = 0)
 namespace {
-// DTC_GRU_XCD_COLS=0: the row-tile map of the general GEMM kernels (map_tile)
-int gru_colmap() {
-    constexpr int on = 1;
-    return on;
-}
 int fwd_args(GruS3Args& a, const dtc::GruStepFwd& it, int R, int H) {
     DTC_REQUIRE(shapes_ok(R, H), "bad shape R=%d H=%d (H must be a multiple of 128)", R, H);
     DTC_REQUIRE(it.hprev && it.img && it.b_hh && it.gi_t && it.hout && it.gates_t && it.hn_t, "null pointer");
@@ -365,7 +315,6 @@ int fwd_args(GruS3Args& a, const dtc::GruStepFwd& it, int R, int H) {
     a.hout = it.hout;
     a.gates = it.gates_t;
     a.hn = it.hn_t;
-    a.colmap = gru_colmap();
     a.nparts = 1;
     return DTC_OK;
 }
@@ -380,8 +329,7 @@ int dtc::gru_s3_step_fwd(const GruStepFwd* items, int count, int R, int H, void*
     }
     hipStream_t s = (hipStream_t)stream;
     dtc::ProfScope prof(dtc::prof_shape_name("gru_step_fwd", R, 3 * H, H), count * 2.0 * R * 3.0 * H * H, s);
-    const unsigned gx = a[0].colmap ? (unsigned)(8 * dtc::ceil_div(H / 32, 8) * dtc::ceil_div(R, BM)) : (unsigned)grid_for((int)dtc::ceil_div(R, BM), H / 32);
-    hipLaunchKernelGGL(gru_s3_kernel<MODE_FWD>, dim3(gx, 1, (unsigned)count), dim3(256), 0, s, a[0], a[count - 1]);
+    hipLaunchKernelGGL(gru_s3_kernel<MODE_FWD>, dim3(dtc::gru_xcd_grid((int)dtc::ceil_div(R, BM), H / 32, 1), 1, (unsigned)count), dim3(256), 0, s, a[0], a[count - 1]);
     return dtc::check_launch("gru_step_fwd_s3");
 }
 extern "C" int dtc_gru_step_fwd_s3(const float* hprev, const void* img, const float* b_hh, const float* gi_t, float* hout, float* gates_t,
@@ -407,7 +355,6 @@ int bwd_args(GruS3Args& a, const dtc::GruDgradParts& it, int64_t part_stride, in
     a.stages_tile = 3 * H / BK;
     a.part = it.part;
     a.part_stride = part_stride;
-    a.colmap = gru_colmap();
     a.nparts = nparts;
     return DTC_OK;
 }
@@ -422,9 +369,7 @@ int dtc::gru_s3_dgrad_parts(const GruDgradParts* items, int count, int64_t part_
     hipStream_t s = (hipStream_t)stream;
     dtc::ProfScope prof(dtc::prof_shape_name("linear_dgrad", R, 3 * H, H), count * 2.0 * R * 3.0 * H * H, s,
                         count * 4.0 * ((double)R * 3 * H + 3.0 * H * H + (double)nparts * R * H));
-    const dim3 grid = a[0].colmap ? dim3((unsigned)(8 * dtc::ceil_div((H / 128) * nparts, 8) * dtc::ceil_div(R, BM)), 1, (unsigned)count)
-                                  : dim3((unsigned)grid_for((int)dtc::ceil_div(R, BM), H / 128), (unsigned)nparts, (unsigned)count);
-    hipLaunchKernelGGL(gru_s3_kernel<MODE_BWD>, grid, dim3(256), 0, s, a[0], a[count - 1]);
+    hipLaunchKernelGGL(gru_s3_kernel<MODE_BWD>, dim3(dtc::gru_xcd_grid((int)dtc::ceil_div(R, BM), H / 128, nparts), 1, (unsigned)count), dim3(256), 0, s, a[0], a[count - 1]);
     return dtc::check_launch("gru_dgrad_parts_s3");
 }
 extern "C" int dtc_gru_dgrad_parts_s3(const float* dgh_t, const void* img, float* part, int64_t part_stride, int R, int H, int nparts,

@@ -16,7 +16,8 @@
 // of a row block then meet at a counter barrier (agent-scope atomics): the exchange rows leave by write-through (agent-scope) stores BEFORE
 // the arrival, the step's fp32 outputs and the next step's gi ride under the wait, and one wave per workgroup invalidates the CU's L1 (and
 // stale L2 lines) after the barrier -- the 16-32 workgroups of a row block that share an XCD then share its L2 for the re-reads.
-// Double-buffered exchange, one barrier per step, no grid-wide synchronisation, no kernel boundary.
+// Double-buffered exchange, one barrier per step, no grid-wide synchronisation, no kernel boundary.  The gate arithmetic is the cell of
+// rnn_cells.hpp, as in the per-step kernels.
 //
 // Residency.  The barrier needs every workgroup of a row block resident at once; a workgroup takes a CU (LDS).  dtc_gru_fwd (one
 // recurrence; the other one may run beside it on another stream) keeps to 4 row blocks x (H / 16) = 128 workgroups = half the CUs (R <= 1024);
@@ -27,6 +28,7 @@
 #include <stdlib.h>
 
 #include "common.hpp"
+#include "rnn_cells.hpp"
 
 namespace {
 
@@ -251,9 +253,8 @@ __global__ __launch_bounds__(MAXT) void gru_seq_fwd_kernel(const SeqFwdPair P) {
             }
         }
         if (tr) tr[1] = __builtin_amdgcn_s_memrealtime();
-        // ---- gate math of torch.nn.GRU (gru_step_fwd_kernel): r = sigmoid(gi_r + gh_r), z = sigmoid(gi_z + gh_z), n = tanh(gi_n + r gh_n),
-        // h_t = (1 - z) n + z h_{t-1}; gh = h_{t-1} W_hh^T + b_hh.  The next step's operand leaves FIRST, the workgroup arrives, and only
-        // then the step's fp32 outputs are stored and the next gi requested: both ride under the wait for the row block
+        // ---- gate math of torch.nn.GRU (rnn_cells.hpp); gh = h_{t-1} W_hh^T + b_hh.  The next step's operand leaves FIRST, the workgroup
+        // arrives, and only then the step's fp32 outputs are stored and the next gi requested: both ride under the wait for the row block
         f32x4 bias[3];
 #pragma unroll
         for (int g = 0; g < 3; ++g) bias[g] = *reinterpret_cast<const f32x4*>(&bl[g][4 * kg]);
@@ -263,11 +264,13 @@ __global__ __launch_bounds__(MAXT) void gru_seq_fwd_kernel(const SeqFwdPair P) {
             f32x4 hnew;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                rg[rt][i] = dtc::sigmoid(gin[rt][0][i] + (acc[rt][0][i] * back + bias[0][i]));
-                zg[rt][i] = dtc::sigmoid(gin[rt][1][i] + (acc[rt][1][i] * back + bias[1][i]));
                 ghn[rt][i] = acc[rt][2][i] * back + bias[2][i];
-                ng[rt][i] = tanhf(gin[rt][2][i] + rg[rt][i] * ghn[rt][i]);
-                hnew[i] = (1.0f - zg[rt][i]) * ng[rt][i] + zg[rt][i] * hp[rt][i];
+                const dtc::GruCell c = dtc::gru_cell_fwd(gin[rt][0][i], gin[rt][1][i], gin[rt][2][i], acc[rt][0][i] * back + bias[0][i],
+                                                         acc[rt][1][i] * back + bias[1][i], ghn[rt][i], hp[rt][i]);
+                rg[rt][i] = c.r;
+                zg[rt][i] = c.z;
+                ng[rt][i] = c.n;
+                hnew[i] = c.h;
             }
             if (rowc[rt] >= R) hnew = f32x4{0.f, 0.f, 0.f, 0.f};      // padding rows of the last row block stay zero
             hp[rt] = hnew;

@@ -51,6 +51,25 @@ __device__ __forceinline__ int hi_exp(u32 bits) {
     const int e = 141 - (int)(bits >> 23);
     return bits == 0u ? HI_EZERO : (e > HI_EMAX ? HI_EMAX : e);
 }
+// largest finite |x| of four values (bit pattern); the exponent of a row's block of 128 columns held four per lane by the 32 lanes
+// of half a wave
+__device__ __forceinline__ u32 hi_max4_bits(f32x4 v) {
+    u32 m = finite_bits(v[0]);
+#pragma unroll
+    for (int k = 1; k < 4; ++k) {
+        const u32 b = finite_bits(v[k]);
+        m = b > m ? b : m;
+    }
+    return m;
+}
+__device__ __forceinline__ int hi_half_wave_exp(u32 m) {
+#pragma unroll
+    for (int off = 16; off >= 1; off >>= 1) {
+        const u32 o = (u32)__shfl_xor((int)m, off, 64);
+        m = o > m ? o : m;
+    }
+    return hi_exp(m);
+}
 // 8 consecutive k of one row -> the 16-byte pieces of the two planes
 struct HiPiece {
     u32x4 p[2];
@@ -63,7 +82,8 @@ __device__ __forceinline__ HiPiece hi_split8(const f32x4 (&v)[2], int e) {
     return r;
 }
 
-// ---- narrow rows written straight by the kernel that produces them (latent / loss kernels; K <= 128: one exponent per row): element
+// ---- rows written straight by the kernel that produces them (latent / loss kernels: narrow rows, K <= 128, one exponent per row; the
+// GRU kernels of gru_h2i.hip: 4 or 8 columns per lane, one exponent per row and block): element
 // (row, col) of image(M, K) as two 2-byte stores, and the row's exponent.  Same values as h2i_pack_kernel writes for the same row
 // (x 2^e rounded to nearest-even fp16, remainder exact in fp32 then rounded); the buffer's padding columns stay as allocated (zero).
 __device__ __forceinline__ void hi_store_elem(void* img, int K, int row, int col, float x, int e) {
@@ -85,9 +105,17 @@ __device__ __forceinline__ void hi_store4(void* img, int K, int row, int col0, f
     *reinterpret_cast<u32x2*>(static_cast<char*>(img) + off) = s.p[0];
     *reinterpret_cast<u32x2*>(static_cast<char*>(img) + off + HI_PLANE) = s.p[1];
 }
-__device__ __forceinline__ void hi_store_row_exp(void* img, long long M, int K, int row, int e) {
-    int* exps = reinterpret_cast<int*>(static_cast<char*>(img) + hi_data_bytes(M, K));
-    exps[(long long)(row >> 7) * hi_kblocks(K) * 128 + (row & 127)] = e;
+// 8 consecutive columns (col0 % 8 == 0) of one row: one 16-byte piece per plane
+__device__ __forceinline__ void hi_store8(void* img, int K, int row, int col0, const HiPiece& pc) {
+    u32x4* chunk = static_cast<u32x4*>(img) + ((long long)(row >> 7) * hi_stages(K) + (col0 >> 4)) * (HI_CHUNK / 16);
+    chunk[rslot(row & 127, (col0 >> 3) & 1)] = pc.p[0];
+    chunk[256 + rslot(row & 127, (col0 >> 3) & 1)] = pc.p[1];
 }
+// exponent of (row, block kb of 128 columns) of image(M, K); K <= 128: the row's only one
+__device__ __forceinline__ void hi_store_exp(void* img, long long M, int K, int row, int kb, int e) {
+    int* exps = reinterpret_cast<int*>(static_cast<char*>(img) + hi_data_bytes(M, K));
+    exps[((long long)(row >> 7) * hi_kblocks(K) + kb) * 128 + (row & 127)] = e;
+}
+__device__ __forceinline__ void hi_store_row_exp(void* img, long long M, int K, int row, int e) { hi_store_exp(img, M, K, row, 0, e); }
 
 }  // namespace

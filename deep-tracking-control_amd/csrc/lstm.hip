@@ -4,6 +4,7 @@
 // class default, :93-97), gate order (i, f, g, o):
 //     a = gi_t + h_{t-1} W_hh^T + b_hh;  i, f, o = sigmoid(a_i, a_f, a_o), g = tanh(a_g)
 //     c_t = f * c_{t-1} + i * g;  h_t = o * tanh(c_t)
+// (stated once, with its derivatives, in rnn_cells.hpp: the gate kernels here and the fused step of gemm.hip call it.)
 // Same structure as gru.hip (all launches issued from this C++ loop, no Python between time steps):
 //   forward  t = 0..T-1 : gh = h_{t-1} W_hh^T + b_hh (dtc_linear_fwd, R rows) + lstm_gate_fwd_kernel (saves i, f, g, o);
 //                         dtc_lstm_fwd_fused: ONE launch per step (dtc_lstm_step_fwd in gemm.hip, the gate math in the GEMM's
@@ -17,6 +18,7 @@
 #include <stdlib.h>
 
 #include "gru_internal.hpp"
+#include "rnn_cells.hpp"
 
 namespace {
 
@@ -30,18 +32,14 @@ __global__ __launch_bounds__(256) void lstm_gate_fwd_kernel(const float* __restr
     const int j = (int)(e - row * H);
     const float* a = gi + row * 4 * H;
     const float* b = gh + row * 4 * H;
-    const float i = dtc::sigmoid(a[j] + b[j]);
-    const float f = dtc::sigmoid(a[H + j] + b[H + j]);
-    const float g = tanhf(a[2 * H + j] + b[2 * H + j]);
-    const float o = dtc::sigmoid(a[3 * H + j] + b[3 * H + j]);
-    const float c = f * cprev[e] + i * g;
-    cout[e] = c;
-    hout[e] = o * tanhf(c);
+    const dtc::LstmCell c = dtc::lstm_cell_fwd(a[j], a[H + j], a[2 * H + j], a[3 * H + j], b[j], b[H + j], b[2 * H + j], b[3 * H + j], cprev[e]);
+    cout[e] = c.c;
+    hout[e] = c.h;
     float* s = gates + row * 4 * H;
-    s[j] = i;
-    s[H + j] = f;
-    s[2 * H + j] = g;
-    s[3 * H + j] = o;
+    s[j] = c.i;
+    s[H + j] = c.f;
+    s[2 * H + j] = c.g;
+    s[3 * H + j] = c.o;
 }
 
 // dc (in/out): gradient flowing into c_t from step t+1 on entry (zero at t = T-1), into c_{t-1} on exit.  `part` holds
@@ -55,20 +53,18 @@ __global__ __launch_bounds__(256) void lstm_gate_bwd_kernel(const float* __restr
     const long long row = e / H;
     const int j = (int)(e - row * H);
     const float* s = gates + row * 4 * H;
-    const float i = s[j], f = s[H + j], g = s[2 * H + j], o = s[3 * H + j];
     float dh = dhs_t[e];
     if (part) {
         const long long rh = (long long)R * H;
         dh = (((dh + part[e]) + part[rh + e]) + part[2 * rh + e]) + part[3 * rh + e];
     }
-    const float tc = tanhf(cnow[e]);
-    const float dct = dc[e] + dh * o * (1.0f - tc * tc);
+    const dtc::LstmCellGrad c = dtc::lstm_cell_bwd(dh, dc[e], s[j], s[H + j], s[2 * H + j], s[3 * H + j], cprev[e], cnow[e]);
     float* d = dgi + row * 4 * H;
-    d[j] = (dct * g) * (i * (1.0f - i));
-    d[H + j] = (dct * cprev[e]) * (f * (1.0f - f));
-    d[2 * H + j] = (dct * i) * (1.0f - g * g);
-    d[3 * H + j] = (dh * tc) * (o * (1.0f - o));
-    dc[e] = dct * f;
+    d[j] = c.da_i;
+    d[H + j] = c.da_f;
+    d[2 * H + j] = c.da_g;
+    d[3 * H + j] = c.da_o;
+    dc[e] = c.dc_prev;
 }
 
 // dh0 <- the four chunks of the last W_hh product
