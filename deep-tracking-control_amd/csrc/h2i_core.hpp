@@ -33,6 +33,14 @@ constexpr int HI_PLANE = 4096, HI_CHUNK = 2 * HI_PLANE;   // bytes
 constexpr int HI_KB = 8;                                  // stages (16 columns each) per exponent block
 constexpr int HI_EZERO = 0x7fff;                          // "nothing here": an all-zero / all-non-finite row block
 constexpr int HI_EMAX = 100, HI_EMIN = -113;              // clamp: |x| < 2^-86 keeps fewer bits (absurdly small data), 2^127 still fits
+// Range of the accumulators.  Exponent sums of two operands span [-226, 200], far more than an fp32 accumulator's 2^128, so every
+// consumer must bound the step by which a block border RAISES its accumulators' scale (a falling scale only shrinks them):
+//   * weight gradient: bounded in the kernel (RESCALE_CAP = 72 above the slice's smallest scale, csrc/wgrad_h2i.hip);
+//   * forward / data gradient (rescale in gemm_h2i.hip: accumulator (m, n) x 2^(Dt[b][m] + dw[n]) at the 128-column borders): NOT
+//     bounded.  A block adds at most 128 k x 3 products of |hi hi'| <= 2^30, i.e. < 2^38.6, at its own scale e(b) = ea(m, b) + ew(n, b);
+//     at the scale of a later block c the accumulator is below MAX_TB x 2^38.6 x 2^max_b(e(c) - e(b)) = 2^(42.6 + step), so it cannot
+//     reach 2^128 while no later block's exponent sum exceeds an earlier one's by more than 85: a row whose 128-column blocks, times
+//     the weight row's, fall by more than 2^-85 (2.6e-26) from one block to a later one can overflow; anything less cannot.
 typedef __attribute__((address_space(3))) void lds_void;
 
 __host__ __device__ inline long long hi_stages(long long K) { return (K + 15) / 16; }

@@ -8,10 +8,22 @@
 // and the MFMA fragments (8 consecutive batch rows of ONE column per lane) come out of it by the hardware transpose read
 // ds_read_b64_tr_b16 (tools/probes/tr16_dma.hip; conflict free).  The images carry one exponent per batch row and 128-column block:
 // row m of dZ is stored times 2^eZ[m], row m of X times 2^eX[m].  Per 128-row block the workgroup forms T = min_m (eZ[m] + eX[m]) and the
-// fp16 factors f[m] = 2^(T - eZ[m] - eX[m]) <= 1; the X fragments are multiplied by f (4 v_pk_mul_f16 per fragment: exact for the rows
-// that carry the block's weight, rows far below it lose low-order bits of products that are far below the sum), the accumulators hold
-// 2^T x the true sums and are rescaled by ONE scalar at the borders of the 128-row blocks.  The bias gradient is dZ^T x fb on the matrix
-// pipe, fb[m] = 2^(Tz - eZ[m]).  Per wave and stage: 4 LDS-DMA pieces, 16 transpose reads, 2 table reads, 16 v_pk_mul_f16, 12 MFMAs.
+// fp16 factors f[m] = 2^(T - eZ[m] - eX[m]) <= 1; the X fragments are multiplied by f (4 v_pk_mul_f16 per fragment), the accumulators hold
+// 2^T x the true sums and are rescaled by ONE scalar at the borders of the 128-row blocks (by at most RESCALE_CAP above the slice's
+// smallest scale, see there).  The bias gradient is dZ^T x fb on the matrix pipe, fb[m] = 2^(Tz - eZ[m]).
+// What a row k = eZ[m] + eX[m] - T octaves below its block's top row keeps (oracle/wgrad_image_ref.py restates the scheme and derives
+// the figures, tests/test_hip_wgrad_image.py holds the kernel to them element by element, profiles/wgrad_image_errors.txt has a run):
+//   * k <= 16: all 22 bits of the (hi, lo) pair, relative to the ROW's largest element (what lo f loses below 2^-24 is below the
+//     pair's own last bit);
+//   * 17 <= k <= 24: at least 38 - k bits (21 .. 14): lo f, then hi f too, are fp16 subnormals, multiples of 2^-24 against a top of
+//     2^(14 - k) (measured on the CPU with numpy float16: 2^-21.4 at k = 17, 2^-18.4 at 20, 2^-14.5 at 24);
+//   * k >= 25: NOTHING -- (_Float16)2^-25 rounds to 0 (halfway to the smallest subnormal, ties to even), the row is multiplied by 0
+//     and the clamp at 2^-30 below is never reached as a value.  The bias factor fb sees k = eZ[m] - Tz alone.
+// Per ELEMENT of dW that is the error of an fp32 product only where the feature is dense: a feature (row of dW, or input column)
+// whose non-zero entries all sit in rows of tier k gets those bits and no more, and one that lives only in rows with k >= 25
+// gets a gradient of exactly 0 -- a ReLU unit that fires only on samples whose gradient rows are 2^-25 below their block's largest.
+// This is the price of one fp16 multiply per fragment; a wider range for f is a performance trade left open.
+// Per wave and stage: 4 LDS-DMA pieces, 16 transpose reads, 2 table reads, 16 v_pk_mul_f16, 12 MFMAs.
 // The stage loop is unrolled over three 128-row blocks (24 stages: the period of (position in the block, stage buffer)).
 // Partial slabs [batch slice][tile][128][128]; wgrad_h2i_reduce_kernel sums the slices in a fixed order.
 #include "h2i_core.hpp"
@@ -20,6 +32,23 @@ namespace {
 
 constexpr int TILE = 128;
 constexpr int MAX_JOBS_H = 12;
+// How far a block may raise the accumulators' scale above the smallest scale a block of the same batch slice has had.  A row of block
+// b adds at most three products |hi hi'| <= 2^30 f, f <= 1, to accumulators held at scale T_b; at a later scale T_c they are therefore
+// below rows x 2^30.01 x 2^(T_c - min_b T_b).  A slice holds at most 2^22 rows: an image is below 2 GiB and a row takes at least 64
+// bytes, so M < 2^25, and a launch has at least 8 slices (rows_per_split).  With T_c - min_b T_b <= 72 the accumulators stay below
+// 2^(22 + 30.01 + 72) < 2^125: finite operands cannot push them to inf at a border.  (The bias accumulators hold |a| 2^FB_UP fb <= 2^30.01
+// per row: the same bound.)  Ordinary data never comes near the cap -- 72 octaves between the top rows of
+// two 128-row blocks of one slice -- so its bits do not depend on it; a block beyond it gets the rest of its step as a smaller f / fb,
+// i.e. it is attenuated like rows far below a block's top, or dropped (oracle/wgrad_image_ref.py, rescale = "bounded").
+constexpr int RESCALE_CAP = 72;
+// The bias factors are stored times 2^FB_UP.  v_mfma_f32_32x32x16_f16 does not keep the bits of a product below about 2^-24: with
+// fb = 2^-k itself, a feature whose bias gradient comes from rows k octaves below the top came out 2^(k - 40) wrong relative to its
+// own sum of magnitudes (measured: 9e-7 at k = 20, 1.3e-5 at k = 24; nothing at k <= 14), although a power-of-two factor promises an
+// exact sum.  With 2^15 fb (the largest power of two fp16 holds) the last bit of a 22-bit (hi, lo) pair times fb sits at 2^-16 for
+// k = 24, and the products stay below 2^30.01, the bound the cap above was derived for.  (The dW products have the same floor, 25 and
+// more octaves below the first bit of hi f: nothing of the bits the factors keep.)
+constexpr int FB_UP = 15;
+constexpr int T_NONE = 0x3fffffff;           // "no block with content yet" (T_NONE + RESCALE_CAP still fits an int)
 typedef __fp16 h16x4 __attribute__((ext_vector_type(4)));
 typedef __fp16 h16x8 __attribute__((ext_vector_type(8)));
 
@@ -98,6 +127,7 @@ __global__ __launch_bounds__(256, 3) void wgrad_h2i_group_kernel(const HGroup G)
     // block before it: (1) request the two exponents, (2) minima over the block -> Tred (per wave), (3) after a barrier: T, Tz and the
     // factors -> Ft / Fb / Tt of the table the next block reads
     int ez_n = HI_EZERO, ex_n = HI_EZERO;
+    int t_lo = T_NONE, tz_lo = T_NONE;      // smallest T / Tz of the slice's blocks with content so far (threads < 128, all the same)
     auto table_request = [&](int mb) {
         if (tid < 128) {
             const int mt = mb >> 7;
@@ -124,12 +154,18 @@ __global__ __launch_bounds__(256, 3) void wgrad_h2i_group_kernel(const HGroup G)
     auto table_finish = [&](int which, int t_prev, int tz_prev) {
         if (tid < 128) {
             int T = min(Tred[0][0], Tred[1][0]), Tz = min(Tred[0][1], Tred[1][1]);
-            T = T == 0x7fffffff ? t_prev : T;           // a block without content keeps the scale (nothing to add, nothing to rescale)
-            Tz = Tz == 0x7fffffff ? tz_prev : Tz;
+            // a block without content keeps the scale (nothing to add, nothing to rescale); one with content raises it to at most
+            // RESCALE_CAP above the slice's smallest so far and takes the rest into its factors
+            const bool has = T != 0x7fffffff, hasz = Tz != 0x7fffffff;
+            T = has ? min(T, t_lo + RESCALE_CAP) : t_prev;
+            Tz = hasz ? min(Tz, tz_lo + RESCALE_CAP) : tz_prev;
+            t_lo = has ? min(t_lo, T) : t_lo;
+            tz_lo = hasz ? min(tz_lo, Tz) : tz_lo;
             const bool live = ez_n != HI_EZERO && ex_n != HI_EZERO;
             const int d = live ? T - (ez_n + ex_n) : 0, dz = ez_n != HI_EZERO ? Tz - ez_n : 0;
             Ft[which][tid] = (_Float16)__builtin_ldexpf(1.0f, d < -30 ? -30 : d);
-            Fb[which][tid] = (_Float16)__builtin_ldexpf(1.0f, dz < -30 ? -30 : dz);
+            // fb carries 2^FB_UP (taken out again in the epilogue) and is 0 from 25 octaves below the top, as f is: see FB_UP
+            Fb[which][tid] = dz < -24 ? (_Float16)0.0f : (_Float16)__builtin_ldexpf(1.0f, dz + FB_UP);
             if (tid == 0) {
                 Tt[which][0] = T;
                 Tt[which][1] = Tz;
@@ -323,7 +359,7 @@ __global__ __launch_bounds__(256, 3) void wgrad_h2i_group_kernel(const HGroup G)
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) bp[(2 * wr + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * half] = __builtin_ldexpf(accb[i][r], -tz_cur);
+            for (int r = 0; r < 16; ++r) bp[(2 * wr + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * half] = __builtin_ldexpf(accb[i][r], -tz_cur - FB_UP);
     }
 #undef AS
 #undef BS

@@ -15,6 +15,9 @@ Pinning status:
     step around them is the ppo.py:288-338 loss block already pinned by `ppo.npz`.
   * Loss, action and bootstrap kernels one operation at a time: `losses_ref.py`, float64 from the formulas with autograd
     gradients; its own checks (torch.distributions, hand-computed batches) are in `tests/test_losses_oracle.py`.
+  * Image weight gradient (`csrc/wgrad_h2i.hip`): `wgrad_image_ref.py` restates the kernel's scaling scheme -- not a reference
+    algorithm -- in numpy with float64 accumulation and bounds it against float64 truth; its own checks are in
+    `tests/test_wgrad_image_oracle.py`.
   * Foothold scorer: pinned against `LeggedRobotDTC.post_physics_step` run on a mock env,
     EXCEPT for the three Isaac Gym quaternion helpers (`isaacgym.torch_utils`, un-vendored,
     version unpinned by the reference) whose published formulas are restated -> that
