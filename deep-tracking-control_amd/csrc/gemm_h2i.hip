@@ -380,7 +380,11 @@ struct TileArgs {
 typedef const AS4 TileArgs CTileArgs;
 // TM = 2: 128-row tiles (2 x 2 waves of 64 x 64); TM = 1: 64-row tiles (2 x 2 waves of 32 x 64: half a chunk of the row operand per
 // stage) for the launches whose 128-row tiles would leave CUs without a workgroup (the 128-column layers: 192 tiles on 256 CUs).
-template <int EPI, int TM, bool WIDE_T = false>
+// PASSES = 3: every product is lo hi' + hi lo' + hi hi' (the default arithmetic, 22-bit operands); PASSES = 1 (opt-in, dtc_set_h2i_passes):
+// hi hi' alone -- plane 0 of both operands is all a stage fetches and reads (2 LDS-DMA pieces per wave and stage instead of 4, half the
+// fragment reads, TM x TN MFMAs), 11-bit operands relative to their row block's largest element, fp32 accumulation as before.  Stage
+// buffers, exponents, border rescales, epilogue and the image of the result are the same code for both.
+template <int EPI, int TM, bool WIDE_T = false, int PASSES = 3>
 __device__ __forceinline__ void h2i_tile(CTileArgs& L, const MseEpiH& mse, const int tr, const int tc, const int slot,
                                          unsigned long long* __restrict__ trace) {
     const auto& A = L.A;
@@ -395,6 +399,8 @@ __device__ __forceinline__ void h2i_tile(CTileArgs& L, const MseEpiH& mse, const
     unsigned short* __restrict__ wmask = L.wmask;
     const auto& dg = L.dg;
     constexpr int BN = 128, WN = 2, TN = 2, BMT = 64 * TM;
+    static_assert(PASSES == 3 || (PASSES == 1 && !WIDE_T), "three passes, or one pass on the 32-bit addressed forms");
+    constexpr int NP = PASSES == 3 ? 2 : 1;             // planes of an operand a stage fetches and reads
 #define XS(b) ((b) == 0 ? Xs0 : (b) == 1 ? Xs1 : Xs2)
 #define WS(b) ((b) == 0 ? Ws0 : (b) == 1 ? Ws1 : Ws2)
     const int tid = threadIdx.x, lane = tid & 63;
@@ -438,7 +444,7 @@ __device__ __forceinline__ void h2i_tile(CTileArgs& L, const MseEpiH& mse, const
         const u32 voff = lane_off | (left > 0 ? 0u : INVALID);
 #if !(DTC_H2I_ABL & 8)
 #pragma unroll
-        for (int p = 0; p < 2; ++p) {
+        for (int p = 0; p < NP; ++p) {
             __builtin_amdgcn_raw_ptr_buffer_load_lds(xres, (lds_void*)&XS(nbuf)[p][wave * 128], 16, voff | xlane, xchunk + p * HI_PLANE, 0, 0);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(wres, (lds_void*)&WS(nbuf)[p][wpiece * 128], 16, wlane_off | (left > 0 ? 0u : INVALID),
                                                      wchunk + p * HI_PLANE, 0, 0);
@@ -520,7 +526,7 @@ __device__ __forceinline__ void h2i_tile(CTileArgs& L, const MseEpiH& mse, const
     auto read_self = [&](auto bc) {
         constexpr int buf = decltype(bc)::value;
 #pragma unroll
-        for (int p = 0; p < 2; ++p) {
+        for (int p = 0; p < NP; ++p) {
 #if DTC_H2I_ABL & 4
             sa[p] = u32x4{(u32)lane, 0x3c003c00u, (u32)p, 0u};
             sb[p] = u32x4{0x3c003c00u, (u32)lane, 0u, (u32)p};
@@ -570,7 +576,30 @@ __device__ __forceinline__ void h2i_tile(CTileArgs& L, const MseEpiH& mse, const
 #else
         using P = Prec<true>;
 #endif
-        if constexpr (SELF) {
+        if constexpr (PASSES == 1) {
+            // one pass: the hi planes alone, one MFMA per 32 x 32 tile; SELF: tile (0, 0) from the fragments read above the barrier
+            if constexpr (SELF) {
+                a[0][0] = sa[0]; b[0][0] = sb[0];
+                rda(1, 0); rdb(1, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                acc[0][0] = P::mfma(a[0][0], b[0][0], acc[0][0]);
+                __builtin_amdgcn_sched_barrier(0);
+                acc[1][0] = P::mfma(a[1][0], b[0][0], acc[1][0]);
+                acc[0][1] = P::mfma(a[0][0], b[1][0], acc[0][1]);
+                acc[1][1] = P::mfma(a[1][0], b[1][0], acc[1][1]);
+            } else {
+                rda(0, 0); rdb(0, 0);
+                if constexpr (TM == 2) rda(1, 0);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int i = 0; i < TM; ++i) acc[i][0] = P::mfma(a[i][0], b[0][0], acc[i][0]);
+                __builtin_amdgcn_sched_barrier(0);
+                rdb(1, 0);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int i = 0; i < TM; ++i) acc[i][1] = P::mfma(a[i][0], b[1][0], acc[i][1]);
+            }
+        } else if constexpr (SELF) {
             // tile (0, 0) from the fragments read above the barrier; the other three tiles' fragments are requested now and arrive
             // under its MFMAs.  Per tile the order of the terms is the plain path's (smallest first: lo hi', hi lo', hi hi'), so the
             // results are bit-identical
@@ -621,8 +650,9 @@ __device__ __forceinline__ void h2i_tile(CTileArgs& L, const MseEpiH& mse, const
             cst = 0;
         }
         // stage s + 1 has landed (this wave's four newest transfers -- stage s + 2 -- may still be in flight: vmcnt(4), the other counters
-        // untouched); then every wave's share has.  A raw barrier: __syncthreads() would wait for ALL transfers
-        __builtin_amdgcn_s_waitcnt(0x0F70 | 4);
+        // untouched; one pass: a stage is TWO transfers per wave, vmcnt(2) -- vmcnt(4) would let the stage that runs next still be in
+        // flight); then every wave's share has.  A raw barrier: __syncthreads() would wait for ALL transfers
+        __builtin_amdgcn_s_waitcnt(0x0F70 | (2 * NP));
         if constexpr (SELF) {                             // this wave's own pieces of stage s + 1 are in LDS: its tile (0, 0) fragments
             read_self(std::integral_constant<int, (buf + 1) % 3>{});
             __builtin_amdgcn_sched_barrier(0);
@@ -947,6 +977,20 @@ __global__ __launch_bounds__(256, 3) void linear_h2i_kernel(const TileArgs L_, c
     h2i_tile<EPI, TM>(L, mse, tr, tc, (int)blockIdx.x, trace);
 #endif
 }
+// ... and its one-pass twin (dtc_set_h2i_passes(1)): the same launch geometry and arguments, h2i_tile with PASSES = 1
+template <int EPI, int TM>
+__global__ __launch_bounds__(256, 3) void linear_h2i_onepass_kernel(const TileArgs L_, const MseEpiH mse, unsigned long long* __restrict__ trace) {
+#ifdef __HIP_DEVICE_COMPILE__
+    CTileArgs& L = *(CTileArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+    (void)L_;
+    int tr, tc;
+    if (!map_tile(blockIdx.x, (L.M + 64 * TM - 1) / (64 * TM), (L.N + 127) / 128, tr, tc)) {
+        if (EPI == EPI_MSE && threadIdx.x == 0) mse.part[blockIdx.x] = 0.0;
+        return;
+    }
+    h2i_tile<EPI, TM, false, 1>(L, mse, tr, tc, (int)blockIdx.x, trace);
+#endif
+}
 
 // the loss layer against a target of 2 GiB or more (dtc_linear_fwd_mse_h2i picks it on the host; smaller targets launch
 // linear_h2i_kernel<EPI_MSE, 2> as before)
@@ -975,13 +1019,11 @@ struct ChainArgs {
 };
 // (128-row tiles -- M > 32768 rows only -- at two workgroups per CU: the column-tile loops around three inlined tile bodies do not fit 168
 // registers; the 64-row form every size of this project takes keeps three)
-template <int EPI, int TM>
-__global__ __launch_bounds__(256, TM == 2 ? 2 : 3) void chain_h2i_kernel(const ChainArgs C_, unsigned long long* __restrict__ trace) {
 #ifdef __HIP_DEVICE_COMPILE__
+template <int EPI, int TM, int PASSES>
+__device__ __forceinline__ void chain_h2i_body() {
     typedef const AS4 ChainArgs CChainArgs;
     CChainArgs& C = *(CChainArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-    (void)C_;
-    (void)trace;
     int tr, tc;
     if (!map_tile(blockIdx.x, (C.layer[0].M + 64 * TM - 1) / (64 * TM), 1, tr, tc)) return;
     const MseEpiH none{};
@@ -989,26 +1031,43 @@ __global__ __launch_bounds__(256, TM == 2 ? 2 : 3) void chain_h2i_kernel(const C
     // the critic's tails 512 -> 256 -> 128 (actor_critic_decoder.py:323-349) forward, 128 -> 256 -> 512 backward
     for (int tc0 = 0; tc0 < (C.layer[0].N + 127) / 128; ++tc0) {
             if (tc0 > 0) __syncthreads();        // (the previous tile's epilogue still uses the stage buffers as its patches)
-            h2i_tile<EPI, TM>(C.layer[0], none, tr, tc0, (int)blockIdx.x, nullptr);
+            h2i_tile<EPI, TM, false, PASSES>(C.layer[0], none, tr, tc0, (int)blockIdx.x, nullptr);
         }
     if (C.count > 1) {
         __syncthreads();                    // (workgroup-scope release / acquire: this tile's image rows and exponents are visible to all its waves)
         for (int tc1 = 0; tc1 < (C.layer[1].N + 127) / 128; ++tc1) {
             if (tc1 > 0) __syncthreads();        // (the previous tile's epilogue still uses the stage buffers as its patches)
-            h2i_tile<EPI, TM>(C.layer[1], none, tr, tc1, (int)blockIdx.x, nullptr);
+            h2i_tile<EPI, TM, false, PASSES>(C.layer[1], none, tr, tc1, (int)blockIdx.x, nullptr);
         }
     }
     if (C.count > 2) {
         __syncthreads();
         for (int tc2 = 0; tc2 < (C.layer[2].N + 127) / 128; ++tc2) {
             if (tc2 > 0) __syncthreads();        // (the previous tile's epilogue still uses the stage buffers as its patches)
-            h2i_tile<EPI, TM>(C.layer[2], none, tr, tc2, (int)blockIdx.x, nullptr);
+            h2i_tile<EPI, TM, false, PASSES>(C.layer[2], none, tr, tc2, (int)blockIdx.x, nullptr);
         }
     }
+}
+#endif
+template <int EPI, int TM>
+__global__ __launch_bounds__(256, TM == 2 ? 2 : 3) void chain_h2i_kernel(const ChainArgs C_, unsigned long long* __restrict__ trace) {
+#ifdef __HIP_DEVICE_COMPILE__
+    (void)C_;
+    (void)trace;
+    chain_h2i_body<EPI, TM, 3>();
+#endif
+}
+template <int EPI, int TM>
+__global__ __launch_bounds__(256, TM == 2 ? 2 : 3) void chain_h2i_onepass_kernel(const ChainArgs C_, unsigned long long* __restrict__ trace) {
+#ifdef __HIP_DEVICE_COMPILE__
+    (void)C_;
+    (void)trace;
+    chain_h2i_body<EPI, TM, 1>();
 #endif
 }
 
 unsigned long long* g_trace = nullptr;      // debug: dtc_h2i_trace
+int g_h2i_passes = 3;                       // dtc_set_h2i_passes: 3 (lo hi' + hi lo' + hi hi') or 1 (hi hi' alone)
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
 int check_img(const void* img, const char* what) {
@@ -1068,6 +1127,18 @@ WimgView wimg_view(const void* wimg, int nr, const HOperand& A) {
 // debug: the image-operand GEMM launches that follow write per-workgroup records {start, K loop done, end (100 MHz ticks), HW_ID} to
 // `buf` (4 x grid uint64, device; NULL: off)
 extern "C" void dtc_h2i_trace(void* buf) { g_trace = (unsigned long long*)buf; }
+
+// MFMA passes per product of the image-operand GEMM family (forward, data gradient, fused MSE layer, chains here; weight gradients in
+// wgrad_h2i.hip): 3 = the default two-term arithmetic, 1 = the hi planes alone (opt-in; 11-bit operands, fp32 accumulation).  Any other
+// value is refused (dtc_last_error) and leaves the setting as it was.
+extern "C" void dtc_set_h2i_passes(int passes) {
+    if (passes != 3 && passes != 1) {
+        dtc::set_error("dtc_set_h2i_passes(%d): 3 (default) or 1", passes);
+        return;
+    }
+    g_h2i_passes = passes;
+}
+extern "C" int dtc_get_h2i_passes(void) { return g_h2i_passes; }
 
 extern "C" int64_t dtc_h2i_bytes(int M, int K) {
     if (M <= 0 || K <= 0) return 0;
@@ -1312,12 +1383,16 @@ extern "C" int dtc_linear_fwd_h2i(const DtcH2iOperand* X, const void* wimg, cons
     if (rc != DTC_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     dtc::ProfScope prof(dtc::prof_shape_name("linear_fwd", M, N, L.K), L.flop, s, L.bytes);
-    if (rows64(M, N))
-        hipLaunchKernelGGL((linear_h2i_kernel<EPI_FWD, 1>), dim3(grid_for((int)dtc::ceil_div(M, 64), (int)dtc::ceil_div(N, 128))), dim3(256), 0, s, L.t,
-                           MseEpiH{}, g_trace);
-    else
-        hipLaunchKernelGGL((linear_h2i_kernel<EPI_FWD, 2>), dim3(grid_for((int)dtc::ceil_div(M, BM), (int)dtc::ceil_div(N, 128))), dim3(256), 0, s, L.t,
-                           MseEpiH{}, g_trace);
+    const bool one = g_h2i_passes == 1;
+    if (rows64(M, N)) {
+        const dim3 grid(grid_for((int)dtc::ceil_div(M, 64), (int)dtc::ceil_div(N, 128)));
+        if (one) hipLaunchKernelGGL((linear_h2i_onepass_kernel<EPI_FWD, 1>), grid, dim3(256), 0, s, L.t, MseEpiH{}, g_trace);
+        else hipLaunchKernelGGL((linear_h2i_kernel<EPI_FWD, 1>), grid, dim3(256), 0, s, L.t, MseEpiH{}, g_trace);
+    } else {
+        const dim3 grid(grid_for((int)dtc::ceil_div(M, BM), (int)dtc::ceil_div(N, 128)));
+        if (one) hipLaunchKernelGGL((linear_h2i_onepass_kernel<EPI_FWD, 2>), grid, dim3(256), 0, s, L.t, MseEpiH{}, g_trace);
+        else hipLaunchKernelGGL((linear_h2i_kernel<EPI_FWD, 2>), grid, dim3(256), 0, s, L.t, MseEpiH{}, g_trace);
+    }
     return dtc::check_launch("linear_fwd_h2i");
 }
 
@@ -1335,6 +1410,9 @@ extern "C" int dtc_linear_fwd_mse_h2i(const DtcH2iOperand* X, const void* wimg, 
     DTC_REQUIRE(tcol0 >= 0 && tcol0 + N <= ldt && target_rows > 0, "target columns [%d, %d) outside its %lld-wide rows", tcol0, tcol0 + N, (long long)ldt);
     DTC_REQUIRE(target_rows < (1ll << 31) && ldt < (1ll << 31), "target rows / row stride beyond 2^31");
     const bool wide = target_rows * ldt > MAX_ELEMS;     // a target of 2 GiB or more: the epilogue with 64-bit lane addresses
+    const bool one = g_h2i_passes == 1;
+    DTC_REQUIRE(!(wide && one), "one-pass mode (dtc_set_h2i_passes(1)) has no form for a target of 2 GiB or more (%lld x %lld floats): "
+                "three passes, or a smaller rollout", (long long)target_rows, (long long)ldt);
     LayerInfo L;
     int rc = fwd_args(X, wimg, b, dY, lddy, dYimg, nullptr, M, N, (int)DTC_ACT_NONE, L);
     if (rc != DTC_OK) return rc;
@@ -1344,6 +1422,9 @@ extern "C" int dtc_linear_fwd_mse_h2i(const DtcH2iOperand* X, const void* wimg, 
     if (wide)
         hipLaunchKernelGGL(linear_h2i_mse_wide_kernel, dim3(grid_for((int)dtc::ceil_div(M, BM), (int)dtc::ceil_div(N, 128))), dim3(256), 0, s, L.t, mse,
                            g_trace);
+    else if (one)
+        hipLaunchKernelGGL((linear_h2i_onepass_kernel<EPI_MSE, 2>), dim3(grid_for((int)dtc::ceil_div(M, BM), (int)dtc::ceil_div(N, 128))), dim3(256), 0, s,
+                           L.t, mse, g_trace);
     else
         hipLaunchKernelGGL((linear_h2i_kernel<EPI_MSE, 2>), dim3(grid_for((int)dtc::ceil_div(M, BM), (int)dtc::ceil_div(N, 128))), dim3(256), 0, s, L.t,
                            mse, g_trace);
@@ -1363,12 +1444,16 @@ extern "C" int dtc_linear_dgrad_h2i(const void* dZimg, int N, const void* wimgT,
     if (rc != DTC_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     dtc::ProfScope prof(dtc::prof_shape_name("linear_dgrad", M, N, Kwin), L.flop, s, L.bytes);
-    if (rows64(M, Kwin))
-        hipLaunchKernelGGL((linear_h2i_kernel<EPI_DGRAD, 1>), dim3(grid_for((int)dtc::ceil_div(M, 64), (int)dtc::ceil_div(Kwin, 128))), dim3(256), 0, s,
-                           L.t, MseEpiH{}, g_trace);
-    else
-        hipLaunchKernelGGL((linear_h2i_kernel<EPI_DGRAD, 2>), dim3(grid_for((int)dtc::ceil_div(M, BM), (int)dtc::ceil_div(Kwin, 128))), dim3(256), 0, s,
-                           L.t, MseEpiH{}, g_trace);
+    const bool one = g_h2i_passes == 1;
+    if (rows64(M, Kwin)) {
+        const dim3 grid(grid_for((int)dtc::ceil_div(M, 64), (int)dtc::ceil_div(Kwin, 128)));
+        if (one) hipLaunchKernelGGL((linear_h2i_onepass_kernel<EPI_DGRAD, 1>), grid, dim3(256), 0, s, L.t, MseEpiH{}, g_trace);
+        else hipLaunchKernelGGL((linear_h2i_kernel<EPI_DGRAD, 1>), grid, dim3(256), 0, s, L.t, MseEpiH{}, g_trace);
+    } else {
+        const dim3 grid(grid_for((int)dtc::ceil_div(M, BM), (int)dtc::ceil_div(Kwin, 128)));
+        if (one) hipLaunchKernelGGL((linear_h2i_onepass_kernel<EPI_DGRAD, 2>), grid, dim3(256), 0, s, L.t, MseEpiH{}, g_trace);
+        else hipLaunchKernelGGL((linear_h2i_kernel<EPI_DGRAD, 2>), grid, dim3(256), 0, s, L.t, MseEpiH{}, g_trace);
+    }
     return dtc::check_launch("linear_dgrad_h2i");
 }
 
@@ -1386,12 +1471,21 @@ int chain_launch(bool dgrad, const LayerInfo* L, int count, int M, hipStream_t s
     const bool r64 = rows64(M, 128);
     const int row_tiles = (int)dtc::ceil_div(M, r64 ? 64 : BM);
     dtc::ProfScope prof(dtc::prof_shape_name(dgrad ? "linear_dgrad_chain" : "linear_fwd_chain", M, count, L[0].K), flop, s, bytes);
-    if (dgrad) {
-        if (r64) hipLaunchKernelGGL((chain_h2i_kernel<EPI_DGRAD, 1>), dim3(grid_for(row_tiles, 1)), dim3(256), 0, s, C, g_trace);
-        else hipLaunchKernelGGL((chain_h2i_kernel<EPI_DGRAD, 2>), dim3(grid_for(row_tiles, 1)), dim3(256), 0, s, C, g_trace);
+    const dim3 grid(grid_for(row_tiles, 1));
+    if (g_h2i_passes == 1) {
+        if (dgrad) {
+            if (r64) hipLaunchKernelGGL((chain_h2i_onepass_kernel<EPI_DGRAD, 1>), grid, dim3(256), 0, s, C, g_trace);
+            else hipLaunchKernelGGL((chain_h2i_onepass_kernel<EPI_DGRAD, 2>), grid, dim3(256), 0, s, C, g_trace);
+        } else {
+            if (r64) hipLaunchKernelGGL((chain_h2i_onepass_kernel<EPI_FWD, 1>), grid, dim3(256), 0, s, C, g_trace);
+            else hipLaunchKernelGGL((chain_h2i_onepass_kernel<EPI_FWD, 2>), grid, dim3(256), 0, s, C, g_trace);
+        }
+    } else if (dgrad) {
+        if (r64) hipLaunchKernelGGL((chain_h2i_kernel<EPI_DGRAD, 1>), grid, dim3(256), 0, s, C, g_trace);
+        else hipLaunchKernelGGL((chain_h2i_kernel<EPI_DGRAD, 2>), grid, dim3(256), 0, s, C, g_trace);
     } else {
-        if (r64) hipLaunchKernelGGL((chain_h2i_kernel<EPI_FWD, 1>), dim3(grid_for(row_tiles, 1)), dim3(256), 0, s, C, g_trace);
-        else hipLaunchKernelGGL((chain_h2i_kernel<EPI_FWD, 2>), dim3(grid_for(row_tiles, 1)), dim3(256), 0, s, C, g_trace);
+        if (r64) hipLaunchKernelGGL((chain_h2i_kernel<EPI_FWD, 1>), grid, dim3(256), 0, s, C, g_trace);
+        else hipLaunchKernelGGL((chain_h2i_kernel<EPI_FWD, 2>), grid, dim3(256), 0, s, C, g_trace);
     }
     return dtc::check_launch(dgrad ? "linear_dgrad_chain_h2i" : "linear_fwd_chain_h2i");
 }

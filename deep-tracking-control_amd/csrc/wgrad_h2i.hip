@@ -71,7 +71,12 @@ struct HGroup {
     HJob job[MAX_JOBS_H];
 };
 
-__global__ __launch_bounds__(256, 3) void wgrad_h2i_group_kernel(const HGroup G) {
+// PASSES = 3: lo hi' + hi lo' + hi hi' per product (the default); PASSES = 1 (opt-in, dtc_set_h2i_passes): plane 0 of both operands alone
+// -- 2 LDS-DMA pieces, 8 transpose reads, 8 v_pk_mul_f16 and 4 dW MFMAs per wave and stage, the bias product on the hi plane.  Tables,
+// RESCALE_CAP, FB_UP, the slabs and the reduce kernel are the same for both.
+template <int PASSES>
+__device__ __forceinline__ void wgrad_h2i_group_body(const HGroup& G) {
+    constexpr int NP = PASSES == 3 ? 2 : 1;                           // planes of an operand a stage fetches and reads
     // separate objects per stage buffer: an LDS-DMA into one cannot alias the fragment reads of the other
     // (three stage buffers: the transfers run two stages ahead of the MFMAs, see linear_h2i_kernel)
     __shared__ __attribute__((aligned(16))) unsigned char A0[2][4096];
@@ -117,7 +122,7 @@ __global__ __launch_bounds__(256, 3) void wgrad_h2i_group_kernel(const HGroup G)
         const u32 ub = (u32)((mb >> 7) * J.st_k) * (u32)HI_CHUNK + (u32)(mb & 127) * 32u;
         const u32 dead = oob_mask(mb + mrow, m_end - 1);
 #pragma unroll
-        for (int p = 0; p < 2; ++p) {
+        for (int p = 0; p < NP; ++p) {
             __builtin_amdgcn_raw_ptr_buffer_load_lds(ares, (lds_void*)&AS(nbuf)[p][wave * 1024], 16, aoff | dead, ua + p * HI_PLANE, 0, 0);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(bres, (lds_void*)&BS(nbuf)[p][wave * 1024], 16, boff | dead, ub + p * HI_PLANE, 0, 0);
         }
@@ -220,7 +225,7 @@ __global__ __launch_bounds__(256, 3) void wgrad_h2i_group_kernel(const HGroup G)
     auto load_at = [&](auto nbc, u32 ua, u32 ub, u32 dead) {
         constexpr int nbuf = decltype(nbc)::value;
 #pragma unroll
-        for (int p = 0; p < 2; ++p) {
+        for (int p = 0; p < NP; ++p) {
             __builtin_amdgcn_raw_ptr_buffer_load_lds(ares, (lds_void*)&AS(nbuf)[p][wave * 1024], 16, aoff | dead, ua + p * HI_PLANE, 0, 0);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(bres, (lds_void*)&BS(nbuf)[p][wave * 1024], 16, boff | dead, ub + p * HI_PLANE, 0, 0);
         }
@@ -271,16 +276,23 @@ __global__ __launch_bounds__(256, 3) void wgrad_h2i_group_kernel(const HGroup G)
         __builtin_amdgcn_sched_barrier(0);
         f16x8 a[2][2], b[2][2];
 #pragma unroll
-        for (int p = 1; p >= 0; --p) {
+        for (int p = NP - 1; p >= 0; --p) {
             a[0][p] = rd(AS(buf)[p], a_base);
             b[0][p] = rd(BS(buf)[p], b_base);
             a[1][p] = rd(AS(buf)[p], a_base + 256);
         }
 #pragma unroll
-        for (int p = 0; p < 2; ++p) b[1][p] = rd(BS(buf)[p], b_base + 256);
+        for (int p = 0; p < NP; ++p) b[1][p] = rd(BS(buf)[p], b_base + 256);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int p = 0; p < 2; ++p) b[0][p] = b[0][p] * fv;
+        for (int p = 0; p < NP; ++p) b[0][p] = b[0][p] * fv;
+        if constexpr (PASSES == 1) {                         // hi hi' alone: four dW MFMAs
+#pragma unroll
+            for (int i = 0; i < 2; ++i) acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][0], b[0][0], acc[i][0], 0, 0, 0);
+            b[1][0] = b[1][0] * fv;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][0], b[1][0], acc[i][1], 0, 0, 0);
+        } else {
         // smallest terms first: lo hi', hi lo', hi hi'
 #pragma unroll
         for (int i = 0; i < 2; ++i) acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][1], b[0][0], acc[i][0], 0, 0, 0);
@@ -296,9 +308,10 @@ __global__ __launch_bounds__(256, 3) void wgrad_h2i_group_kernel(const HGroup G)
         for (int i = 0; i < 2; ++i) acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][0], b[1][1], acc[i][1], 0, 0, 0);
 #pragma unroll
         for (int i = 0; i < 2; ++i) acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][0], b[1][0], acc[i][1], 0, 0, 0);
+        }
         if (bias && wc == 0) {                               // wave-uniform: this tile's share of the column sums of dZ (the wc = 1 waves hold the same rows)
 #pragma unroll
-            for (int p = 1; p >= 0; --p)
+            for (int p = NP - 1; p >= 0; --p)
 #pragma unroll
                 for (int i = 0; i < 2; ++i) accb[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][p], fbv, accb[i], 0, 0, 0);
         }
@@ -306,7 +319,8 @@ __global__ __launch_bounds__(256, 3) void wgrad_h2i_group_kernel(const HGroup G)
         if constexpr (ph == 6) {
             if (B.more) table_minima();                       // the exponents requested at the stage's head have long arrived
         }
-        __builtin_amdgcn_s_waitcnt(0x0070 | 4);               // vmcnt(4), lgkmcnt(0), expcnt untouched
+        // this wave's newest stage (4 transfers; one pass: 2) may stay in flight: vmcnt(4) / vmcnt(2), lgkmcnt(0), expcnt untouched
+        __builtin_amdgcn_s_waitcnt(0x0070 | (2 * NP));
         __builtin_amdgcn_s_barrier();
     };
     auto block = [&](auto b0c, int kt0) {
@@ -364,6 +378,9 @@ __global__ __launch_bounds__(256, 3) void wgrad_h2i_group_kernel(const HGroup G)
 #undef AS
 #undef BS
 }
+
+__global__ __launch_bounds__(256, 3) void wgrad_h2i_group_kernel(const HGroup G) { wgrad_h2i_group_body<3>(G); }
+__global__ __launch_bounds__(256, 3) void wgrad_h2i_onepass_group_kernel(const HGroup G) { wgrad_h2i_group_body<1>(G); }
 
 // Sum of the batch slices in a fixed order; dW / db written once.  block = (tile, 8 rows); thread = (row, float4 of columns)
 __global__ __launch_bounds__(256) void wgrad_h2i_reduce_kernel(const HGroup G) {
@@ -530,7 +547,9 @@ extern "C" int dtc_wgrad_group_h2i(const DtcWgradH2iJob* jobs, int count, int M,
     const HGroup& G = P.dev;
     {
         dtc::ProfScope prof(dtc::prof_shape_name("linear_wgrad", M, G.tiles_total, count), P.flop, s, P.algo_bytes);
-        hipLaunchKernelGGL(wgrad_h2i_group_kernel, dim3(G.tiles_total * 8 * (int)dtc::ceil_div(G.splits, 8)), dim3(256), 0, s, G);
+        const dim3 grid(G.tiles_total * 8 * (int)dtc::ceil_div(G.splits, 8));
+        if (dtc_get_h2i_passes() == 1) hipLaunchKernelGGL(wgrad_h2i_onepass_group_kernel, grid, dim3(256), 0, s, G);
+        else hipLaunchKernelGGL(wgrad_h2i_group_kernel, grid, dim3(256), 0, s, G);
     }
     {
         dtc::ProfScope prof(dtc::prof_shape_name("wgrad_reduce", G.splits, G.tiles_total, count), (double)P.bytes + P.bytes / (double)G.splits, s);

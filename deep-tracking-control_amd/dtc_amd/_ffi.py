@@ -186,7 +186,7 @@ class DtcProfRec(C.Structure):
 ACT = {None: 0, "none": 0, "relu": 1, "crelu": 1, "elu": 2, "selu": 3, "lrelu": 4, "tanh": 5, "sigmoid": 6}
 MAX_OPERAND_ELEMS = (1 << 29) - 1
 
-ABI_VERSION = 17         # DTC_ABI_VERSION of include/dtc_hip.h this binding was written against
+ABI_VERSION = 18         # DTC_ABI_VERSION of include/dtc_hip.h this binding was written against
 
 _SIGS = {
     "dtc_version": (C.c_int, []),
@@ -243,6 +243,8 @@ _SIGS = {
     "dtc_probe_poison": (C.c_int, [C.c_uint32, C.c_int, c_f32p, c_stream]),
     "dtc_h2i_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "dtc_h2i_rows64_max": (None, [C.c_int]),
+    "dtc_set_h2i_passes": (None, [C.c_int]),
+    "dtc_get_h2i_passes": (C.c_int, []),
     "dtc_linear_fwd_chain_h2i": (C.c_int, [C.POINTER(DtcH2iFwdLayer), C.c_int, C.c_int, c_stream]),
     "dtc_linear_dgrad_chain_h2i": (C.c_int, [C.POINTER(DtcH2iDgradLayer), C.c_int, C.c_int, c_stream]),
     "dtc_h2i_trace": (None, [C.c_void_p]),

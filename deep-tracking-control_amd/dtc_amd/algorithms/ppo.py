@@ -312,8 +312,15 @@ class PPO:
 
     def __init__(self, actor_critic, num_learning_epochs=5, num_mini_batches=4, clip_param=0.2, gamma=0.99, lam=0.95,
                  value_loss_coef=1.0, entropy_coef=0.01, learning_rate=5.e-4, max_grad_norm=1.0,
-                 use_clipped_value_loss=True, schedule="adaptive", desired_kl=0.01, device='cpu'):
+                 use_clipped_value_loss=True, schedule="adaptive", desired_kl=0.01, device='cpu', *, gemm_passes=3):
         self.device = device
+        # MFMA passes per product of the update's operand-image schedule (h2i.set_h2i_passes): 3 = two-term fp16 operands, the arithmetic
+        # of the 1e-5 contract; 1 (opt-in) = their hi planes alone.  The rollout side (act / evaluate / compute_returns) does not follow it.
+        if gemm_passes not in (1, 3):
+            raise ValueError(f"gemm_passes: 3 (default) or 1, not {gemm_passes!r}")
+        self.gemm_passes = int(gemm_passes)
+        if self.gemm_passes != 3 and type(self).update is not PPO.update:
+            raise TypeError(f"{type(self).__name__} has no gemm_passes: its update() runs the three-pass arithmetic")
         self.desired_kl = desired_kl
         self.schedule = schedule
         self.learning_rate = learning_rate
@@ -542,6 +549,27 @@ class PPO:
         """This step runs the wide stacks on operand images (see ActorCriticDecoder.images_ok)."""
         return (self.use_images and self.relu_masks and self.group_wgrad and self.fuse_height_loss and self.actor_critic.images_ok(fw)
                 and fw.relu_mask("t1", 512) is not None)
+
+    ARITHMETIC = {3: "f32 (emulated: f16x2 split per operand, f32 accumulate)", 1: "f16 (block-scaled hi plane, f32 accumulate)"}
+
+    @property
+    def arithmetic(self):
+        """What the update's wide products compute on (gemm_passes)."""
+        return self.ARITHMETIC[self.gemm_passes]
+
+    @contextlib.contextmanager
+    def _gemm_passes_scope(self, fw):
+        """The optimisation steps inside run their image products with `gemm_passes` passes.  One pass exists on the operand-image
+        schedule alone: a configuration that would run any product of the step on other kernels is refused, not run on other arithmetic."""
+        if self.gemm_passes == 3:
+            yield                                      # (the library's setting is not touched: the default path is what it was)
+            return
+        if not (self.narrow_images and type(self)._ppo_step is PPO._ppo_step and self._image_mode(fw)):
+            raise _ffi.DtcError(f"gemm_passes=1 needs the operand-image schedule for the whole step: split path on (ops.SPLIT = {ops.SPLIT}), "
+                                f"mini-batches of a multiple of 128 rows (this one: {fw.B}), use_images / narrow_images / relu_masks / "
+                                f"group_wgrad / fuse_height_loss as constructed")
+        with h2i.h2i_passes_as(1):
+            yield
 
     def _wset(self, phase):
         ws = self._wsets.get(phase)
@@ -989,7 +1017,7 @@ class PPO:
         self._amax_static(flat, fw)
         self.optimizer.set_lr(self.learning_rate)
         stats = torch.zeros(STAT_COLS, dtype=torch.float32, device=dev) if stats is None else stats.to(dev)
-        with fw.slots.open():                          # the packed rollout rows serve both optimisation steps of this call
+        with self._gemm_passes_scope(fw), fw.slots.open():     # the packed rollout rows serve both optimisation steps of this call
             try:
                 if which in ("vae", "both"):
                     self._vae_step(fw, tw, flat, idx, eps1.to(dev).contiguous(), stats)
@@ -1061,7 +1089,7 @@ class PPO:
         stats = torch.zeros(steps, STAT_COLS, dtype=torch.float32, device=dev)
         lr_hist = torch.zeros(steps, dtype=torch.float64, device=dev) if return_stats else None
         k = 0
-        with fw.slots.open():                          # the packed rollout rows of a mini-batch serve all five epochs (packed_input)
+        with self._gemm_passes_scope(fw), fw.slots.open():     # the packed rollout rows of a mini-batch serve all five epochs (packed_input)
             try:
                 for _ in range(epochs):
                     for i in range(nmb):

@@ -10,6 +10,7 @@ Nothing here keeps a scale on the host: every image carries its own exponents, c
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 
 import torch
@@ -18,6 +19,32 @@ from . import _ffi
 from ._ffi import ACT, check, cptr, lib, ptr, segmat, seg, stream
 
 f32 = torch.float32
+
+
+# ---------------------------------------------------------------- MFMA passes per product (dtc_set_h2i_passes)
+def set_h2i_passes(n):
+    """3 (default): every product below is lo hi' + hi lo' + hi hi' (22-bit operands); 1 (opt-in): hi hi' alone -- 11-bit operands relative
+    to their row block's largest element, fp32 accumulation, a third of the matrix instructions.  Read by linear_fwd, linear_fwd_chain,
+    linear_dgrad, linear_dgrad_chain, linear_fwd_mse and wgrad_group at each call; images, packs and every other kernel do not follow it."""
+    n = int(n)
+    if n not in (1, 3):
+        raise ValueError(f"h2i passes: 3 (default) or 1, not {n}")
+    lib().dtc_set_h2i_passes(n)
+
+
+def h2i_passes() -> int:
+    return int(lib().dtc_get_h2i_passes())
+
+
+@contextlib.contextmanager
+def h2i_passes_as(n):
+    """The products launched inside the block run with `n` passes; the previous setting is back on exit, whatever happened inside."""
+    prev = h2i_passes()
+    set_h2i_passes(n)
+    try:
+        yield
+    finally:
+        lib().dtc_set_h2i_passes(prev)
 
 
 class HImage:

@@ -38,7 +38,7 @@ extern "C" {
 #define DTC_ACT_SIGMOID 6
 
 /* library / device info ------------------------------------------------------------------ */
-#define DTC_ABI_VERSION 17                   /* bumped whenever a signature or a by-value struct layout changes       */
+#define DTC_ABI_VERSION 18                   /* bumped whenever a signature or a by-value struct layout changes       */
 int dtc_version(void);                       /* == DTC_ABI_VERSION of the build; the host binding refuses a mismatch   */
 /* sizeof() of the structs that cross the boundary, in the order DtcGridCfg, DtcObsCfg, DtcRowCopy, DtcSeg, DtcSegMat,
    DtcFwdLayer, DtcWgradJob, DtcPpoCfg, DtcProfRec, DtcWimgJob, DtcH2iWJob, DtcH2iOperand, DtcWgradH2iJob, DtcEnvStep, DtcH2iFwdLayer, DtcH2iDgradLayer, DtcGruFwdItem, DtcGruBwdItem: the binding compares them with its own layouts at load time (a library
@@ -519,6 +519,15 @@ int64_t dtc_h2i_bytes(int M, int K);
 /* tuning: forward / data-gradient launches with at most max_tiles 128 x 128 result tiles run on 64-row tiles (twice the workgroups; default
  * 256 = one tile per CU; 0: never; -1: back to DTC_H2I_ROWS64_MAX / the default).  Results are bit-identical either way. */
 void dtc_h2i_rows64_max(int max_tiles);
+/* MFMA passes per product of the image-operand GEMM family: 3 (default) = lo hi' + hi lo' + hi hi', the arithmetic every accuracy
+ * statement of this header is made for; 1 (OPT-IN) = hi hi' alone: a third of the matrix instructions, half of the LDS-DMA pieces and
+ * fragment reads of the K loops, operands of 11 bits relative to their row block's largest element
+ * (|C - C_exact| <= (2^-10 + 2^-22) (|A| |B|^T) + fp32 accumulation), fp32 accumulation, the same images, exponents and epilogues.
+ * Read by dtc_linear_fwd_h2i, dtc_linear_fwd_chain_h2i, dtc_linear_dgrad_chain_h2i, dtc_linear_fwd_mse_h2i, dtc_linear_dgrad_h2i and
+ * dtc_wgrad_group_h2i at each call and by no other entry point.  Any other value is refused (dtc_last_error) and changes nothing.
+ * One pass has no form for a loss target of 2 GiB or more: dtc_linear_fwd_mse_h2i fails there instead of running three passes. */
+void dtc_set_h2i_passes(int passes);
+int dtc_get_h2i_passes(void);
 void dtc_h2i_trace(void* buf);   /* debug: per-workgroup {start, K loop done, end (100 MHz ticks), HW_ID} records of the launches that follow (NULL: off) */
 int dtc_h2i_pack(const DtcSegMat* X, int M, void* img, void* stream);
 int dtc_h2i_unpack(const void* img, int M, int K, float* out, int64_t ld, void* stream);
