@@ -498,12 +498,14 @@ class PPO:
 
     @staticmethod
     def _world():
-        return dp.world_size()
+        """This is a data-parallel job (dp.data_parallel(): more than one rank, or a one-rank group forced to count as one -- forcing
+        must be on before the trainer is constructed, where the rank-0 parameter broadcast happens)."""
+        return dp.data_parallel()
 
     def _allreduce_grads(self, opt):
         """One flat all-reduce per optimiser step (no-op on a single rank): the fallback when the per-bucket exchange did
         not run.  The main optimiser's range starts at offset 0, so its exchange carries the KL header too."""
-        if self._world() == 1:
+        if not self._world():
             return
         arena, (lo, hi) = self.actor_critic.arena, opt.range
         dp.allreduce_mean_(arena.grad_full[0:arena.HEADER + hi] if lo == 0 else opt.g)
@@ -516,7 +518,7 @@ class PPO:
         header) and overlaps the data-gradient chain still running on the compute lanes -- the decoders' / heads' bucket
         travels over xGMI while the encoders run backward.  Returns True when it took place."""
         self._flush_wgrads(tw)
-        if self._world() == 1 or not (self.overlap_exchange and self.overlap_wgrad):
+        if not self._world() or not (self.overlap_exchange and self.overlap_wgrad):
             return False
         for lane in ((tw.main, tw.aux) if tw.two_lanes else (torch.cuda.current_stream(),)):
             ev = tw.event()
@@ -542,7 +544,7 @@ class PPO:
     def _lr_from_header(self, stats):
         """After the exchange: the averaged KL drives the learning-rate rule (identical on every rank) and replaces the
         local value in the statistics table (written by the same launch)."""
-        if self._world() > 1 and self._adaptive():
+        if self._world() and self._adaptive():
             ops.lr_adapt(self.actor_critic.arena.kl_slot, self.optimizer.lr_dev, float(self.desired_kl), kl_out=stats[S_KL:S_KL + 1])
 
     def _image_mode(self, fw):
@@ -1058,10 +1060,10 @@ class PPO:
         cfg.clip_param, cfg.value_loss_coef, cfg.entropy_coef = self.clip_param, self.value_loss_coef, self.entropy_coef
         cfg.desired_kl = float(self.desired_kl) if self.desired_kl is not None else 0.0
         cfg.use_clipped_value_loss = int(bool(self.use_clipped_value_loss))
-        cfg.adaptive_schedule = int(self._adaptive() and self._world() == 1)
+        cfg.adaptive_schedule = int(self._adaptive() and not self._world())
         # data parallel: the finalize launch also deposits the KL mean in the gradient header (slot 0), which the first bucket's
         # all-reduce averages over the ranks
-        cfg.kl_mirror = self.actor_critic.arena.kl_slot.data_ptr() if (self._adaptive() and self._world() > 1) else None
+        cfg.kl_mirror = self.actor_critic.arena.kl_slot.data_ptr() if (self._adaptive() and self._world()) else None
         return cfg
 
     def update(self, perm=None, eps1=None, eps2=None, return_stats=False):

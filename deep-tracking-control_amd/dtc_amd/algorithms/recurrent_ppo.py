@@ -132,9 +132,9 @@ class RecurrentPPO:
         cfg.desired_kl = float(self.desired_kl) if self.desired_kl is not None else 0.0
         cfg.use_clipped_value_loss = int(bool(self.use_clipped_value_loss))
         adaptive = self.desired_kl is not None and self.schedule == 'adaptive'
-        cfg.adaptive_schedule = int(adaptive and dp.world_size() == 1)
+        cfg.adaptive_schedule = int(adaptive and not dp.data_parallel())
         # data parallel: the finalize launch also deposits the KL mean in slot 0 of the gradient header (averaged by the exchange)
-        cfg.kl_mirror = self.actor_critic.ensure_arena().kl_slot.data_ptr() if (adaptive and dp.world_size() > 1) else None
+        cfg.kl_mirror = self.actor_critic.ensure_arena().kl_slot.data_ptr() if (adaptive and dp.data_parallel()) else None
         return cfg
 
     def _train_ws(self, M, dev):
@@ -221,15 +221,32 @@ class RecurrentPPO:
             with self._wimages:                      # weight images of the step's split-path layers: one launch
                 self._forward_backward(tw, batch, stats, unpad_idx, store_idx, M, T, R, dev)
         arena = ac.arena
-        dp_adaptive = dp.world_size() > 1 and self.desired_kl is not None and self.schedule == 'adaptive'
-        if dp.world_size() > 1:
-            dp.allreduce_mean_(arena.grad_full)      # header (KL) + every gradient: one collective per optimiser step
+        dp_adaptive = dp.data_parallel() and self.desired_kl is not None and self.schedule == 'adaptive'
+        if dp.data_parallel():
+            self._exchange(tw, arena)
         if dp_adaptive:
             ops.lr_adapt(arena.kl_slot, self.optimizer.lr_dev, float(self.desired_kl), kl_out=stats[S_KL:S_KL + 1])
         if self.capture_grads:
             self.captured["main"] = ac.arena.grad.clone()
         self.optimizer.step(self.max_grad_norm, stats[S_GNORM:S_GNORM + 1])
         return stats
+
+    def _exchange(self, tw, arena):
+        """Data parallel: header (KL) + every gradient, one collective per optimiser step, after the join.  With the overlapped schedule
+        it is issued on the weight-gradient stream, as the bucket exchanges of PPO._exchange_bucket are -- the library-owned lane of
+        _lane_streams, not torch's current stream --, ordered behind the joined step and in front of the optimiser."""
+        if not self.overlap:
+            dp.allreduce_mean_(arena.grad_full)
+            return
+        main = torch.cuda.current_stream()
+        ev = tw.event()
+        ev.record(main)
+        tw.side.wait_event(ev)
+        with torch.cuda.stream(tw.side):
+            dp.allreduce_mean_(arena.grad_full)
+        tw.joined.record(tw.side)
+        main.wait_event(tw.joined)
+        tw._ev_next = 0
 
     def _forward_backward(self, tw, batch, stats, unpad_idx, store_idx, M, T, R, dev):
         ac = self.actor_critic

@@ -11,6 +11,10 @@ places where the hot path talks to other ranks:
 CE-net outlier statistics and the mini-batch permutation stay rank-local.  Everything else (planner,
 GAE scan, forward, backward, Adam) is embarrassingly parallel over envs; parameters stay bit-identical
 across ranks because every rank applies the same averaged gradient with the same learning rate.
+
+"Is this a data-parallel job" is `data_parallel()`: a process group with more than one rank -- or a one-rank group under
+`force_data_parallel()` / DTC_DP_FORCE=1, which runs the whole collective sequence through the backend on one GPU.
+`world_size()` is the NUMBER of ranks (counts, 1 / w) and does not follow forcing.
 """
 from __future__ import annotations
 
@@ -77,6 +81,38 @@ def world_size() -> int:
     return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
 
 
+# ---- a one-rank group that counts as data parallel (DTC_DP_FORCE=1 or `force_data_parallel()`): with world_size() == 1 every helper
+# below and every data-parallel branch of the trainers is skipped, so the production exchange -- bucket all-reduces on the
+# weight-gradient stream, the KL mean in the first bucket's header, ReduceOp.AVG -- never meets the collective library on one GPU.
+# Forced, one process on one device issues that whole sequence through RCCL; a mean or a sum over one rank returns its input bit for bit.
+_FORCE = os.environ.get("DTC_DP_FORCE", "0") == "1"
+
+
+class force_data_parallel:
+    """`force_data_parallel()` / `force_data_parallel(False)`: switch forcing on / off from here on; as a context manager
+    (`with force_data_parallel(): ...`) the previous value comes back on exit, also when the block raises.  Without an initialised
+    process group forcing does nothing.  Switch it on BEFORE the trainer is constructed: the rank-0 parameter broadcast is issued
+    there, and the trainer's lanes and loss configuration are chosen by `data_parallel()` as it is at that moment and at each update."""
+
+    def __init__(self, on: bool = True):
+        global _FORCE
+        self._previous = _FORCE
+        _FORCE = bool(on)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        global _FORCE
+        _FORCE = self._previous
+        return False
+
+
+def data_parallel() -> bool:
+    """This job exchanges gradients and statistics: a process group exists and it has more than one rank -- or forcing is on."""
+    return dist.is_available() and dist.is_initialized() and (dist.get_world_size() > 1 or _FORCE)
+
+
 def backend() -> str:
     return dist.get_backend() if dist.is_available() and dist.is_initialized() else ""
 
@@ -86,7 +122,7 @@ def rank() -> int:
 
 
 def allreduce_sum_(t: torch.Tensor) -> torch.Tensor:
-    if world_size() > 1:
+    if data_parallel():
         _record("all_reduce_sum", t)
         dist.all_reduce(t)
     return t
@@ -96,7 +132,7 @@ def allreduce_mean_(t: torch.Tensor) -> torch.Tensor:
     """In-place mean over the ranks.  RCCL averages inside the collective (ReduceOp.AVG: no second pass over the
     bucket); gloo has no AVG, there the sum is scaled afterwards (CPU tests, one-GPU rehearsals)."""
     w = world_size()
-    if w > 1:
+    if data_parallel():
         _record("all_reduce_mean", t)
         if dist.get_backend() == "nccl":
             dist.all_reduce(t, op=dist.ReduceOp.AVG)
@@ -116,7 +152,7 @@ def shard_range(num_items: int, r: int | None = None, w: int | None = None):
 
 def broadcast_parameters_(flat: torch.Tensor, src: int = 0) -> torch.Tensor:
     """Make the flat parameter arena identical on all ranks (called once after construction)."""
-    if world_size() > 1:
+    if data_parallel():
         _record("broadcast", flat)
         dist.broadcast(flat, src)
     return flat

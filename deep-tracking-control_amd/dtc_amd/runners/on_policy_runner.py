@@ -1,11 +1,16 @@
 """OnPolicyRunner with the reference's constructor / learn / save / load / get_inference_policy
 (rsl_rl/rsl_rl/runners/on_policy_runner.py:45-273).  The rollout loop and the checkpoint dictionary
-layout are kept; TensorBoard is optional (logging is not part of the hot path)."""
+layout are kept; TensorBoard is optional (logging is not part of the hot path).
+
+Under a process group (`distributed.data_parallel()`: one process per GPU, each with its own env shard -- INTEGRATION.md §4) rank 0 alone
+creates the TensorBoard writer, prints the log block and writes checkpoints; the episode means, the loss means and the throughput it
+logs are those of the whole job, gathered by ONE small all-reduce per iteration that every rank joins."""
 import os
 import time
 
 import torch
 
+from .. import distributed as dp
 from ..algorithms import PPO, RecurrentDecoderPPO, RecurrentPPO
 from ..env import HistoryWrapper
 from ..modules import ActorCritic, ActorCriticDecoder, ActorCriticDecoderRecurrent, ActorCriticRecurrent  # resolved by name from train_cfg
@@ -21,6 +26,9 @@ except Exception:                          # pragma: no cover
 _POLICIES = {"ActorCritic": ActorCritic, "ActorCriticRecurrent": ActorCriticRecurrent, "ActorCriticDecoder": ActorCriticDecoder,
              "ActorCriticDecoderRecurrent": ActorCriticDecoderRecurrent}
 _ALGORITHMS = {"PPO": PPO, "RecurrentPPO": RecurrentPPO, "RecurrentDecoderPPO": RecurrentDecoderPPO}
+
+
+_LOCAL = object()          # log(finished=...): take the means from the tracker
 
 
 class _EpisodeTracker:
@@ -53,6 +61,13 @@ class _EpisodeTracker:
         m = self.ring[:n].mean(dim=0)
         return float(m[0]), float(m[1])
 
+    def sums(self):
+        """float64 [3] on the device: sum of returns, sum of lengths and count over the ring entries `means()` averages -- what a rank
+        contributes to the job's means; no host round trip."""
+        n = self.finished.clamp(max=self.keep)
+        live = (torch.arange(self.keep, device=self.ring.device) < n).to(torch.float64).unsqueeze(1)
+        return torch.cat(((self.ring[:self.keep].double() * live).sum(dim=0), n.to(torch.float64).reshape(1)))
+
 
 class OnPolicyRunner:
     def __init__(self, env, train_cfg, log_dir=None, device='cpu'):
@@ -79,6 +94,7 @@ class OnPolicyRunner:
                                   [self.env.num_privileged_obs], [self.env.num_obs_history], [self.env.num_actions])
         self.log_dir = log_dir
         self.writer = None
+        self.tracker = None                    # the _EpisodeTracker of the last learn() that logged
         self.tot_timesteps = 0
         self.tot_time = 0
         self.current_learning_iteration = 0
@@ -112,6 +128,15 @@ class OnPolicyRunner:
 
     def learn(self, num_learning_iterations, init_at_random_ep_len=False):
         logging = self.log_dir is not None
+        dpj = dp.data_parallel()
+        if dpj:
+            # one small collective settles on every rank alike whether anyone logs: then every rank keeps a tracker and joins the
+            # per-iteration all-reduce of _job_means, or none does.  Files are rank 0's business alone, whatever log_dir the others got
+            wanted = torch.tensor([float(logging)], dtype=torch.float64, device=self.device)
+            tracking = float(dp.allreduce_sum_(wanted)) > 0
+            logging = logging and dp.rank() == 0
+        else:
+            tracking = logging
         if logging and self.writer is None and SummaryWriter is not None:
             self.writer = SummaryWriter(log_dir=self.log_dir, flush_secs=10)
         if init_at_random_ep_len:
@@ -119,7 +144,7 @@ class OnPolicyRunner:
                                                              high=int(self.env.max_episode_length))
         self.alg.actor_critic.train()
         state = dict(obs_dict=self.env.get_observations(), rew_buf=self.env.get_reward_buf())
-        tracker = _EpisodeTracker(self.env.num_envs, self.device) if logging else None
+        tracker = self.tracker = _EpisodeTracker(self.env.num_envs, self.device) if tracking else None
         ep_infos = []
         first, last = self.current_learning_iteration, self.current_learning_iteration + num_learning_iterations
         for it in range(first, last):
@@ -128,8 +153,11 @@ class OnPolicyRunner:
             t1 = time.time()
             losses = self.alg.update()           # (value, surrogate, adaptation, decoder, recons, vel, kld) means
             t2 = time.time()
+            finished = _LOCAL
+            if dpj and tracking:
+                losses, finished = self._job_means(losses, tracker)
             if logging:
-                self.log(it, last, losses, collection_time=t1 - t0, learn_time=t2 - t1, tracker=tracker)
+                self.log(it, last, losses, collection_time=t1 - t0, learn_time=t2 - t1, tracker=tracker, finished=finished)
                 if it % self.save_interval == 0:
                     self.save(os.path.join(self.log_dir, f'model_{it}.pt'))
             ep_infos.clear()
@@ -137,9 +165,21 @@ class OnPolicyRunner:
         if logging:
             self.save(os.path.join(self.log_dir, f'model_{last}.pt'))
 
-    def log(self, it, last, losses, collection_time, learn_time, tracker, width=80, pad=35):
+    def _job_means(self, losses, tracker):
+        """Data parallel: ONE all-reduce (sum) of a float64 device tensor per iteration, joined by every rank -- the tracker's local sum of
+        returns, sum of lengths and count, and the seven loss means of update() -> (loss means of the job, (mean reward, mean episode
+        length) over the finished episodes of ALL ranks or None)."""
+        local = torch.tensor(tuple(float(x) for x in losses) + (0.0,) * (7 - len(losses)), dtype=torch.float64, device=self.device)
+        total = dp.allreduce_sum_(torch.cat((tracker.sums(), local))).tolist()
+        count = total[2]
+        finished = (total[0] / count, total[1] / count) if count > 0 else None
+        return tuple(x / dp.world_size() for x in total[3:]), finished
+
+    def log(self, it, last, losses, collection_time, learn_time, tracker, width=80, pad=35, finished=_LOCAL):
+        """Writes and prints the scalars of iteration `it` and returns them.  `finished`: the (mean reward, mean episode length) to log
+        instead of the tracker's own (data parallel: the job's, _job_means); throughput counts the envs of every rank."""
         value_loss, surrogate_loss, _adaptation, _decoder, recons_loss, vel_loss, kld_loss = tuple(losses) + (0.0,) * (7 - len(losses))
-        steps = self.num_steps_per_env * self.env.num_envs
+        steps = self.num_steps_per_env * self.env.num_envs * dp.world_size()
         self.tot_timesteps += steps
         self.tot_time += collection_time + learn_time
         scalars = {
@@ -148,7 +188,8 @@ class OnPolicyRunner:
             'Policy/mean_noise_std': float(self.alg.actor_critic.std.mean()),
             'Perf/total_fps': int(steps / (collection_time + learn_time)),
             'Perf/collection time': collection_time, 'Perf/learning_time': learn_time}
-        finished = tracker.means()
+        if finished is _LOCAL:
+            finished = tracker.means()
         if finished is not None:
             scalars['Train/mean_reward'], scalars['Train/mean_episode_length'] = finished
         if self.writer is not None:
@@ -157,6 +198,7 @@ class OnPolicyRunner:
         lines = [f" Learning iteration {it}/{last} ".center(width, ' ')]
         lines += [f"{k + ':':>{pad}} {v:.4f}" for k, v in scalars.items()]
         print("#" * width + "\n" + "\n".join(lines))
+        return scalars
 
     def save(self, path, infos=None):
         torch.save({'model_state_dict': self.alg.actor_critic.state_dict(),
