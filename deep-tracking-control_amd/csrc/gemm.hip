@@ -852,8 +852,10 @@ extern "C" int dtc_debug_set_trace(unsigned long long* buf) {
 }
 #endif
 
-// rows of 16-bit words per matrix of M rows: 2 per 32-row block, row tiles of 128 rows are always written whole
-static inline long long mask_rows(int M) { return dtc::ceil_div(M, BM) * (BM / 32) * 2; }
+// rows of 16-bit words per matrix of M rows: 2 per 32-row group, ceil(M / 32) groups.  The kernels of this file and of gemm_s3.hip write
+// whole 128-row tiles and take M % 128 == 0 only; the operand-image kernels (gemm_h2i.hip) take any M and neither write nor read a group
+// whose first row is >= M (h2i_core.hpp: tail rows)
+static inline long long mask_rows(int M) { return dtc::ceil_div(M, 32) * 2; }
 
 extern "C" int64_t dtc_relu_mask_elems(int M, int N) {
     if (M <= 0 || N <= 0) return 0;

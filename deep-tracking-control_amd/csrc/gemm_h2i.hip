@@ -693,11 +693,17 @@ __device__ __forceinline__ void h2i_tile(CTileArgs& L, const MseEpiH& mse, const
             const float bv = (bias && col < N) ? bias[col] : 0.f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] += bv;
-            if (wmask && col < N) {                         // sign record of a ReLU layer (see linear_fwd_kernel); M % 128 == 0 (host)
+            if (wmask && col < N) {                         // sign record of a ReLU layer (see linear_fwd_kernel), any M (h2i_core.hpp: tail rows)
                 unsigned bits = 0u;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) bits |= acc[i][j][r] > 0.f ? (1u << r) : 0u;
-                wmask[((long long)((m0 + ro[i]) >> 5) * 2 + half) * ldwm + col] = (unsigned short)bits;
+                const int g0 = m0 + ro[i];                  // first row of this wave's 32-row group (wave-uniform)
+                bool has_words = true;
+                if (!full) {                                // (uniform) a group behind M has no record words; in one that straddles M the bits of rows
+                    has_words = g0 < M;                     // >= M are 0.  The 64-column form is never `full` (n0 + 128 > N): its whole row tiles
+                    bits &= hi_tail_bits(M - g0 - 4 * half);   // come through here too, where hi_tail_bits(>= 28) keeps every bit
+                }
+                if (has_words) wmask[((long long)(g0 >> 5) * 2 + half) * ldwm + col] = (unsigned short)bits;
             }
             if (act == DTC_ACT_RELU) {
 #pragma unroll
@@ -711,13 +717,15 @@ __device__ __forceinline__ void h2i_tile(CTileArgs& L, const MseEpiH& mse, const
             }
         }
     } else {
-        if (dg.rmask) {                                     // M % 128 == 0 (host); columns past the window read no record (results unused)
+        if (dg.rmask) {                                     // any M; columns past the window read no record (results unused)
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 const int mcol = n0 + co[j] + l31;
-                const unsigned bits = mcol < N ? dg.rmask[((long long)((m0 + ro[i]) >> 5) * 2 + half) * dg.ldm + mcol] : 0u;
+                // (uniform) a group behind M has no record words: its rows are zeros; a group that straddles M holds 0 bits for its rows >= M
+                const bool grp = full || m0 + ro[i] < M;
+                const unsigned bits = (grp && mcol < N) ? dg.rmask[((long long)((m0 + ro[i]) >> 5) * 2 + half) * dg.ldm + mcol] : 0u;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[i][j][r] = (bits >> r) & 1u ? acc[i][j][r] : 0.f;
             }
@@ -1290,7 +1298,7 @@ int fwd_args(const DtcH2iOperand* X, const void* wimg, const float* b, float* Y,
     rc = to_operand(X, M, t.A, out.K);
     if (rc != DTC_OK) return rc;
     DTC_REQUIRE((long long)M * (ldy > N ? ldy : N) <= MAX_ELEMS * 4 && hi_bytes(M, N) < (1ll << 31), "matrix too large");
-    if (relu_mask) DTC_REQUIRE(act == DTC_ACT_RELU && M % BM == 0 && (N % 128 == 0 || N == 64), "sign record: M=%d must be a multiple of 128, N=%d a multiple of 128 or 64", M, N);
+    if (relu_mask) DTC_REQUIRE(act == DTC_ACT_RELU && (N % 128 == 0 || N == 64), "sign record: ReLU only, N=%d must be a multiple of 128 or 64", N);
     const WimgView wv = wimg_view(wimg, N, t.A);
     t.wimg = wv.img;
     t.wexps = wv.exps;
@@ -1322,7 +1330,7 @@ int dgrad_args(const void* dZimg, int N, const void* wimgT, int Kwin, const DtcS
     if (rc != DTC_OK) return rc;
     rc = check_img(wimgT, "data gradient: weight image");
     if (rc != DTC_OK) return rc;
-    if (relu_mask) DTC_REQUIRE(M % BM == 0 && (Kwin % 128 == 0 || Kwin == 64), "sign record: M=%d must be a multiple of 128, the window %d a multiple of 128 or 64", M, Kwin);
+    if (relu_mask) DTC_REQUIRE(Kwin % 128 == 0 || Kwin == 64, "sign record: the window %d must be a multiple of 128 or 64", Kwin);
     DTC_REQUIRE(hi_bytes(M, Kwin) < (1ll << 31), "matrix too large");
     DtcH2iOperand zo{};
     zo.nseg = 1;

@@ -24,6 +24,20 @@
 //   * weight gradient (both operands images, the reduction index is the batch ROW): fragments of one operand are multiplied by
 //     2^(T - eZ[m] - eX[m]) <= 1 per batch row (4 v_pk_mul_f16 per fragment; T = the block's smallest exponent sum), accumulators
 //     rescaled by one scalar at the borders of the 128-row blocks.
+//
+// Tail rows.  image(M, K) with M % 128 != 0 owns the rows M .. 128 ceil(M / 128) - 1 of its last row tile (planes and exponent entries
+// are allocated for whole tiles).  The contract every producer and consumer keeps:
+//   * no consumer's result for a row < M, and no weight gradient, depends on the PLANES of those rows: forward / data gradient compute
+//     row m from row m alone and drop the tile's rows >= M in the epilogue (no fp32 store, zeros in the result image, no part in the
+//     loss partials); the weight gradient replaces the fragments of batch rows >= M by zeros before they meet an MFMA;
+//   * what a producer leaves there: h2i_pack_kernel and the GEMM epilogues write zeros (exponent HI_EZERO) into the tail rows of every
+//     row tile they visit (on 64-row tiles a 64-row half of the last 128 rows that lies wholly behind M belongs to no workgroup); the
+//     latent / loss kernels write rows < B only.  What nobody visits stays as allocated -- zeros, HI_EZERO (dtc_amd/h2i.py HImage) --
+//     and an image serves ONE row count for its lifetime.  Gradient images written by those kernels or by a data gradient with a sign
+//     record therefore hold ZEROS there;
+//   * ReLU sign records (one uint16 per 16 rows of a 32-row group, per half, per column; dtc_relu_mask_elems: ceil(M / 32) groups): a
+//     group whose first row is >= M has no words -- it is neither written nor read; in the group that straddles M the bits of rows
+//     >= M are written as 0 (hi_tail_bits), so the data gradient masks those rows to exact zeros whatever the product held.
 #pragma once
 #include "s3_core.hpp"
 
@@ -77,6 +91,15 @@ __device__ __forceinline__ int hi_half_wave_exp(u32 m) {
         m = o > m ? o : m;
     }
     return hi_exp(m);
+}
+// Sign-record word of a lane (accumulator layout of the 32 x 32 MFMA tile): bit r = 4 g + e stands for row 8 g + e of the lane's half
+// of a 32-row group (+ 4 for the upper half wave).  The bits whose row lies below `left` = M - (first row of the group) - 4 half;
+// left <= 0: none, left >= 28: all.
+__device__ __forceinline__ unsigned hi_tail_bits(int left) {
+    unsigned m = 0u;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) m |= (8 * (r >> 2) + (r & 3) < left) ? (1u << r) : 0u;
+    return m;
 }
 // 8 consecutive k of one row -> the 16-byte pieces of the two planes
 struct HiPiece {

@@ -332,6 +332,10 @@ extern "C" int dtc_cenet_latent_fwd(float* mulv, const float* eps, float* z, uin
     return dtc_cenet_latent_fwd_img(mulv, eps, z, mask, info, workspace, B, z_amax, nullptr, stream);
 }
 
+// zmu_img = image(B, 19).  Any B: the kernel writes the planes and the exponent of rows < B only (its element loop runs over 16 B
+// entries) and leaves the rows B .. 128 ceil(B / 128) - 1 of the last row tile as allocated -- zeros, HI_EZERO (h2i_core.hpp: tail rows).
+// Moments, thresholds, the radix select of the lower median and the outlier count are taken over the 16 B entries, never over the
+// tile-rounded row count.
 extern "C" int dtc_cenet_latent_fwd_img(float* mulv, const float* eps, float* z, uint8_t* mask, int32_t* info,
                                         void* workspace, int B, uint32_t* z_amax, void* zmu_img, void* stream) {
     DTC_REQUIRE(B > 0 && (long long)B * LAT >= 2, "bad batch %d", B);

@@ -587,6 +587,8 @@ extern "C" int dtc_vae_loss_fused(const float* recons, const float* mulv, const 
                                   drec_amax, nullptr, stream);
 }
 
+// drec_img = image(B, 53).  Any B: one wavefront per row b < B writes that row's planes and exponent; the rows behind B of the last row
+// tile stay as allocated -- zeros, HI_EZERO (h2i_core.hpp: tail rows).  Every loss mean and gradient scale divides by B.
 extern "C" int dtc_vae_loss_fused_img(const float* recons, const float* mulv, const float* next_obs, const float* base_vel,
                                       const int64_t* idx, float* d_recons, float* dmulv, const double* height_sq_part,
                                       int n_height_part, float* losses, void* workspace, int B, uint32_t* drec_amax, void* drec_img,
@@ -649,6 +651,9 @@ extern "C" int dtc_ppo_heads_loss(const float* Ha, int64_t ldha, const float* Hc
                                   num_actions, dha_amax, dhc_amax, dmean_amax, dval_amax, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
+// dHa_img / dHc_img = image(B, H), dmean_img = image(B, A), dval_img = image(B, 1).  Any B: rows < B only are written (planes and
+// exponents); the rows behind B of the last row tile stay as allocated -- zeros, HI_EZERO (h2i_core.hpp: tail rows).  The loss means,
+// the KL mean and the gradient scales are taken over B rows.
 extern "C" int dtc_ppo_heads_loss_img(const float* Ha, int64_t ldha, const float* Hc, int64_t ldhc, int H, const float* Wa,
                                       const float* ba, const float* Wc, const float* bc, int act_prev, const float* std,
                                       const float* actions, const float* old_logp, const float* old_mu, const float* old_sigma,

@@ -103,6 +103,7 @@ __device__ __forceinline__ void wgrad_h2i_group_body(const HGroup& G) {
     const int tr = t / J.col_tiles, tc = t - tr * J.col_tiles;
     const int m_begin = split * G.rows_per_split;                    // multiples of 128: a slice is a whole number of exponent blocks
     const int m_end = min(G.mtiles * 128, m_begin + G.rows_per_split);
+    const int m_live = min(m_end, G.M);                              // batch rows >= M (the tail of the last row tile, h2i_core.hpp) are never fetched: zeros land
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 1, wc = wave & 1;
@@ -120,7 +121,7 @@ __device__ __forceinline__ void wgrad_h2i_group_body(const HGroup& G) {
         // batch rows mb .. mb + 15 sit in row tile mb >> 7 at local rows (mb & 127) ..; rows >= m_end: nothing valid -> zeros
         const u32 ua = (u32)((mb >> 7) * J.st_n) * (u32)HI_CHUNK + (u32)(mb & 127) * 32u;
         const u32 ub = (u32)((mb >> 7) * J.st_k) * (u32)HI_CHUNK + (u32)(mb & 127) * 32u;
-        const u32 dead = oob_mask(mb + mrow, m_end - 1);
+        const u32 dead = oob_mask(mb + mrow, m_live - 1);
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
             __builtin_amdgcn_raw_ptr_buffer_load_lds(ares, (lds_void*)&AS(nbuf)[p][wave * 1024], 16, aoff | dead, ua + p * HI_PLANE, 0, 0);
@@ -222,6 +223,12 @@ __device__ __forceinline__ void wgrad_h2i_group_body(const HGroup& G) {
     // reads and the transfers' row offsets are immediates, a block's validity is one scalar -- ~80 instructions per stage, 12-16 of them MFMAs
     // (round 6; with ph = kt % 8 and the buffer as run-time / per-trip values the stage had ~130 and five taken branches: -6..9 % for the launch
     // alone, -1.15 ms per bench step, same bits; profiles/r06_wgrad_unroll_*.txt).  Three blocks (24 stages) per trip: stage kt sits in buffer kt % 3.
+    // A ragged M ends inside ONE block of a launch (tail / tail_n below).  Whole blocks are fetched by the plain transfers, one scalar
+    // dead / dead_n and the offsets hoisted per block; for the block M ends in those transfers are dead as a whole (zeros land) and a second
+    // set, issued right behind them in an unlikely uniform branch that lies out of line, fetches its live rows with a per-lane limit (a
+    // wave's transfers reach LDS in the order they were issued; the stage waits count them in that order, so a stage with twice the
+    // transfers only waits longer).  A whole block's stage is the stage it was plus one scalar test and one branch that is not taken.
+    auto tail_dead = [&](int row, int lim) { return oob_mask(mrow + row, lim - 1); };
     auto load_at = [&](auto nbc, u32 ua, u32 ub, u32 dead) {
         constexpr int nbuf = decltype(nbc)::value;
 #pragma unroll
@@ -233,7 +240,9 @@ __device__ __forceinline__ void wgrad_h2i_group_body(const HGroup& G) {
     struct Blk {
         int kt0, which;
         bool more;
-        u32 ua, ub, dead, ua_n, ub_n, dead_n;       // byte offsets of this block's / the next block's row tile in the two images; INVALID behind the slice
+        u32 ua, ub, dead, ua_n, ub_n, dead_n;       // byte offsets of this block's / the next block's row tile in the two images; INVALID: no live row in it
+        int lim, lim_n;                             // live batch rows of this block / the next one (<= 0: none -- behind the slice or behind M; >= 128: all)
+        bool tail, tail_n;                          // 0 < lim < 128: a ragged M ends inside the block
     };
     auto stage = [&](auto bc, auto phc, const Blk& B) {
         constexpr int buf = decltype(bc)::value, ph = decltype(phc)::value;
@@ -271,8 +280,15 @@ __device__ __forceinline__ void wgrad_h2i_group_body(const HGroup& G) {
         const f16x8 fv = *reinterpret_cast<const f16x8*>(&Ft[which][ph * 16 + 8 * khalf]);
         const f16x8 fbv = *reinterpret_cast<const f16x8*>(&Fb[which][ph * 16 + 8 * khalf]);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (ph < 6) load_at(std::integral_constant<int, (buf + 2) % 3>{}, B.ua + (ph + 2) * 512, B.ub + (ph + 2) * 512, B.dead);
-        else load_at(std::integral_constant<int, (buf + 2) % 3>{}, B.ua_n + (ph - 6) * 512, B.ub_n + (ph - 6) * 512, B.dead_n);
+        if constexpr (ph < 6) {
+            load_at(std::integral_constant<int, (buf + 2) % 3>{}, B.ua + (ph + 2) * 512, B.ub + (ph + 2) * 512, B.dead);
+            if (__builtin_expect(B.tail, 0))                  // (uniform, once per launch at most) the live rows of the block a ragged M ends in
+                load_at(std::integral_constant<int, (buf + 2) % 3>{}, B.ua + (ph + 2) * 512, B.ub + (ph + 2) * 512, tail_dead((ph + 2) * 16, B.lim));
+        } else {
+            load_at(std::integral_constant<int, (buf + 2) % 3>{}, B.ua_n + (ph - 6) * 512, B.ub_n + (ph - 6) * 512, B.dead_n);
+            if (__builtin_expect(B.tail_n, 0))
+                load_at(std::integral_constant<int, (buf + 2) % 3>{}, B.ua_n + (ph - 6) * 512, B.ub_n + (ph - 6) * 512, tail_dead((ph - 6) * 16, B.lim_n));
+        }
         __builtin_amdgcn_sched_barrier(0);
         f16x8 a[2][2], b[2][2];
 #pragma unroll
@@ -334,8 +350,12 @@ __device__ __forceinline__ void wgrad_h2i_group_body(const HGroup& G) {
         B.ub = (u32)((mb0 >> 7) * J.st_k) * (u32)HI_CHUNK;
         B.ua_n = B.ua + (u32)J.st_n * (u32)HI_CHUNK;
         B.ub_n = B.ub + (u32)J.st_k * (u32)HI_CHUNK;
-        B.dead = mb0 >= m_end ? INVALID : 0u;                 // (slices are whole 128-row blocks)
-        B.dead_n = mb0 + 128 >= m_end ? INVALID : 0u;
+        B.lim = m_live - mb0;                                 // (slices are whole 128-row blocks; M need not be)
+        B.lim_n = B.lim - 128;
+        B.dead = B.lim < 128 ? INVALID : 0u;                  // whole blocks alone are fetched by the plain transfers
+        B.dead_n = B.lim_n < 128 ? INVALID : 0u;
+        B.tail = B.lim > 0 && B.lim < 128;
+        B.tail_n = B.lim_n > 0 && B.lim_n < 128;
         stage(std::integral_constant<int, (b0 + 0) % 3>{}, std::integral_constant<int, 0>{}, B);
         stage(std::integral_constant<int, (b0 + 1) % 3>{}, std::integral_constant<int, 1>{}, B);
         stage(std::integral_constant<int, (b0 + 2) % 3>{}, std::integral_constant<int, 2>{}, B);

@@ -304,7 +304,10 @@ class _TrainWorkspace(_StepWorkspace):
                   (128, 64), (53, 128), (128, 265), (64, 128), (35, 64), (num_actions, 128), (1, 128)]
         self.wg = ops.workspace(max(lib.dtc_linear_wgrad_workspace(B, n, k) for n, k in shapes), dev)
         self.loss_ws = ops.workspace(lib.dtc_loss_workspace(B), dev)
-        self.hpart = torch.zeros(int(lib.dtc_linear_fwd_mse_parts(B, 693)), dtype=torch.float64, device=dev)
+        # (any B: every size below comes from the library's own size function of the kernel that writes the buffer -- the partial sums of
+        # whichever fused height-loss layer runs, the images through h2i.HImage / dtc_h2i_bytes, the sign records through dtc_relu_mask_elems)
+        self.hpart = torch.zeros(int(max(lib.dtc_linear_fwd_mse_parts(B, 693), lib.dtc_linear_fwd_mse_s3_parts(B, 693),
+                                         lib.dtc_linear_fwd_mse_h2i_parts(B, 693))), dtype=torch.float64, device=dev)
 
 
 class PPO:
@@ -312,7 +315,7 @@ class PPO:
 
     def __init__(self, actor_critic, num_learning_epochs=5, num_mini_batches=4, clip_param=0.2, gamma=0.99, lam=0.95,
                  value_loss_coef=1.0, entropy_coef=0.01, learning_rate=5.e-4, max_grad_norm=1.0,
-                 use_clipped_value_loss=True, schedule="adaptive", desired_kl=0.01, device='cpu', *, gemm_passes=3):
+                 use_clipped_value_loss=True, schedule="adaptive", desired_kl=0.01, device='cpu', *, gemm_passes=3, ragged_images=False):
         self.device = device
         # MFMA passes per product of the update's operand-image schedule (h2i.set_h2i_passes): 3 = two-term fp16 operands, the arithmetic
         # of the 1e-5 contract; 1 (opt-in) = their hi planes alone.  The rollout side (act / evaluate / compute_returns) does not follow it.
@@ -321,6 +324,14 @@ class PPO:
         self.gemm_passes = int(gemm_passes)
         if self.gemm_passes != 3 and type(self).update is not PPO.update:
             raise TypeError(f"{type(self).__name__} has no gemm_passes: its update() runs the three-pass arithmetic")
+        # The operand-image schedule of update() at ANY mini-batch row count >= 1 (opt-in).  False (default): mini-batches of whole 128-row
+        # tiles run on it, every other row count on round 4's converting kernels -- except where those have no form at all (rollout
+        # tensors of 2 GiB and more: _wants_ragged), which takes the image schedule at a ragged row count as well.  gemm_passes=1 at a
+        # ragged row count needs the flag: without it that combination stays the loud error it was (_gemm_passes_scope).
+        self.ragged_images = bool(ragged_images)
+        self._ragged = {}                  # mini-batch rows -> this trainer's choice for its update in flight (_set_ragged)
+        if self.ragged_images and type(self).update is not PPO.update:
+            raise TypeError(f"{type(self).__name__} has no ragged_images: its update() runs the operand-image schedule on whole 128-row tiles only")
         self.desired_kl = desired_kl
         self.schedule = schedule
         self.learning_rate = learning_rate
@@ -548,9 +559,27 @@ class PPO:
             ops.lr_adapt(self.actor_critic.arena.kl_slot, self.optimizer.lr_dev, float(self.desired_kl), kl_out=stats[S_KL:S_KL + 1])
 
     def _image_mode(self, fw):
-        """This step runs the wide stacks on operand images (see ActorCriticDecoder.images_ok)."""
-        return (self.use_images and self.relu_masks and self.group_wgrad and self.fuse_height_loss and self.actor_critic.images_ok(fw)
-                and fw.relu_mask("t1", 512) is not None)
+        """This step runs the wide stacks on operand images (see ActorCriticDecoder.images_ok).  The forward workspace is cached per
+        row count on the model and may serve another trainer: its `ragged` mark is re-stated here from THIS trainer's choice
+        (_set_ragged), so that it never carries over from whoever used the workspace last."""
+        ragged = fw.ragged = self._ragged.get(fw.B, False)
+        return (self.use_images and self.relu_masks and self.group_wgrad and self.fuse_height_loss
+                and self.actor_critic.images_ok(fw, ragged) and fw.relu_mask("t1", 512) is not None)
+
+    def _wants_ragged(self, B, flat):
+        """A mini-batch of B rows, B % 128 != 0, is to run on the operand-image schedule: asked for (ragged_images), or the step has no
+        other form -- a rollout tensor of 2 GiB and more (the converting kernels address 2^31 bytes per operand)."""
+        if B % 128 == 0 or type(self).update is not PPO.update or type(self)._ppo_step is not PPO._ppo_step:
+            return False
+        if self.ragged_images:
+            return True
+        return any(t.dim() == 2 and t.shape[0] * t.stride(0) > _ffi.MAX_OPERAND_ELEMS for t in flat.values())
+
+    def _set_ragged(self, fw, flat):
+        """Mark the forward workspace for this update.  The ragged schedule needs the WHOLE step on images (the fp32 / converting kernels
+        take sign records on whole 128-row tiles only), so it is on only with every switch of the image schedule as constructed."""
+        fw.ragged = self._ragged[fw.B] = bool(self._wants_ragged(fw.B, flat) and ops.SPLIT and self.use_images and self.narrow_images and self.relu_masks
+                         and self.group_wgrad and self.fuse_height_loss)
 
     ARITHMETIC = {3: "f32 (emulated: f16x2 split per operand, f32 accumulate)", 1: "f16 (block-scaled hi plane, f32 accumulate)"}
 
@@ -568,7 +597,7 @@ class PPO:
             return
         if not (self.narrow_images and type(self)._ppo_step is PPO._ppo_step and self._image_mode(fw)):
             raise _ffi.DtcError(f"gemm_passes=1 needs the operand-image schedule for the whole step: split path on (ops.SPLIT = {ops.SPLIT}), "
-                                f"mini-batches of a multiple of 128 rows (this one: {fw.B}), use_images / narrow_images / relu_masks / "
+                                f"mini-batches of a multiple of 128 rows (this one: {fw.B}) or ragged_images=True, use_images / narrow_images / relu_masks / "
                                 f"group_wgrad / fuse_height_loss as constructed")
         with h2i.h2i_passes_as(1):
             yield
@@ -1016,6 +1045,7 @@ class PPO:
         B = idx.numel()
         flat = {k: st.flat(k) for k in self._FLAT_NAMES}
         fw, tw = ac._fwd_ws(B), self._train_ws(B)
+        self._set_ragged(fw, flat)
         self._amax_static(flat, fw)
         self.optimizer.set_lr(self.learning_rate)
         stats = torch.zeros(STAT_COLS, dtype=torch.float32, device=dev) if stats is None else stats.to(dev)
@@ -1085,6 +1115,7 @@ class PPO:
         perm = perm.to(dev).contiguous()
         flat = {k: st.flat(k) for k in self._FLAT_NAMES}
         fw, tw = ac._fwd_ws(B), self._train_ws(B)
+        self._set_ragged(fw, flat)
         self._amax_static(flat, fw)
         cfg = self._loss_cfg()
         self.optimizer.set_lr(self.learning_rate)

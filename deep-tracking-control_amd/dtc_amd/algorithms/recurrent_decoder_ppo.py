@@ -106,6 +106,10 @@ class RecurrentDecoderPPO(PPO):
             first = last
 
     # ---------------------------------------------------------------- policy step with BPTT
+    def _image_mode(self, fw):
+        """The recurrent schedules (padded [T, R] layout, GRU time steps on images) are built for whole 128-row tiles: no ragged form."""
+        return fw.B % 128 == 0 and super()._image_mode(fw)
+
     def _memory_images(self):
         """The operand-image schedule of the policy step is built for 1-layer GRU memories with H % 128 == 0."""
         ac = self.actor_critic

@@ -149,13 +149,21 @@ def _cap_put(key, got, ref, native, got32=None):
 
 
 def unpack_sign_record(mask, M, N):
-    """The ReLU sign record of an [M, N] layer output (dtc_linear_fwd_mask layout) as a bool matrix."""
-    w = mask.view(torch.int16)[:(M // 32) * 2 * N].view(M // 32, 2, N).to(torch.int32) & 0xffff
-    out = torch.zeros(M // 32, 32, N, dtype=torch.bool, device=mask.device)
+    """The ReLU sign record of an [M, N] layer output (dtc_linear_fwd_mask layout) as a bool matrix.  Any M: the record holds
+    ceil(M / 32) groups of 32 rows; the rows behind M of the last group (written as 0 bits) are trimmed (`unpack_sign_groups` keeps them)."""
+    return unpack_sign_groups(mask, M, N)[:M]
+
+
+def unpack_sign_groups(mask, M, N):
+    """The ReLU sign record of an [M, N] layer output as a bool matrix of all 32 * ceil(M / 32) rows of its groups: the rows behind M of
+    the last group (0 bits) included."""
+    G = -(-M // 32)
+    w = mask.view(torch.int16)[:G * 2 * N].view(G, 2, N).to(torch.int32) & 0xffff
+    out = torch.zeros(G, 32, N, dtype=torch.bool, device=mask.device)
     for r in range(16):
         for half in range(2):
             out[:, (r & 3) + 8 * (r >> 2) + 4 * half, :] = ((w[:, half, :] >> r) & 1).bool()
-    return out.view(M, N)
+    return out.view(G * 32, N)
 
 
 def _act64(v, act):

@@ -292,6 +292,7 @@ class ActorCriticDecoder(nn.Module):
         def __init__(self, B, dev, num_actions):
             e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
             self.B = B
+            self.ragged = False              # set by the trainer: this step runs on operand images although B % 128 != 0 (images_ok)
             self.e1, self.e, self.mulv, self.z = e(B, 128), e(B, 64), e(B, 35), e(B, 16)
             self.mask = torch.empty(B, 16, dtype=torch.uint8, device=dev)
             self.info = torch.zeros(4, dtype=torch.int32, device=dev)
@@ -318,8 +319,10 @@ class ActorCriticDecoder(nn.Module):
 
         def relu_mask(self, name, width, enabled=True):
             """Sign record of a ReLU layer's [B, width] output (training only): the data gradient reads one bit per
-            element instead of the saved activation.  None when the shape is not eligible or the feature is off."""
-            if not enabled or not ops.relu_mask_ok(self.B, width):
+            element instead of the saved activation.  None when the shape is not eligible or the feature is off.  A row count that
+            is no multiple of 128 is eligible on the operand-image schedule alone (`ragged`): the fp32 / converting kernels take whole
+            128-row tiles only."""
+            if not enabled or not ops.relu_mask_ok(self.B, width) or not (self.B % 128 == 0 or self.ragged):
                 return None
             m = self._masks.get(name)
             if m is None:
@@ -390,11 +393,12 @@ class ActorCriticDecoder(nn.Module):
             zmu = ws.cur["p_zmu"] = ws.img("p_zmu", 19)
         ops.cenet_latent_fwd(ws.mulv, eps, ws.z, ws.mask, ws.info, ws.lat_ws, zmu_img=zmu)
 
-    def images_ok(self, ws):
+    def images_ok(self, ws, ragged=False):
         """The operand-image chain (dtc_amd/h2i.py: the wide stacks' activations live in HBM as the fp16 (hi, lo) planes the GEMM
-        kernels read by LDS-DMA, written once by the producing epilogue) runs on training steps whose mini-batch is a whole number of
-        128-row tiles (ReLU sign records, exponent blocks of the weight gradients)."""
-        return ops.SPLIT and ws.B % 128 == 0
+        kernels read by LDS-DMA, written once by the producing epilogue) runs by default on training steps whose mini-batch is a whole
+        number of 128-row tiles; `ragged`: at any row count >= 1 (the kernels keep the tail-row contract of csrc/h2i_core.hpp: the rows
+        behind B of the last tile are never a source of anything)."""
+        return ops.SPLIT and (bool(ragged) or ws.B % 128 == 0)
 
     def packed_input(self, ws, name, X, idx=None, reuse=False):
         """Operand image `name` of the fp32 operand X (DtcSegMat: the gathered rollout rows, narrow hand-over tensors).

@@ -392,8 +392,11 @@ def _wimage(W, segs, N, K, trans, h2=False):
 
 
 def relu_mask_ok(M, N):
-    """Shapes for which a ReLU layer can record its output signs (dtc_linear_fwd_mask / dtc_linear_dgrad_mask)."""
-    return M % 128 == 0 and (N % 128 == 0 or N == 64)
+    """Shapes for which a ReLU layer can record its output signs: whole 128-column tiles, or the 64-column form.  Any row count M >= 1:
+    the record holds ceil(M / 32) groups (dtc_relu_mask_elems).  The operand-image kernels (h2i.linear_fwd / linear_dgrad and their
+    chains) take it at any M; the fp32 and converting kernels behind ops.linear_fwd / linear_dgrad still need M % 128 == 0 and refuse
+    a record otherwise."""
+    return M >= 1 and (N % 128 == 0 or N == 64)
 
 
 def relu_mask(M, N, device):
