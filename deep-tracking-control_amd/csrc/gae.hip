@@ -6,6 +6,9 @@
 //  * dtc_adv_sqdev /    rollout_storage.py:151-152  (mean, unbiased std over all T*N samples; the
 //    dtc_adv_normalize  two reductions are exposed separately so data-parallel ranks can all-reduce
 //                       the two scalars in between -- SURVEY.md 8e item 2)
+//  * dtc_gae_contained / dtc_adv_sqdev_contained / dtc_adv_normalize_contained
+//                       the same three over the VALID rows of a per-row validity record (contain.hip): same grids, same block_sum,
+//                       same partials, same finalize order -- with no invalid row the results are the bits of the three above
 //  * dtc_gather_rows    rollout_storage.py:195-209  (`tensor.flatten(0,1)[batch_idx]`)
 //
 // Compiled with -ffp-contract=off: the scan reproduces oracle/gae.py bit for bit.
@@ -89,6 +92,82 @@ __global__ __launch_bounds__(256) void normalize_kernel(float* __restrict__ adv,
         adv[i] = (adv[i] - mean) / den;
 }
 
+// ---- the contained forms: gae_kernel / sqdev_kernel / normalize_kernel statement for statement, plus the validity record ------------
+__device__ __forceinline__ bool finite_f32(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
+
+// row_valid comes in as the record of the stored tensors and leaves as the final one: incoming AND finite return AND finite advantage.
+// A NaN travels backwards through an env's earlier steps, also across a done (0 * NaN is NaN in the reference's formula): those rows
+// become invalid -- the multiplication is NOT replaced by a select.  Sum and count take the valid rows only.
+__global__ __launch_bounds__(256) void gae_contained_kernel(const float* __restrict__ rewards, const float* __restrict__ values,
+                                                            const uint8_t* __restrict__ dones, const float* __restrict__ last_values,
+                                                            float gamma, float lam, float* __restrict__ returns,
+                                                            float* __restrict__ adv_out, uint8_t* __restrict__ row_valid,
+                                                            double* __restrict__ partials, double* __restrict__ count_partials, int T,
+                                                            int N) {
+    __shared__ double sh[4];
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    double local = 0.0, cnt = 0.0;
+    if (n < N) {
+        float adv = 0.0f;
+        float next_v = last_values[n];
+        for (int t = T - 1; t >= 0; --t) {
+            const int64_t o = (int64_t)t * N + n;
+            const float v = values[o];
+            const float nnt = 1.0f - (float)dones[o];
+            const float ng = nnt * gamma;
+            const float delta = (rewards[o] + ng * next_v) - v;
+            adv = delta + (ng * lam) * adv;
+            const float ret = adv + v;
+            returns[o] = ret;
+            const float a = ret - v;
+            adv_out[o] = a;
+            const bool ok = row_valid[o] != 0 && finite_f32(ret) && finite_f32(a);
+            row_valid[o] = ok ? 1 : 0;
+            if (ok) {
+                local += (double)a;
+                cnt += 1.0;
+            }
+            next_v = v;
+        }
+    }
+    const double tot = block_sum(local, sh);
+    const double ctot = block_sum(cnt, sh);
+    if (threadIdx.x == 0) {
+        partials[blockIdx.x] = tot;
+        count_partials[blockIdx.x] = ctot;
+    }
+}
+
+// stats = [sum, count, sum of squared deviations, -]: the count is read from device memory (data parallel: the job's, all-reduced with
+// the sum in one collective)
+__global__ __launch_bounds__(256) void sqdev_contained_kernel(const float* __restrict__ adv, const uint8_t* __restrict__ row_valid,
+                                                              const double* __restrict__ stats, double* __restrict__ partials,
+                                                              int64_t n) {
+    __shared__ double sh[4];
+    const double count = stats[1];
+    const double mean = stats[0] / count;
+    double v = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        if (row_valid[i]) {
+            const double d = (double)adv[i] - mean;
+            v += d * d;
+        }
+    }
+    const double tot = block_sum(v, sh);
+    if (threadIdx.x == 0) partials[blockIdx.x] = tot;
+}
+
+// only valid rows are normalised; an invalid row keeps whatever the scan wrote
+__global__ __launch_bounds__(256) void normalize_contained_kernel(float* __restrict__ adv, const uint8_t* __restrict__ row_valid,
+                                                                  const double* __restrict__ stats, int64_t n) {
+    const double count = stats[1];
+    const float mean = (float)(stats[0] / count);
+    const float stdv = (float)sqrt(stats[2] / (count - 1.0));
+    const float den = stdv + 1e-8f;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        if (row_valid[i]) adv[i] = (adv[i] - mean) / den;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void gather_rows_kernel(const T* __restrict__ src, const int64_t* __restrict__ idx,
                                                           T* __restrict__ dst, int64_t rows, int64_t row_elems) {
@@ -127,15 +206,16 @@ constexpr int MAX_PARTIALS = 4096;
 // Reduction partials: one lazily allocated scratch PER DEVICE (keyed by the device that is current at the call, which
 // is the device of the caller's tensors).  Calls that share a device must be ordered on one stream -- the storage
 // issues dtc_gae / dtc_adv_sqdev back to back on torch's current stream; they are not meant to run concurrently.
-double* partial_buffer() {
+// `which`: 0 = the sums, 1 = the valid-row counts of the contained scan (a slab of their own beside the sums).
+double* partial_buffer(int which = 0) {
     constexpr int MAX_DEV = 64;
-    static double* buf[MAX_DEV] = {};
+    static double* buf[2][MAX_DEV] = {};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV) return nullptr;
-    if (!buf[dev]) {
-        if (hipMalloc(&buf[dev], sizeof(double) * MAX_PARTIALS) != hipSuccess) buf[dev] = nullptr;
+    if (!buf[which][dev]) {
+        if (hipMalloc(&buf[which][dev], sizeof(double) * MAX_PARTIALS) != hipSuccess) buf[which][dev] = nullptr;
     }
-    return buf[dev];
+    return buf[which][dev];
 }
 
 }  // namespace
@@ -176,6 +256,48 @@ extern "C" int dtc_adv_normalize(float* advantages, const double* stats, int64_t
     const int grid = (int)(dtc::ceil_div(n_local, 256) < 2048 ? dtc::ceil_div(n_local, 256) : 2048);
     hipLaunchKernelGGL(normalize_kernel, dim3(grid), dim3(256), 0, s, advantages, stats, count, n_local);
     return dtc::check_launch("adv_normalize");
+}
+
+extern "C" int dtc_gae_contained(const float* rewards, const float* values, const uint8_t* dones, const float* last_values,
+                                 float gamma, float lam, float* returns, float* advantages, uint8_t* row_valid, double* stats, int T,
+                                 int N, void* stream) {
+    DTC_REQUIRE(T > 0 && N > 0, "bad shape T=%d N=%d", T, N);
+    DTC_REQUIRE(rewards && values && dones && last_values && returns && advantages && row_valid && stats, "null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    double* partials = partial_buffer();
+    double* counts = partial_buffer(1);
+    DTC_REQUIRE(partials != nullptr && counts != nullptr, "partial buffer allocation failed");
+    const int grid = (int)dtc::ceil_div(N, 256);
+    DTC_REQUIRE(grid <= MAX_PARTIALS, "N too large for one call (max %d envs)", MAX_PARTIALS * 256);
+    {
+        dtc::ProfScope prof("gae_scan_contained", (double)T * N * 19.0, s);
+        hipLaunchKernelGGL(gae_contained_kernel, dim3(grid), dim3(256), 0, s, rewards, values, dones, last_values, gamma, lam,
+                           returns, advantages, row_valid, partials, counts, T, N);
+    }
+    hipLaunchKernelGGL(finalize_sum_kernel, dim3(1), dim3(256), 0, s, partials, grid, stats, 0);
+    hipLaunchKernelGGL(finalize_sum_kernel, dim3(1), dim3(256), 0, s, counts, grid, stats, 1);
+    return dtc::check_launch("gae_contained");
+}
+
+extern "C" int dtc_adv_sqdev_contained(const float* advantages, const uint8_t* row_valid, double* stats, int64_t n_local,
+                                       void* stream) {
+    DTC_REQUIRE(advantages && row_valid && stats && n_local > 0, "bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    double* partials = partial_buffer();
+    DTC_REQUIRE(partials != nullptr, "partial buffer allocation failed");
+    const int grid = (int)(dtc::ceil_div(n_local, 256) < 1024 ? dtc::ceil_div(n_local, 256) : 1024);
+    hipLaunchKernelGGL(sqdev_contained_kernel, dim3(grid), dim3(256), 0, s, advantages, row_valid, stats, partials, n_local);
+    hipLaunchKernelGGL(finalize_sum_kernel, dim3(1), dim3(256), 0, s, partials, grid, stats, 2);
+    return dtc::check_launch("adv_sqdev_contained");
+}
+
+extern "C" int dtc_adv_normalize_contained(float* advantages, const uint8_t* row_valid, const double* stats, int64_t n_local,
+                                           void* stream) {
+    DTC_REQUIRE(advantages && row_valid && stats && n_local > 0, "bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    const int grid = (int)(dtc::ceil_div(n_local, 256) < 2048 ? dtc::ceil_div(n_local, 256) : 2048);
+    hipLaunchKernelGGL(normalize_contained_kernel, dim3(grid), dim3(256), 0, s, advantages, row_valid, stats, n_local);
+    return dtc::check_launch("adv_normalize_contained");
 }
 
 extern "C" int dtc_gather_rows(const void* src, const int64_t* idx, void* dst, int64_t rows, int64_t row_bytes,

@@ -186,7 +186,7 @@ class DtcProfRec(C.Structure):
 ACT = {None: 0, "none": 0, "relu": 1, "crelu": 1, "elu": 2, "selu": 3, "lrelu": 4, "tanh": 5, "sigmoid": 6}
 MAX_OPERAND_ELEMS = (1 << 29) - 1
 
-ABI_VERSION = 18         # DTC_ABI_VERSION of include/dtc_hip.h this binding was written against
+ABI_VERSION = 19        # DTC_ABI_VERSION of include/dtc_hip.h this binding was written against
 
 _SIGS = {
     "dtc_version": (C.c_int, []),
@@ -220,6 +220,14 @@ _SIGS = {
                           C.c_int, c_stream]),
     "dtc_adv_sqdev": (C.c_int, [c_f32p, c_f64p, C.c_int64, C.c_double, c_stream]),
     "dtc_adv_normalize": (C.c_int, [c_f32p, c_f64p, C.c_int64, C.c_double, c_stream]),
+    "dtc_rows_finite": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int, C.c_int64, c_u8p, c_stream]),
+    "dtc_gae_contained": (C.c_int, [c_f32p, c_f32p, c_u8p, c_f32p, C.c_float, C.c_float, c_f32p, c_f32p, c_u8p, c_f64p, C.c_int,
+                                    C.c_int, c_stream]),
+    "dtc_adv_sqdev_contained": (C.c_int, [c_f32p, c_u8p, c_f64p, C.c_int64, c_stream]),
+    "dtc_adv_normalize_contained": (C.c_int, [c_f32p, c_u8p, c_f64p, C.c_int64, c_stream]),
+    "dtc_compact_workspace": (C.c_int64, [C.c_int64]),
+    "dtc_compact_valid": (C.c_int, [c_u8p, C.c_int64, c_i64p, c_i64p, C.c_void_p, c_stream]),
+    "dtc_perm_repair": (C.c_int, [c_i64p, C.c_int64, c_u8p, C.c_int64, c_i64p, c_i64p, c_i64p, c_stream]),
     "dtc_gather_rows": (C.c_int, [C.c_void_p, c_i64p, C.c_void_p, C.c_int64, C.c_int64, c_stream]),
     "dtc_scatter_rows": (C.c_int, [c_f32p, c_i64p, c_f32p, C.c_int64, C.c_int64, c_stream]),
     "dtc_pack_cols": (C.c_int, [C.POINTER(DtcSegMat), c_f32p, C.c_int64, C.c_int64, C.c_void_p, c_stream]),

@@ -315,8 +315,17 @@ class PPO:
 
     def __init__(self, actor_critic, num_learning_epochs=5, num_mini_batches=4, clip_param=0.2, gamma=0.99, lam=0.95,
                  value_loss_coef=1.0, entropy_coef=0.01, learning_rate=5.e-4, max_grad_norm=1.0,
-                 use_clipped_value_loss=True, schedule="adaptive", desired_kl=0.01, device='cpu', *, gemm_passes=3, ragged_images=False):
+                 use_clipped_value_loss=True, schedule="adaptive", desired_kl=0.01, device='cpu', *, gemm_passes=3, ragged_images=False,
+                 contain_nonfinite=False):
         self.device = device
+        # Rows of the stored rollout with a non-finite element stay out of the update (opt-in): compute_returns takes the advantage
+        # statistics over the valid rows only and leaves a validity record (RolloutStorage), update() repairs its permutation so that
+        # it names valid rows only -- and reads the rollout through that permutation alone, which holds on the operand-image schedule
+        # (_contain_scope).  `last_nonfinite_rows`: this rank's invalid rows of the last update.  False (default): nothing is added.
+        self.contain_nonfinite = bool(contain_nonfinite)
+        self.last_nonfinite_rows = 0
+        if self.contain_nonfinite and type(self).update is not PPO.update:
+            raise TypeError(f"{type(self).__name__} has no contain_nonfinite: the mini-batches of its update() are trajectories, not row sets")
         # MFMA passes per product of the update's operand-image schedule (h2i.set_h2i_passes): 3 = two-term fp16 operands, the arithmetic
         # of the 1e-5 contract; 1 (opt-in) = their hi planes alone.  The rollout side (act / evaluate / compute_returns) does not follow it.
         if gemm_passes not in (1, 3):
@@ -428,6 +437,8 @@ class PPO:
                      obs_history_shape, action_shape):
         self.storage = RolloutStorage(num_envs, num_transitions_per_env, actor_obs_shape, privileged_obs_shape,
                                       obs_history_shape, action_shape, self.device)
+        if self.contain_nonfinite:
+            self.storage.contain_nonfinite = True
 
     def test_mode(self):
         self.actor_critic.eval()
@@ -601,6 +612,21 @@ class PPO:
                                 f"group_wgrad / fuse_height_loss as constructed")
         with h2i.h2i_passes_as(1):
             yield
+
+    def _contained_perm(self, fw, perm):
+        """contain_nonfinite: the permutation of this update with every entry that names an invalid row replaced by a valid one
+        (ops.perm_repair; unchanged when every row is valid).  Containment holds only where the update reads the rollout through the
+        mini-batch index alone -- the operand-image schedule: the converting kernels scale by a whole-tensor amax and turn everything
+        NaN by design -- and needs the validity record compute_returns left for the rollout in the storage."""
+        st = self.storage
+        if not (self.narrow_images and type(self)._ppo_step is PPO._ppo_step and self._image_mode(fw)):
+            raise _ffi.DtcError(f"contain_nonfinite=True needs the operand-image schedule for the whole step: split path on (ops.SPLIT = {ops.SPLIT}), "
+                                f"mini-batches of a multiple of 128 rows (this one: {fw.B}) or ragged_images=True, use_images / narrow_images / relu_masks / "
+                                f"group_wgrad / fuse_height_loss as constructed -- every other schedule reads whole rollout tensors (amax)")
+        if not (st.contain_nonfinite and st.record_fresh and st.row_valid is not None):
+            raise _ffi.DtcError("contain_nonfinite=True: the storage holds no validity record of this rollout (compute_returns makes it, "
+                                "storage.clear() voids it) -- call compute_returns after the rollout and before update()")
+        return ops.perm_repair(perm, st.row_valid, st.valid_list, st.valid_rows)
 
     def _wset(self, phase):
         ws = self._wsets.get(phase)
@@ -1116,6 +1142,8 @@ class PPO:
         flat = {k: st.flat(k) for k in self._FLAT_NAMES}
         fw, tw = ac._fwd_ws(B), self._train_ws(B)
         self._set_ragged(fw, flat)
+        if self.contain_nonfinite:
+            perm = self._contained_perm(fw, perm)
         self._amax_static(flat, fw)
         cfg = self._loss_cfg()
         self.optimizer.set_lr(self.learning_rate)
@@ -1144,6 +1172,15 @@ class PPO:
             g['lr'] = self.learning_rate
         self.last_update_stats = host
         m = host.double().mean(dim=0)
+        if self.contain_nonfinite:
+            # (behind the update's one synchronisation: every step has run, the two counts are plain reads)
+            rows, valid, job = st.row_valid.numel(), int(st.valid_rows.item()), int(st._stats[1].item())
+            self.last_nonfinite_rows = rows - valid
+            if valid < 1 or job < 2:
+                st.clear()
+                raise _ffi.DtcError(f"contain_nonfinite: {valid} valid rows of {rows} on this rank, {job} valid rows in the job -- with none "
+                                    "on a rank or fewer than two in the job nothing can be contained: the advantage statistics and "
+                                    "this update's weights are not finite")
         st.clear()
         out = (float(m[S_VALUE]), float(m[S_SURR]), 0.0, 0, float(m[S_RECONS]), float(m[S_VEL]), float(m[S_KLD]))
         if return_stats:

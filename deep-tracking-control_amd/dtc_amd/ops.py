@@ -34,6 +34,72 @@ def adv_normalize(advantages, stats, count):
                                   float(count), stream()), "dtc_adv_normalize")
 
 
+# containment of non-finite rollout rows (csrc/contain.hip; the contained scan and statistics: csrc/gae.hip)
+MAX_SCAN_MATS = 16
+
+
+def rows_finite(tensors, out: torch.Tensor | None = None) -> torch.Tensor:
+    """uint8 [R]: 1 where row r of EVERY matrix is finite.  `tensors`: up to 16 contiguous fp32 [R, w] matrices of any width w >= 1
+    (any size: the kernel reads them as flat arrays at 64-bit indices).  `out` given: ANDed into it (a 0 already there stays 0)."""
+    tensors = list(tensors)
+    if not 1 <= len(tensors) <= MAX_SCAN_MATS:
+        raise _ffi.DtcError(f"rows_finite takes 1..{MAX_SCAN_MATS} matrices, got {len(tensors)}")
+    R = tensors[0].shape[0]
+    for t in tensors:
+        if t.dim() != 2 or t.shape[0] != R or t.shape[1] < 1:
+            raise _ffi.DtcError(f"rows_finite: every matrix is [R = {R}, w >= 1], got {tuple(t.shape)}")
+    if out is None:
+        out = torch.ones(R, dtype=torch.uint8, device=tensors[0].device)
+    elif out.shape != (R,):
+        raise _ffi.DtcError(f"rows_finite: out is uint8 [{R}], got {tuple(out.shape)}")
+    mats = (C.c_void_p * len(tensors))(*(cptr(t, f32) for t in tensors))
+    widths = (C.c_int64 * len(tensors))(*(t.shape[1] for t in tensors))
+    check(lib().dtc_rows_finite(mats, widths, len(tensors), R, cptr(out, torch.uint8), stream()), "dtc_rows_finite")
+    return out
+
+
+def gae_contained(rewards, values, dones, last_values, gamma, lam, returns, advantages, row_valid, stats):
+    """ops.gae with the validity record (uint8 [T * N], in and out): row_valid &= finite return and advantage;
+    stats[0] = sum(adv), stats[1] = count, both over the rows valid afterwards."""
+    T, N = rewards.shape[0], rewards.shape[1]
+    if row_valid.numel() != T * N:
+        raise _ffi.DtcError(f"gae_contained: the record has {row_valid.numel()} rows, the rollout {T * N}")
+    check(lib().dtc_gae_contained(cptr(rewards, f32), cptr(values, f32), cptr(dones, torch.uint8), cptr(last_values, f32),
+                                  gamma, lam, cptr(returns, f32), cptr(advantages, f32), cptr(row_valid, torch.uint8),
+                                  cptr(stats, torch.float64), T, N, stream()), "dtc_gae_contained")
+
+
+def adv_sqdev_contained(advantages, row_valid, stats):
+    """stats[2] = sum of squared deviations of the valid advantages from stats[0] / stats[1] (the count is read on the device)."""
+    check(lib().dtc_adv_sqdev_contained(cptr(advantages, f32), cptr(row_valid, torch.uint8), cptr(stats, torch.float64),
+                                        advantages.numel(), stream()), "dtc_adv_sqdev_contained")
+
+
+def adv_normalize_contained(advantages, row_valid, stats):
+    check(lib().dtc_adv_normalize_contained(cptr(advantages, f32), cptr(row_valid, torch.uint8), cptr(stats, torch.float64),
+                                            advantages.numel(), stream()), "dtc_adv_normalize_contained")
+
+
+def compact_valid(row_valid, valid_list=None, n_valid=None, ws=None):
+    """(valid_list int64 [R]: the valid rows in ascending order in its first n_valid entries, n_valid int64 [1]), on the device."""
+    R, dev = row_valid.numel(), row_valid.device
+    valid_list = torch.zeros(R, dtype=torch.int64, device=dev) if valid_list is None else valid_list
+    n_valid = torch.zeros(1, dtype=torch.int64, device=dev) if n_valid is None else n_valid
+    ws = workspace(lib().dtc_compact_workspace(R), dev) if ws is None else ws
+    check(lib().dtc_compact_valid(cptr(row_valid, torch.uint8), R, cptr(valid_list, torch.int64), cptr(n_valid, torch.int64),
+                                  ptr(ws), stream()), "dtc_compact_valid")
+    return valid_list, n_valid
+
+
+def perm_repair(perm, row_valid, valid_list, n_valid) -> torch.Tensor:
+    """int64 [len(perm)]: perm[j] where that row is valid, valid_list[perm[j] % n_valid] otherwise."""
+    out = torch.empty_like(perm)
+    check(lib().dtc_perm_repair(cptr(perm, torch.int64), perm.numel(), cptr(row_valid, torch.uint8), row_valid.numel(),
+                                cptr(valid_list, torch.int64), cptr(n_valid, torch.int64), cptr(out, torch.int64), stream()),
+          "dtc_perm_repair")
+    return out
+
+
 def gather_rows(src: torch.Tensor, idx: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     """src[idx] for a contiguous 2-D+ tensor (rows = dim 0)."""
     assert src.is_contiguous() and idx.dtype == torch.int64 and idx.is_contiguous()

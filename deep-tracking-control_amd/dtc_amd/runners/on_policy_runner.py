@@ -153,7 +153,7 @@ class OnPolicyRunner:
             t1 = time.time()
             losses = self.alg.update()           # (value, surrogate, adaptation, decoder, recons, vel, kld) means
             t2 = time.time()
-            finished = _LOCAL
+            finished, self._job_nonfinite = _LOCAL, None
             if dpj and tracking:
                 losses, finished = self._job_means(losses, tracker)
             if logging:
@@ -169,11 +169,19 @@ class OnPolicyRunner:
         """Data parallel: ONE all-reduce (sum) of a float64 device tensor per iteration, joined by every rank -- the tracker's local sum of
         returns, sum of lengths and count, and the seven loss means of update() -> (loss means of the job, (mean reward, mean episode
         length) over the finished episodes of ALL ranks or None)."""
-        local = torch.tensor(tuple(float(x) for x in losses) + (0.0,) * (7 - len(losses)), dtype=torch.float64, device=self.device)
+        local = tuple(float(x) for x in losses) + (0.0,) * (7 - len(losses))
+        if self._contains():
+            local += (float(self.alg.last_nonfinite_rows),)     # the job's SUM of invalid rows rides in the same all-reduce
+        local = torch.tensor(local, dtype=torch.float64, device=self.device)
         total = dp.allreduce_sum_(torch.cat((tracker.sums(), local))).tolist()
         count = total[2]
         finished = (total[0] / count, total[1] / count) if count > 0 else None
-        return tuple(x / dp.world_size() for x in total[3:]), finished
+        if self._contains():
+            self._job_nonfinite = int(total[10])
+        return tuple(x / dp.world_size() for x in total[3:10]), finished
+
+    def _contains(self):
+        return bool(getattr(self.alg, "contain_nonfinite", False))
 
     def log(self, it, last, losses, collection_time, learn_time, tracker, width=80, pad=35, finished=_LOCAL):
         """Writes and prints the scalars of iteration `it` and returns them.  `finished`: the (mean reward, mean episode length) to log
@@ -192,6 +200,10 @@ class OnPolicyRunner:
             finished = tracker.means()
         if finished is not None:
             scalars['Train/mean_reward'], scalars['Train/mean_episode_length'] = finished
+        if self._contains():
+            # rows of the last update that were not finite and stayed out of it (data parallel: the job's sum, _job_means)
+            job = getattr(self, "_job_nonfinite", None)
+            scalars['Train/nonfinite_rows'] = self.alg.last_nonfinite_rows if job is None else job
         if self.writer is not None:
             for k, v in scalars.items():
                 self.writer.add_scalar(k, v, it)

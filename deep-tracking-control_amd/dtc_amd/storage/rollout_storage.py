@@ -154,8 +154,41 @@ class RolloutStorage:
             for dst, h in zip(saved, net):
                 dst[self.step].copy_(h)
 
+    # Containment of non-finite rows (PPO(contain_nonfinite=True), set by PPO.init_storage): compute_returns then leaves the validity
+    # record of the stored rollout -- `row_valid` uint8 [T * N] (1 = every stored element of the row, its return and its advantage
+    # are finite), `valid_list` int64 [T * N] (the valid flat rows t * N + n, ascending, in its first `valid_rows` entries),
+    # `valid_rows` int64 [1] on the device -- and marks it fresh; clear() voids the mark.  Off (default): none of these exists.
+    contain_nonfinite = False
+    row_valid = valid_list = valid_rows = None
+    record_fresh = False
+    _SCANNED = ("observations", "next_observations", "privileged_observations", "observation_histories", "actions", "rewards",
+                "values", "actions_log_prob", "mu", "sigma", "base_vel")
+
     def clear(self):
         self.step = 0
+        self.record_fresh = False
+
+    def _compute_returns_contained(self, last_values, gamma, lam):
+        """compute_returns over the valid rows only: scan of the eleven stored tensors, contained GAE, compaction, all-reduce of
+        [sum, count], squared deviations, all-reduce, normalise -- two collectives, as without containment; the count never reaches
+        the host here.  _stats = [sum, count, squared deviations, -] (the job's under data parallelism)."""
+        R = self.num_transitions_per_env * self.num_envs
+        if self.row_valid is None or self.row_valid.device != self._stats.device:
+            dev = self._stats.device
+            self.row_valid = torch.empty(R, dtype=torch.uint8, device=dev)
+            self.valid_list = torch.zeros(R, dtype=torch.int64, device=dev)
+            self.valid_rows = torch.zeros(1, dtype=torch.int64, device=dev)
+            self._compact_ws = ops.workspace(_ffi.lib().dtc_compact_workspace(R), dev)
+        self.row_valid.fill_(1)
+        ops.rows_finite([self.flat(k) for k in self._SCANNED], out=self.row_valid)
+        ops.gae_contained(self.rewards, self.values, self.dones, last_values.contiguous().float(), gamma, lam, self.returns,
+                          self.advantages, self.row_valid, self._stats)
+        ops.compact_valid(self.row_valid, self.valid_list, self.valid_rows, self._compact_ws)
+        dp.allreduce_sum_(self._stats[0:2])
+        ops.adv_sqdev_contained(self.advantages, self.row_valid, self._stats)
+        dp.allreduce_sum_(self._stats[2:3])
+        ops.adv_normalize_contained(self.advantages, self.row_valid, self._stats)
+        self.record_fresh = True
 
     def compute_returns(self, last_values, gamma, lam):
         """GAE(lambda) + advantage normalisation (rollout_storage.py:138-152).  Under torch.distributed
@@ -163,6 +196,8 @@ class RolloutStorage:
         T, N = self.num_transitions_per_env, self.num_envs
         if self._stats is None:
             self._stats = torch.zeros(4, dtype=torch.float64, device=self.device)
+        if self.contain_nonfinite:
+            return self._compute_returns_contained(last_values, gamma, lam)
         ops.gae(self.rewards, self.values, self.dones, last_values.contiguous().float(), gamma, lam, self.returns,
                 self.advantages, self._stats)
         world = dp.world_size()

@@ -38,7 +38,7 @@ extern "C" {
 #define DTC_ACT_SIGMOID 6
 
 /* library / device info ------------------------------------------------------------------ */
-#define DTC_ABI_VERSION 18                   /* bumped whenever a signature or a by-value struct layout changes       */
+#define DTC_ABI_VERSION 19                  /* bumped whenever a signature or a by-value struct layout changes       */
 int dtc_version(void);                       /* == DTC_ABI_VERSION of the build; the host binding refuses a mismatch   */
 /* sizeof() of the structs that cross the boundary, in the order DtcGridCfg, DtcObsCfg, DtcRowCopy, DtcSeg, DtcSegMat,
    DtcFwdLayer, DtcWgradJob, DtcPpoCfg, DtcProfRec, DtcWimgJob, DtcH2iWJob, DtcH2iOperand, DtcWgradH2iJob, DtcEnvStep, DtcH2iFwdLayer, DtcH2iDgradLayer, DtcGruFwdItem, DtcGruBwdItem: the binding compares them with its own layouts at load time (a library
@@ -409,6 +409,38 @@ int dtc_gae(const float* rewards, const float* values, const uint8_t* dones, con
 int dtc_adv_sqdev(const float* advantages, double* stats, int64_t n_local, double count, void* stream);
 /* adv = (adv - mean) / (std_unbiased + 1e-8) with mean = stats[0]/count, std from stats[1]. */
 int dtc_adv_normalize(float* advantages, const double* stats, int64_t n_local, double count, void* stream);
+
+/* ---- containment of non-finite rollout rows (PPO(contain_nonfinite=True)): rollout_storage.py:138-152, 165 --------------------
+ * Row (t, n) of the stored rollout is VALID iff every element of its row is finite (exponent field not all ones: denormals, +-0 and
+ * +-FLT_MAX are finite) in every stored fp32 tensor, and its return and un-normalised advantage are finite.  The record is one byte
+ * per flat row t * N + n (1 = valid). */
+/* The record of the stored tensors (rollout_storage.py:57-97, the buffers the sums of :138-152 and the mini-batches of :165 read):
+ * `mats` / `widths` are HOST arrays of `count` (1..16) device pointers to contiguous fp32 [R, widths[i]] matrices (4-byte aligned, any
+ * width >= 1, any size: 64-bit flat indices) -- row_valid[r] &= every element of row r of every matrix is finite.  row_valid is
+ * read-modify-write in the sense that the kernel only ever stores 0: the caller initialises it (to 1, or to an earlier record). */
+int dtc_rows_finite(const float* const* mats, const int64_t* widths, int count, int64_t R, uint8_t* row_valid, void* stream);
+/* dtc_gae (rollout_storage.py:138-150) with the record: the same scan statement for statement (a NaN travels backwards through an
+ * env's earlier steps, also across a done); row_valid[o] <- row_valid[o] AND finite(return) AND finite(advantage);
+ * stats[0] = sum(advantages) and stats[1] = count over the rows that are valid afterwards.  stats is double[4] on the device. */
+int dtc_gae_contained(const float* rewards, const float* values, const uint8_t* dones, const float* last_values, float gamma,
+                      float lam, float* returns, float* advantages, uint8_t* row_valid, double* stats, int T, int N, void* stream);
+/* rollout_storage.py:151-152 over the valid rows: stats[2] = sum((adv - stats[0]/stats[1])^2); then adv = (adv - mean) /
+ * (std_unbiased + 1e-8) on the valid rows (invalid rows keep what the scan wrote).  The count is READ FROM stats[1] on the device
+ * (data-parallel callers all-reduce stats[0..1] in one collective first, stats[2] in a second); reductions in the order of
+ * dtc_adv_sqdev / dtc_adv_normalize, so with no invalid row the results are theirs bit for bit. */
+int dtc_adv_sqdev_contained(const float* advantages, const uint8_t* row_valid, double* stats, int64_t n_local, void* stream);
+int dtc_adv_normalize_contained(float* advantages, const uint8_t* row_valid, const double* stats, int64_t n_local, void* stream);
+/* The rows a permutation of rollout_storage.py:165 may name: record -> valid_list[0 .. *n_valid) = the valid flat rows in ascending
+ * order, *n_valid = their number (both on the device;
+ * valid_list has room for n entries, those behind *n_valid are not written).  Deterministic (counts, one single-block scan, scatter);
+ * `workspace`: dtc_compact_workspace(n) bytes. */
+int64_t dtc_compact_workspace(int64_t n);
+int dtc_compact_valid(const uint8_t* row_valid, int64_t n, int64_t* valid_list, int64_t* n_valid, void* workspace, void* stream);
+/* The permutation of rollout_storage.py:165 over valid rows only: out[j] = perm[j] where row perm[j] is valid, else
+ * valid_list[perm[j] % *n_valid].  The length does not change; with no invalid row out == perm.  (*n_valid == 0, or an entry outside
+ * [0, R): the entry passes through.) */
+int dtc_perm_repair(const int64_t* perm, int64_t len, const uint8_t* row_valid, int64_t R, const int64_t* valid_list,
+                    const int64_t* n_valid, int64_t* out, void* stream);
 
 /* ---- mini-batch gather: rollout_storage.py:195-209 (`tensor[batch_idx]`) ------------------ */
 int dtc_gather_rows(const void* src, const int64_t* idx, void* dst, int64_t rows, int64_t row_bytes,
