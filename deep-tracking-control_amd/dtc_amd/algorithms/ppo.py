@@ -22,6 +22,7 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -34,6 +35,14 @@ from ..utils import PaddedBuffers
 # columns of the per-step statistics table
 S_RECONS, S_VEL, S_KLD, S_HEIGHT, S_VAE_GNORM, S_SURR, S_VALUE, S_ENTROPY, S_KL, S_GNORM = range(10)
 STAT_COLS = 12
+
+
+class Schedule(NamedTuple):
+    """The kernel schedule of the update in flight, decided once per update (PPO._resolve_schedule; the rule: DESIGN.md §4.2f)."""
+    images: bool = False     # the wide stacks run on operand images (dtc_amd/h2i.py)
+    whole: bool = False      # ... and the narrow ones: the step launches no layer kernel outside the image family
+    ragged: bool = False     # ... at a mini-batch row count that is no multiple of 128
+    passes: int = 3          # MFMA passes per image product (gemm_passes)
 
 
 class FusedAdam:
@@ -232,7 +241,7 @@ class _StepWorkspace(_Lanes):
         self.wg = self.gws = self.gws2 = self.gws_img = None
         self.pending, self.held = [], []      # queued weight-gradient jobs; operands of flushed jobs (alive until the join)
         self.pending_img = []                 # queued weight-gradient jobs whose operands are activation images
-        self.narrow_wgrad = False             # the step in flight runs the image chain: its fp32 weight-gradient jobs are the narrow layers
+        self.schedule = Schedule()            # of the owning trainer's update in flight (PPO._resolve_schedule)
 
     def padded(self, name, rows, width, slots=None):
         return self.pad.get(name, rows, width, self._dev, slots)
@@ -312,6 +321,9 @@ class _TrainWorkspace(_StepWorkspace):
 
 class PPO:
     actor_critic: ActorCriticDecoder
+    # The mini-batches of update() are row sets of the stored rollout, each run by _vae_step / _ppo_step.  False (RecurrentDecoderPPO):
+    # trajectories -- no contain_nonfinite, no gemm_passes, no ragged_images, no step that is `whole` (Schedule)
+    row_sets = True
 
     def __init__(self, actor_critic, num_learning_epochs=5, num_mini_batches=4, clip_param=0.2, gamma=0.99, lam=0.95,
                  value_loss_coef=1.0, entropy_coef=0.01, learning_rate=5.e-4, max_grad_norm=1.0,
@@ -321,25 +333,24 @@ class PPO:
         # Rows of the stored rollout with a non-finite element stay out of the update (opt-in): compute_returns takes the advantage
         # statistics over the valid rows only and leaves a validity record (RolloutStorage), update() repairs its permutation so that
         # it names valid rows only -- and reads the rollout through that permutation alone, which holds on the operand-image schedule
-        # (_contain_scope).  `last_nonfinite_rows`: this rank's invalid rows of the last update.  False (default): nothing is added.
+        # (_contained_perm).  `last_nonfinite_rows`: this rank's invalid rows of the last update.  False (default): nothing is added.
         self.contain_nonfinite = bool(contain_nonfinite)
         self.last_nonfinite_rows = 0
-        if self.contain_nonfinite and type(self).update is not PPO.update:
+        if self.contain_nonfinite and not self.row_sets:
             raise TypeError(f"{type(self).__name__} has no contain_nonfinite: the mini-batches of its update() are trajectories, not row sets")
         # MFMA passes per product of the update's operand-image schedule (h2i.set_h2i_passes): 3 = two-term fp16 operands, the arithmetic
         # of the 1e-5 contract; 1 (opt-in) = their hi planes alone.  The rollout side (act / evaluate / compute_returns) does not follow it.
         if gemm_passes not in (1, 3):
             raise ValueError(f"gemm_passes: 3 (default) or 1, not {gemm_passes!r}")
         self.gemm_passes = int(gemm_passes)
-        if self.gemm_passes != 3 and type(self).update is not PPO.update:
+        if self.gemm_passes != 3 and not self.row_sets:
             raise TypeError(f"{type(self).__name__} has no gemm_passes: its update() runs the three-pass arithmetic")
         # The operand-image schedule of update() at ANY mini-batch row count >= 1 (opt-in).  False (default): mini-batches of whole 128-row
         # tiles run on it, every other row count on round 4's converting kernels -- except where those have no form at all (rollout
         # tensors of 2 GiB and more: _wants_ragged), which takes the image schedule at a ragged row count as well.  gemm_passes=1 at a
-        # ragged row count needs the flag: without it that combination stays the loud error it was (_gemm_passes_scope).
+        # ragged row count needs the flag: without it that combination stays the loud error it was (_needs_whole_step).
         self.ragged_images = bool(ragged_images)
-        self._ragged = {}                  # mini-batch rows -> this trainer's choice for its update in flight (_set_ragged)
-        if self.ragged_images and type(self).update is not PPO.update:
+        if self.ragged_images and not self.row_sets:
             raise TypeError(f"{type(self).__name__} has no ragged_images: its update() runs the operand-image schedule on whole 128-row tiles only")
         self.desired_kl = desired_kl
         self.schedule = schedule
@@ -569,28 +580,32 @@ class PPO:
         if self._world() and self._adaptive():
             ops.lr_adapt(self.actor_critic.arena.kl_slot, self.optimizer.lr_dev, float(self.desired_kl), kl_out=stats[S_KL:S_KL + 1])
 
-    def _image_mode(self, fw):
-        """This step runs the wide stacks on operand images (see ActorCriticDecoder.images_ok).  The forward workspace is cached per
-        row count on the model and may serve another trainer: its `ragged` mark is re-stated here from THIS trainer's choice
-        (_set_ragged), so that it never carries over from whoever used the workspace last."""
-        ragged = fw.ragged = self._ragged.get(fw.B, False)
-        return (self.use_images and self.relu_masks and self.group_wgrad and self.fuse_height_loss
-                and self.actor_critic.images_ok(fw, ragged) and fw.relu_mask("t1", 512) is not None)
+    def _image_mode(self, fw, ragged=None):
+        """A step of this trainer on forward workspace `fw` runs the wide stacks on operand images (see ActorCriticDecoder.images_ok).
+        A query that changes nothing.  `ragged` None: as this trainer's last resolved schedule at that row count has it -- not the
+        workspace's own mark, which is whoever's update ran on it last."""
+        if ragged is None:
+            tw = self._tws.get((fw.B, self.actor_critic.std.device))
+            ragged = tw is not None and tw.schedule.ragged
+        return bool(self.use_images and self.relu_masks and self.group_wgrad and self.fuse_height_loss
+                    and self.actor_critic.images_ok(fw, ragged) and ops.relu_mask_ok(fw.B, 512))
 
     def _wants_ragged(self, B, flat):
         """A mini-batch of B rows, B % 128 != 0, is to run on the operand-image schedule: asked for (ragged_images), or the step has no
         other form -- a rollout tensor of 2 GiB and more (the converting kernels address 2^31 bytes per operand)."""
-        if B % 128 == 0 or type(self).update is not PPO.update or type(self)._ppo_step is not PPO._ppo_step:
+        if B % 128 == 0 or not self.row_sets:
             return False
         if self.ragged_images:
             return True
         return any(t.dim() == 2 and t.shape[0] * t.stride(0) > _ffi.MAX_OPERAND_ELEMS for t in flat.values())
 
-    def _set_ragged(self, fw, flat):
-        """Mark the forward workspace for this update.  The ragged schedule needs the WHOLE step on images (the fp32 / converting kernels
-        take sign records on whole 128-row tiles only), so it is on only with every switch of the image schedule as constructed."""
-        fw.ragged = self._ragged[fw.B] = bool(self._wants_ragged(fw.B, flat) and ops.SPLIT and self.use_images and self.narrow_images and self.relu_masks
-                         and self.group_wgrad and self.fuse_height_loss)
+    def _resolve_schedule(self, fw, flat):
+        """The Schedule of the update that starts here, from the knobs as they stand now (the rule: DESIGN.md §4.2f), and the one place
+        that marks the forward workspace (`fw.ragged`, read by its relu_mask): it is cached per row count on the model and may have served
+        another trainer.  Ragged needs the WHOLE step on images: the fp32 / converting kernels take sign records on whole tiles only."""
+        fw.ragged = ragged = bool(self.narrow_images and self._wants_ragged(fw.B, flat) and self._image_mode(fw, True))
+        images = self._image_mode(fw, ragged)
+        return Schedule(images, bool(images and self.narrow_images and self.row_sets), ragged, self.gemm_passes)
 
     ARITHMETIC = {3: "f32 (emulated: f16x2 split per operand, f32 accumulate)", 1: "f16 (block-scaled hi plane, f32 accumulate)"}
 
@@ -599,30 +614,29 @@ class PPO:
         """What the update's wide products compute on (gemm_passes)."""
         return self.ARITHMETIC[self.gemm_passes]
 
-    @contextlib.contextmanager
-    def _gemm_passes_scope(self, fw):
-        """The optimisation steps inside run their image products with `gemm_passes` passes.  One pass exists on the operand-image
-        schedule alone: a configuration that would run any product of the step on other kernels is refused, not run on other arithmetic."""
-        if self.gemm_passes == 3:
-            yield                                      # (the library's setting is not touched: the default path is what it was)
-            return
-        if not (self.narrow_images and type(self)._ppo_step is PPO._ppo_step and self._image_mode(fw)):
-            raise _ffi.DtcError(f"gemm_passes=1 needs the operand-image schedule for the whole step: split path on (ops.SPLIT = {ops.SPLIT}), "
-                                f"mini-batches of a multiple of 128 rows (this one: {fw.B}) or ragged_images=True, use_images / narrow_images / relu_masks / "
-                                f"group_wgrad / fuse_height_loss as constructed")
-        with h2i.h2i_passes_as(1):
-            yield
+    @staticmethod
+    def _needs_whole_step(tw, what, why=""):
+        """`what` (an opt-in) exists where the whole step runs on operand images (Schedule.whole) and is refused everywhere else."""
+        if not tw.schedule.whole:
+            raise _ffi.DtcError(f"{what} needs the operand-image schedule for the whole step: split path on (ops.SPLIT = {ops.SPLIT}), "
+                                f"mini-batches of a multiple of 128 rows (this one: {tw.B}) or ragged_images=True, use_images / narrow_images / relu_masks / "
+                                f"group_wgrad / fuse_height_loss as constructed{why}")
 
-    def _contained_perm(self, fw, perm):
+    def _gemm_passes_scope(self, tw):
+        """The optimisation steps inside run their image products with the schedule's passes.  One pass exists on the operand-image
+        schedule alone: a configuration that would run any product of the step on other kernels is refused, not run on other arithmetic."""
+        if tw.schedule.passes == 3:
+            return contextlib.nullcontext()            # (the library's setting is not touched: the default path is what it was)
+        self._needs_whole_step(tw, "gemm_passes=1")
+        return h2i.h2i_passes_as(tw.schedule.passes)
+
+    def _contained_perm(self, tw, perm):
         """contain_nonfinite: the permutation of this update with every entry that names an invalid row replaced by a valid one
         (ops.perm_repair; unchanged when every row is valid).  Containment holds only where the update reads the rollout through the
         mini-batch index alone -- the operand-image schedule: the converting kernels scale by a whole-tensor amax and turn everything
         NaN by design -- and needs the validity record compute_returns left for the rollout in the storage."""
         st = self.storage
-        if not (self.narrow_images and type(self)._ppo_step is PPO._ppo_step and self._image_mode(fw)):
-            raise _ffi.DtcError(f"contain_nonfinite=True needs the operand-image schedule for the whole step: split path on (ops.SPLIT = {ops.SPLIT}), "
-                                f"mini-batches of a multiple of 128 rows (this one: {fw.B}) or ragged_images=True, use_images / narrow_images / relu_masks / "
-                                f"group_wgrad / fuse_height_loss as constructed -- every other schedule reads whole rollout tensors (amax)")
+        self._needs_whole_step(tw, "contain_nonfinite=True", " -- every other schedule reads whole rollout tensors (amax)")
         if not (st.contain_nonfinite and st.record_fresh and st.row_valid is not None):
             raise _ffi.DtcError("contain_nonfinite=True: the storage holds no validity record of this rollout (compute_returns makes it, "
                                 "storage.clear() voids it) -- call compute_returns after the rollout and before update()")
@@ -673,7 +687,7 @@ class PPO:
             return
         jobs, tw.pending = tw.pending, []
         jobs_img, tw.pending_img = tw.pending_img, []
-        narrow = tw.narrow_wgrad                               # image chain: the fp32 jobs are the narrow layers -> single-pass kernels
+        narrow = tw.schedule.images                            # image chain: the fp32 jobs are the narrow layers -> single-pass kernels
         two = self.overlap_wgrad and bool(jobs_img) and bool(jobs) and narrow and self.side2_wgrad   # the narrow group runs BESIDE the wide one
         ws = tw.group_ws(jobs, False if narrow else None, lane2=two) if jobs else None
         ws_img = tw.group_ws_img(jobs_img) if jobs_img else None
@@ -698,7 +712,6 @@ class PPO:
 
     def _join(self, tw):
         self._flush_wgrads(tw)
-        tw.narrow_wgrad = False
         tw.join()
         tw.held.clear()
 
@@ -732,11 +745,7 @@ class PPO:
             self._bwd_img(tw, L["ce1"], g_headi, fw.img("e1"))
             chain = [dict(dZimg=dmi, W=L["head"].W, dXimg=g_headi),
                      dict(dZimg=g_headi, W=L["ce1"].W, dXimg=g_ce1i, mask=fw.relu_mask("e1", L["ce0"].n_out, self.relu_masks))]
-            if self.narrow_chains:
-                h2i.linear_dgrad_chain(chain, wset=wset)
-            else:
-                for c in chain:
-                    h2i.linear_dgrad(c["dZimg"], c["W"], None, c["dXimg"], mask=c.get("mask"), wset=wset)
+            h2i.dgrad_layers(chain, self.narrow_chains, wset)
             self._bwd_img(tw, L["ce0"], g_ce1i, fw.cur["p_hist"])
             tw.live_img |= {"g_head", "g_ce1"}
             return
@@ -752,14 +761,12 @@ class PPO:
         Two compute lanes: the CE-net branch (encoder -> latent -> decoder; small layers) runs on `aux` next to
         the terrain auto-encoder (512-wide layers) on the main stream; `tw.order(a, b)` marks each point where
         one branch needs the other's result."""
-        ac = self.actor_critic
-        L = ac.L
         _ffi.lib().dtc_set_concurrency_hint(int(bool(self.overlap_wgrad)))     # weight gradients on the side stream
         early = self._run_phase("vae", fw, tw, self._vae_forward_backward, flat, idx, eps, stats)
         if not early:
             self._allreduce_grads(self.vae_optimizer)
         if self.capture_grads:
-            self.captured["vae"] = ac.arena.grad.clone()
+            self.captured["vae"] = self.actor_critic.arena.grad.clone()
         self.vae_optimizer.step(self.max_grad_norm, stats[S_VAE_GNORM:S_VAE_GNORM + 1])
 
     def _images(self, phase):
@@ -774,8 +781,7 @@ class PPO:
         """Forward + backward of one optimisation step.  Image chain: the phase's weight images are rebuilt by one grouped launch in
         front of the lanes' fork (the optimiser wrote the weights since they were last built); nothing else is kept on the host.
         Otherwise: round 4's converting kernels inside their ops.WeightImages block."""
-        tw.narrow_wgrad = self._image_mode(fw)
-        if tw.narrow_wgrad:
+        if tw.schedule.images:
             wset = self._wset(phase)
             wset.rebuild()
             return body(fw, tw, *args, wset)
@@ -804,11 +810,7 @@ class PPO:
                 chain = [dict(X=[p_d, fw.img("lt")], W=L["cd0"].W, b=L["cd0"].b, Yimg=c1i, act="relu", mask=fw.relu_mask("c1", 64, rm)),
                          dict(X=c1i, W=L["cd1"].W, b=L["cd1"].b, Yimg=c2i, act="relu", mask=fw.relu_mask("c2", 128, rm)),
                          dict(X=c2i, W=L["cd2"].W, b=L["cd2"].b, Y=tw.rec)]
-                if self.narrow_chains:
-                    h2i.linear_fwd_chain(chain, wset=wset)
-                else:
-                    for c in chain:
-                        h2i.linear_fwd(c["X"], c["W"], c["b"], c.get("Y"), c.get("Yimg"), c.get("act"), mask=c.get("mask"), wset=wset)
+                h2i.fwd_layers(chain, self.narrow_chains, wset)
                 tw.live_img |= {"c1", "c2"}
             else:
                 ops.linear_fwd(dec_in, L["cd0"].W, L["cd0"].b, tw.c1, "relu", M=tw.B, mask=fw.relu_mask("c1", 64, rm), split=ns)
@@ -861,12 +863,8 @@ class PPO:
                 self._bwd_img(tw, L["cd1"], g_cd2i, tw.img("c1"))
                 chain = [dict(dZimg=g_reci, W=L["cd2"].W, dXimg=g_cd2i, mask=fw.relu_mask("c2", 128, rm)),
                          dict(dZimg=g_cd2i, W=L["cd1"].W, dXimg=g_cd1i, mask=fw.relu_mask("c1", 64, rm))]
-                if self.narrow_chains:
-                    h2i.linear_dgrad_chain(chain, wset=wset)
-                else:
-                    for c in chain:
-                        h2i.linear_dgrad(c["dZimg"], c["W"], None, c["dXimg"], mask=c.get("mask"), wset=wset)
-                self._bwd_img(tw, L["cd0"], g_cd1i, fw.img("lt"), wcol0=19)          # columns of dW that meet l_t ...
+                h2i.dgrad_layers(chain, self.narrow_chains, wset)
+                self._bwd_img(tw, L["cd0"], g_cd1i, fw.img("lt"), wcol0=19)         # columns of dW that meet l_t ...
                 self._bwd_img(tw, L["cd0"], g_cd1i, fw.cur["p_zmu"], wcol0=0, bias=False)      # ... and [z | mu[:, :3]]
                 # W's columns [19, 531) first (d l_t: four whole 128-column tiles, 16-byte stores), then [0, 19) (dz | d mu[:, :3] accumulating)
                 h2i.linear_dgrad(g_cd1i, L["cd0"].W, segmat([seg(tw.dlt, 0, 512), seg(tw.dz, 0, 16), seg(tw.dmulv, 0, 3, accumulate=True)]), None,
@@ -907,16 +905,13 @@ class PPO:
     def _ppo_step(self, fw, tw, flat, idx, eps, stats, cfg):
         """ppo.py:265-335: policy / value forward with the freshly updated VAE, PPO losses, backward,
         clip, Adam(adaptive lr).  Lanes: CE-net encoder + critic on `aux`, terrain encoder + actor on main."""
-        ac = self.actor_critic
-        L = ac.L
-        act = AC_Args.activation
         _ffi.lib().dtc_set_concurrency_hint(int(bool(self.overlap_wgrad)))     # weight gradients on the side stream
         early = self._run_phase("ppo", fw, tw, self._ppo_forward_backward, flat, idx, eps, stats, cfg)
         if not early:
             self._allreduce_grads(self.optimizer)
         self._lr_from_header(stats)
         if self.capture_grads:
-            self.captured["main"] = ac.arena.grad.clone()
+            self.captured["main"] = self.actor_critic.arena.grad.clone()
         self.optimizer.step(self.max_grad_norm, stats[S_GNORM:S_GNORM + 1])
 
     def _ppo_forward_backward(self, fw, tw, flat, idx, eps, stats, cfg, wset=None):
@@ -1049,12 +1044,8 @@ class PPO:
         """Data gradients of a body's tail 128 -> 256 -> 512 (actor_critic_decoder.py:323-349 backward): ONE launch -- the workgroup of a
         row tile runs the two column tiles of the 256-wide gradient, then the four of the 512-wide one (round 6; bit-identical) -- measured
         slower than a launch per layer (see modules/actor_critic_decoder.py: TAIL_CHAINS), so `tail_chains` is False."""
-        chain = [dict(dZimg=G3, W=L2.W, dXimg=g2i, Xsaved=x2, act=act), dict(dZimg=g2i, W=L1.W, dXimg=g1i, Xsaved=x1, act=act)]
-        if self.tail_chains:
-            h2i.linear_dgrad_chain(chain, wset=wset)
-        else:
-            for c in chain:
-                h2i.linear_dgrad(c["dZimg"], c["W"], None, c["dXimg"], Xsaved=c["Xsaved"], act=c["act"], wset=wset)
+        h2i.dgrad_layers([dict(dZimg=G3, W=L2.W, dXimg=g2i, Xsaved=x2, act=act), dict(dZimg=g2i, W=L1.W, dXimg=g1i, Xsaved=x1, act=act)],
+                         self.tail_chains, wset)
 
     def _adaptive(self):
         return self.desired_kl is not None and self.schedule == 'adaptive'
@@ -1071,11 +1062,11 @@ class PPO:
         B = idx.numel()
         flat = {k: st.flat(k) for k in self._FLAT_NAMES}
         fw, tw = ac._fwd_ws(B), self._train_ws(B)
-        self._set_ragged(fw, flat)
-        self._amax_static(flat, fw)
+        tw.schedule = self._resolve_schedule(fw, flat)
+        self._amax_static(flat, tw.schedule.whole)
         self.optimizer.set_lr(self.learning_rate)
         stats = torch.zeros(STAT_COLS, dtype=torch.float32, device=dev) if stats is None else stats.to(dev)
-        with self._gemm_passes_scope(fw), fw.slots.open():     # the packed rollout rows serve both optimisation steps of this call
+        with self._gemm_passes_scope(tw), fw.slots.open():     # the packed rollout rows serve both optimisation steps of this call
             try:
                 if which in ("vae", "both"):
                     self._vae_step(fw, tw, flat, idx, eps1.to(dev).contiguous(), stats)
@@ -1083,24 +1074,33 @@ class PPO:
                     self._ppo_step(fw, tw, flat, idx, eps2.to(dev).contiguous(), stats, self._loss_cfg())
             finally:
                 ops.amax_static_clear()
+        return self._read_back(stats, whole_update=False)[0], self.learning_rate
+
+    def _read_back(self, stats, whole_update=True):
+        """The single device -> host synchronisation of an update (or of a lone mini-batch): the statistics table and the adapted
+        learning rate come to the host.  Returns the host table and the 7-tuple of ppo.py:356-357, the means of its columns."""
+        host = stats.cpu()
         self.learning_rate = float(self.optimizer.lr_dev.item())
         for g in self.optimizer.param_groups:
             g['lr'] = self.learning_rate
-        return stats.cpu(), self.learning_rate
+        if whole_update:
+            self.last_update_stats = host
+        m = host.double().reshape(-1, STAT_COLS).mean(dim=0)
+        return host, (float(m[S_VALUE]), float(m[S_SURR]), 0.0, 0, float(m[S_RECONS]), float(m[S_VEL]), float(m[S_KLD]))
 
     _FLAT_NAMES = ("observations", "next_observations", "privileged_observations", "observation_histories", "actions",
                    "values", "advantages", "returns", "actions_log_prob", "mu", "sigma", "base_vel")
 
     _AMAX_STATIC = ("observations", "next_observations", "privileged_observations", "observation_histories", "base_vel")
 
-    def _amax_static(self, flat, fw=None, images=False):
+    def _amax_static(self, flat, whole=False, images=False):
         """Two-term fp16 GEMM path (ops.H2) on round 4's converting kernels: the rollout tensors that enter GEMMs as gathered operands bring
         the amax of the whole stored tensor -- they do not change during the update, so it is computed once here, before the compute lanes
-        fork.  The operand-image chain keeps no amax records at all: where the whole step runs on it (`fw` given and _image_mode(fw), with
-        the narrow layers on images too) the five passes over up to 546 MB are skipped (round 6: 0.33 ms per update).  `images`: the
-        caller's steps run on operand images; a tensor dtc_amax cannot address (2 GiB and more) is then left without a record, and a
-        kernel that asked for one after all would fail loudly on the tensor's size."""
-        if fw is not None and type(self)._ppo_step is PPO._ppo_step and self.narrow_images and self._image_mode(fw):
+        fork.  The operand-image chain keeps no amax records at all: where the whole step runs on it (`whole`: Schedule.whole) the five
+        passes over up to 546 MB are skipped (round 6: 0.33 ms per update).  `images`: the caller's steps run on operand images; a tensor
+        dtc_amax cannot address (2 GiB and more) is then left without a record, and a kernel that asked for one after all would fail
+        loudly on the tensor's size."""
+        if whole:
             ops.amax_static_clear()
             return
         if ops.SPLIT and ops.H2:
@@ -1141,16 +1141,16 @@ class PPO:
         perm = perm.to(dev).contiguous()
         flat = {k: st.flat(k) for k in self._FLAT_NAMES}
         fw, tw = ac._fwd_ws(B), self._train_ws(B)
-        self._set_ragged(fw, flat)
+        tw.schedule = self._resolve_schedule(fw, flat)
         if self.contain_nonfinite:
-            perm = self._contained_perm(fw, perm)
-        self._amax_static(flat, fw)
+            perm = self._contained_perm(tw, perm)
+        self._amax_static(flat, tw.schedule.whole)
         cfg = self._loss_cfg()
         self.optimizer.set_lr(self.learning_rate)
         stats = torch.zeros(steps, STAT_COLS, dtype=torch.float32, device=dev)
         lr_hist = torch.zeros(steps, dtype=torch.float64, device=dev) if return_stats else None
         k = 0
-        with self._gemm_passes_scope(fw), fw.slots.open():     # the packed rollout rows of a mini-batch serve all five epochs (packed_input)
+        with self._gemm_passes_scope(tw), fw.slots.open():     # the packed rollout rows of a mini-batch serve all five epochs (packed_input)
             try:
                 for _ in range(epochs):
                     for i in range(nmb):
@@ -1165,13 +1165,7 @@ class PPO:
                         k += 1
             finally:
                 ops.amax_static_clear()                # the storage is about to be refilled: its amax slots are void
-        # the single device -> host synchronisation of the update
-        host = stats.cpu()
-        self.learning_rate = float(self.optimizer.lr_dev.item())
-        for g in self.optimizer.param_groups:
-            g['lr'] = self.learning_rate
-        self.last_update_stats = host
-        m = host.double().mean(dim=0)
+        host, out = self._read_back(stats)
         if self.contain_nonfinite:
             # (behind the update's one synchronisation: every step has run, the two counts are plain reads)
             rows, valid, job = st.row_valid.numel(), int(st.valid_rows.item()), int(st._stats[1].item())
@@ -1182,7 +1176,6 @@ class PPO:
                                     "on a rank or fewer than two in the job nothing can be contained: the advantage statistics and "
                                     "this update's weights are not finite")
         st.clear()
-        out = (float(m[S_VALUE]), float(m[S_SURR]), 0.0, 0, float(m[S_RECONS]), float(m[S_VEL]), float(m[S_KLD]))
         if return_stats:
             return out, host, lr_hist.cpu()
         return out

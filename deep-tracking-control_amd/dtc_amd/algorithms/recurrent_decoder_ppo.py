@@ -29,13 +29,14 @@ from .._ffi import seg, segmat
 from ..modules.actor_critic_decoder import Dense
 from ..modules.actor_critic_decoder_recurrent import ActorCriticDecoderRecurrent
 from ..utils import split_and_pad_trajectories, true_indices
-from .ppo import PPO, S_GNORM, S_KL, S_RECONS, S_SURR, S_VALUE, S_VEL, S_KLD, STAT_COLS
+from .ppo import PPO, S_GNORM, S_SURR, STAT_COLS, Schedule
 from .recurrent_heads import GruHead, forward_backward
 from .recurrent_ppo import _share_rule
 
 
 class RecurrentDecoderPPO(PPO):
     actor_critic: ActorCriticDecoderRecurrent
+    row_sets = False                 # the mini-batches of update() are trajectories (recurrent_slices)
     # DTC_GRU_MULTI=1: the actor's and the critic's recurrence advance together, one launch per time step (dtc_gru_fwd_multi /
     # dtc_gru_bwd_multi; bit-identical).  Off: measured 136 vs 129 ms per step against one chain of launches per recurrence, each on
     # its own lane
@@ -106,9 +107,9 @@ class RecurrentDecoderPPO(PPO):
             first = last
 
     # ---------------------------------------------------------------- policy step with BPTT
-    def _image_mode(self, fw):
+    def _image_mode(self, fw, ragged=False):
         """The recurrent schedules (padded [T, R] layout, GRU time steps on images) are built for whole 128-row tiles: no ragged form."""
-        return fw.B % 128 == 0 and super()._image_mode(fw)
+        return fw.B % 128 == 0 and super()._image_mode(fw, False)
 
     def _memory_images(self):
         """The operand-image schedule of the policy step is built for 1-layer GRU memories with H % 128 == 0."""
@@ -116,15 +117,15 @@ class RecurrentDecoderPPO(PPO):
         return (all(m.kind == 'gru' and m.num_layers == 1 for m in (ac.memory_a, ac.memory_c)) and ac.rnn_hidden_size % 128 == 0)
 
     def _ppo_step_recurrent(self, fw, tw, flat, bt, eps, stats, cfg):
-        if self._image_mode(fw) and self._memory_images():
+        sched = tw.schedule
+        if sched.images and self._memory_images():
             # every GEMM outside the GRU time steps on operand images (dtc_amd/h2i.py), as in PPO._ppo_step
-            tw.narrow_wgrad = True
-            wset = self._wset("ppo_recurrent")
-            wset.rebuild()
-            early = self._ppo_recurrent_forward_backward_images(fw, tw, flat, bt, eps, stats, cfg, wset)
+            early = self._run_phase("ppo_recurrent", fw, tw, self._ppo_recurrent_forward_backward_images, flat, bt, eps, stats, cfg)
         else:
+            tw.schedule = Schedule()                               # this phase alone runs on the converting kernels, whatever the VAE step ran on
             with self._images("ppo_recurrent"):                    # weight images of the step's split-path layers: one launch
                 early = self._ppo_recurrent_forward_backward(fw, tw, flat, bt, eps, stats, cfg)
+            tw.schedule = sched
         if not early:
             self._allreduce_grads(self.optimizer)
         self._lr_from_header(stats)
@@ -307,8 +308,9 @@ class RecurrentDecoderPPO(PPO):
         flat = {k: st.flat(k) for k in self._FLAT_NAMES}
         fw, tw = ac._fwd_ws(B), self._train_ws(B)
         own_gen = fw.slots.gen is None                # outside update(): the packed rollout rows serve this call only
-        if own_gen:
-            self._amax_static(flat, images=self._image_mode(fw) and self._memory_images())      # (inside update(): once per update -- the storage does not change between mini-batches)
+        if own_gen:      # (inside update(): once per update -- the knobs and the storage do not change between mini-batches)
+            tw.schedule = self._resolve_schedule(fw, flat)
+            self._amax_static(flat, images=tw.schedule.images and self._memory_images())
         with fw.slots.open() if own_gen else contextlib.nullcontext():
             if own_gen:
                 # (inside update() the device-side learning rate carries the adaptive schedule from mini-batch to mini-batch, ppo.py:301-307:
@@ -338,14 +340,17 @@ class RecurrentDecoderPPO(PPO):
             eps1 = ops.randn((steps, B, 16), dev, seed + 1) if eps1 is None else eps1
             eps2 = ops.randn((steps, B, 16), dev, seed + 2) if eps2 is None else eps2
         stats = torch.zeros(steps, STAT_COLS, dtype=torch.float32, device=dev)
-        self._train_ws(B).pad.zero("gi_")             # padded input projections: the padding slots start every update from zero
+        tw = self._train_ws(B)
+        tw.pad.zero("gi_")                            # padded input projections: the padding slots start every update from zero
         slices = list(self.recurrent_slices())
         k = 0
         fw = ac._fwd_ws(B)
         self.optimizer.set_lr(self.learning_rate)      # once per update: the schedule then lives on the device (lr_dev)
         # amax records of the stored rollout tensors ONCE per update (they were recomputed by every mini-batch: 100 passes over up to
         # 546 MB = 6.5 ms of a 133 ms step)
-        self._amax_static({k: st.flat(k) for k in self._FLAT_NAMES}, images=self._image_mode(fw) and self._memory_images())
+        flat = {k: st.flat(k) for k in self._FLAT_NAMES}
+        tw.schedule = self._resolve_schedule(fw, flat)
+        self._amax_static(flat, images=tw.schedule.images and self._memory_images())
         with fw.slots.open():                    # the slices are the same in every epoch: their packed rollout rows serve all five
             try:
                 for _ in range(epochs):
@@ -355,13 +360,7 @@ class RecurrentDecoderPPO(PPO):
                         k += 1
             finally:
                 ops.amax_static_clear()          # the storage is about to be refilled: its amax slots are void
-        host = stats.cpu()                       # the single device -> host synchronisation of the update
+        host, out = self._read_back(stats)
         ops.gru_seq_check()                      # (the persistent recurrence launches of this update all ran to their end)
-        self.learning_rate = float(self.optimizer.lr_dev.item())
-        for g in self.optimizer.param_groups:
-            g['lr'] = self.learning_rate
-        self.last_update_stats = host
-        m = host.double().mean(dim=0)
         st.clear()
-        out = (float(m[S_VALUE]), float(m[S_SURR]), 0.0, 0, float(m[S_RECONS]), float(m[S_VEL]), float(m[S_KLD]))
         return (out, host) if return_stats else out

@@ -278,16 +278,33 @@ def linear_fwd(X, W, b, Y=None, Yimg=None, act=None, mask=None, wset=None, cols=
     return ws
 
 
+def fwd_layers(layers, chain, wset=None):
+    """`layers` (dicts with the keyword arguments of linear_fwd) as ONE launch (`chain`: linear_fwd_chain) or as a launch per layer, in
+    order: the same bits either way.  Returns the weight set the launches used (`wset`, or the one the first layer made)."""
+    if chain:
+        return linear_fwd_chain(layers, wset=wset)
+    for L in layers:
+        wset = linear_fwd(L["X"], L["W"], L.get("b"), L.get("Y"), L.get("Yimg"), L.get("act"), L.get("mask"), wset, L.get("cols"))
+    return wset
+
+
+def dgrad_layers(layers, chain, wset=None):
+    """fwd_layers for data gradients: `layers` (dicts with the arguments of linear_dgrad) as linear_dgrad_chain or a launch per layer."""
+    if chain:
+        return linear_dgrad_chain(layers, wset=wset)
+    for L in layers:
+        wset = linear_dgrad(L["dZimg"], L["W"], L.get("dX"), L.get("dXimg"), L.get("window"), L.get("add"), L.get("Xsaved"), L.get("act"),
+                            L.get("mask"), wset)
+    return wset
+
+
 def linear_fwd_chain(layers, wset=None):
     """Up to three forward layers of at most 512 output columns each (round 6: several column tiles per layer, run one after the other by the
     row tile's workgroup) in ONE launch (dtc_linear_fwd_chain_h2i): `layers` = list of dicts
     with the keyword arguments of linear_fwd (X, W, b, Y, Yimg, act, mask, cols); layer i + 1's X must be layer i's Yimg.  Bit for bit
     the per-layer calls.  (A capture in flight takes the per-layer calls: it checks every product on its own.)"""
     if CAPTURE is not None or len(layers) == 1:
-        ws = wset
-        for L in layers:
-            ws = linear_fwd(L["X"], L["W"], L.get("b"), L.get("Y"), L.get("Yimg"), L.get("act"), L.get("mask"), ws if ws is not None else wset, L.get("cols"))
-        return ws
+        return fwd_layers(layers, False, wset)
     arr = (_ffi.DtcH2iFwdLayer * len(layers))()
     keep, ws = [], wset
     M = None
@@ -310,11 +327,7 @@ def linear_dgrad_chain(layers, wset=None):
     list of dicts with the arguments of linear_dgrad (dZimg, W, dX, dXimg, window (one range), add, Xsaved, act, mask); layer i + 1's
     dZimg must be layer i's dXimg.  Bit for bit the per-layer calls."""
     if CAPTURE is not None or len(layers) == 1:
-        ws = wset
-        for L in layers:
-            ws = linear_dgrad(L["dZimg"], L["W"], L.get("dX"), L.get("dXimg"), L.get("window"), L.get("add"), L.get("Xsaved"), L.get("act"),
-                              L.get("mask"), ws if ws is not None else wset)
-        return ws
+        return dgrad_layers(layers, False, wset)
     arr = (_ffi.DtcH2iDgradLayer * len(layers))()
     keep = []
     ws = wset if wset is not None else WeightSet()

@@ -292,7 +292,7 @@ class ActorCriticDecoder(nn.Module):
         def __init__(self, B, dev, num_actions):
             e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
             self.B = B
-            self.ragged = False              # set by the trainer: this step runs on operand images although B % 128 != 0 (images_ok)
+            self.ragged = False              # set by PPO._resolve_schedule alone: this update runs on operand images although B % 128 != 0
             self.e1, self.e, self.mulv, self.z = e(B, 128), e(B, 64), e(B, 35), e(B, 16)
             self.mask = torch.empty(B, 16, dtype=torch.uint8, device=dev)
             self.info = torch.zeros(4, dtype=torch.int32, device=dev)
@@ -377,11 +377,7 @@ class ActorCriticDecoder(nn.Module):
             e1i, ei = ws.img("e1", L["ce0"].n_out), ws.img("e", L["ce1"].n_out)
             chain = [dict(X=pin, W=L["ce0"].W, b=L["ce0"].b, Yimg=e1i, act="relu", mask=ws.relu_mask("e1", L["ce0"].n_out, masks)),
                      dict(X=e1i, W=L["ce1"].W, b=L["ce1"].b, Yimg=ei), dict(X=ei, W=L["head"].W, b=L["head"].b, Y=ws.mulv)]
-            if NARROW_CHAINS:          # the three layers as ONE launch (h2i.linear_fwd_chain; DTC_H2I_CHAIN=0: a launch per layer)
-                h2i.linear_fwd_chain(chain, wset=wset)
-            else:
-                for c in chain:
-                    h2i.linear_fwd(c["X"], c["W"], c["b"], c.get("Y"), c.get("Yimg"), c.get("act"), mask=c.get("mask"), wset=wset)
+            h2i.fwd_layers(chain, NARROW_CHAINS, wset)     # the three layers as ONE launch (DTC_H2I_CHAIN=0: a launch per layer)
             ws.live_img |= {"e1", "e"}
         else:
             ws.live_img -= {"e1", "e"}
@@ -463,13 +459,10 @@ class ActorCriticDecoder(nn.Module):
             h2i.linear_fwd(X, l0.W, l0.b, o0, i0, act, wset=wset, cols=cols)
             # (last_img: the third activation as an image as well -- the X operand of the output layer's image-operand weight gradient)
             i2 = ws.img(outs[2], l2.n_out) if last_img else None
-            if TAIL_CHAINS:        # the tail 512 -> 256 -> 128 as ONE launch: a row tile's workgroup runs both column tiles of the 256-wide
-                                   # layer, then the 128-wide one (round 6; bit for bit the two launches)
-                h2i.linear_fwd_chain([dict(X=i0, W=l1.W, b=l1.b, Y=o1, Yimg=i1, act=act), dict(X=i1, W=l2.W, b=l2.b, Y=o2, Yimg=i2, act=act)],
-                                     wset=wset)
-            else:
-                h2i.linear_fwd(i0, l1.W, l1.b, o1, i1, act, wset=wset)
-                h2i.linear_fwd(i1, l2.W, l2.b, o2, i2, act, wset=wset)
+            # TAIL_CHAINS: the tail 512 -> 256 -> 128 as ONE launch: a row tile's workgroup runs both column tiles of the 256-wide layer,
+            # then the 128-wide one (round 6; bit for bit the two launches)
+            h2i.fwd_layers([dict(X=i0, W=l1.W, b=l1.b, Y=o1, Yimg=i1, act=act), dict(X=i1, W=l2.W, b=l2.b, Y=o2, Yimg=i2, act=act)],
+                           TAIL_CHAINS, wset)
             return
         ops.linear_fwd(X, l0.W, l0.b, o0, act, M=ws.B)
         ops.linear_fwd(o0, l1.W, l1.b, o1, act)

@@ -204,7 +204,145 @@ def test_a_diverged_env_stays_in_its_row_at_a_ragged_row_count():
         assert bool(torch.isfinite(c).all()) and not bool(torch.isfinite(d[119]).all()), name
 
 
+@pytest.mark.gpu
+def test_two_trainers_on_one_model_each_get_their_own_schedule():
+    """a default PPO and a PPO(ragged_images=True) on ONE model (one forward workspace per row count), 20 envs (120 rows), their
+    step_minibatch calls alternating twice: after each call the workspace's `ragged` mark and live images are that trainer's (the
+    assertions of test_default_is_untouched and test_the_ragged_update_runs_on_images_only), and the other trainer's _image_mode query
+    in between changes nothing"""
+    from dtc_amd.algorithms import PPO
+    _, plain = _pair(20, oracle=False)
+    ac = plain.actor_critic
+    ragged = PPO(ac, learning_rate=1e-3, entropy_coef=0.003, device=DEV, ragged_images=True)
+    ragged.init_storage(20, 24, [53], [1389], [265], [12])
+    d = S.rollout(20, 24, seed=4)
+    for k, v in d.items():
+        if k != "last_values":
+            getattr(ragged.storage, k).copy_(v.to(DEV))
+    ragged.storage.compute_returns(d["last_values"].to(DEV), 0.99, 0.95)
+    perm, e1, e2 = S.update_noise(20, 24, 4, 5, seed=123)
+    fw = ac._fwd_ws(120)
+    for k in range(2):
+        row, _ = plain.step_minibatch(perm[:120], e1[k], e2[k])
+        assert bool(torch.isfinite(row).all())
+        assert not fw.ragged and not plain._image_mode(fw) and fw.relu_mask("t1", 512) is None and not fw.live_img
+        asked = ragged._image_mode(fw)
+        assert bool(asked) == (k == 1)                  # its own last schedule at 120 rows (none before its first step), not the mark
+        assert not fw.ragged and fw.relu_mask("t1", 512) is None and not fw.live_img
+        row, _ = ragged.step_minibatch(perm[:120], e1[k], e2[k])
+        assert bool(torch.isfinite(row).all())
+        assert fw.ragged and ragged._image_mode(fw) and {"t1", "t2"} <= fw.live_img
+        live = set(fw.live_img)
+        assert not plain._image_mode(fw)
+        assert fw.ragged and fw.live_img == live and fw.relu_mask("t1", 512) is not None
+
+
 # ------------------------------------------------------------------------------------------------ host side: no GPU
+class _StandInWs:
+    """what PPO._image_mode / PPO._resolve_schedule read of a forward workspace (test_images_ok_and_the_workspace_rule's stand-in,
+    with the mark)"""
+
+    def __init__(self, B, ragged=False):
+        self.B, self.ragged = B, ragged
+
+
+_SWITCHES = ("use_images", "narrow_images", "relu_masks", "group_wgrad", "fuse_height_loss")
+
+
+def _rollouts():
+    """a small rollout tensor, and test_images_ok_and_the_workspace_rule's 2 GiB one (no storage behind it)"""
+    from dtc_amd import _ffi
+    big = dict(privileged_observations=torch.empty_strided((400000, 1389), (1389, 1), device="meta"))
+    assert 400000 * 1389 > _ffi.MAX_OPERAND_ELEMS
+    return dict(observations=torch.empty(480, 53)), big
+
+
+def test_image_mode_is_a_pure_query():
+    """a default trainer asked about a workspace another trainer left marked ragged: the mark stays, nothing else appears on the
+    workspace, and the answer is the default trainer's own (whole tiles only)"""
+    from dtc_amd import ops
+    from dtc_amd.algorithms import PPO
+    from dtc_amd.modules import ActorCriticDecoder
+    plain = PPO(ActorCriticDecoder(53, 1389, 12), device="cpu")
+    for B in (120, 384, 600):
+        ws = _StandInWs(B, ragged=True)
+        got = plain._image_mode(ws)
+        assert ws.ragged is True and vars(ws) == dict(B=B, ragged=True)
+        assert got is (bool(ops.SPLIT) and B % 128 == 0)
+
+
+def test_the_resolver_truth_table():
+    """PPO._resolve_schedule over 120 / 384 / 600 rows x the trainer keywords x a small and a 2 GiB rollout x each switch of the image
+    schedule off in turn: `whole` needs every switch, `images` every one but narrow_images, `ragged` a ragged row count + the flag or
+    the 2 GiB tensor + `whole`; `passes` is gemm_passes; the resolver (and nothing else) marks the workspace.  ops.SPLIT as it stands."""
+    from dtc_amd import ops
+    from dtc_amd.algorithms import PPO, RecurrentDecoderPPO
+    from dtc_amd.algorithms.ppo import Schedule
+    from dtc_amd.modules import ActorCriticDecoder
+    ac = ActorCriticDecoder(53, 1389, 12)
+    small, big = _rollouts()
+    split = bool(ops.SPLIT)
+    seen = set()
+    for kw in (dict(), dict(ragged_images=True), dict(gemm_passes=1), dict(gemm_passes=1, ragged_images=True)):
+        alg = PPO(ac, device="cpu", **kw)
+        for off in (None,) + _SWITCHES:
+            for name in _SWITCHES:
+                setattr(alg, name, name != off)
+            for B in (120, 384, 600):
+                for flat in (small, big):
+                    ws = _StandInWs(B, ragged=B == 384)                      # a stale mark either way
+                    got = alg._resolve_schedule(ws, flat)
+                    ragged = split and off is None and B % 128 != 0 and (alg.ragged_images or flat is big)
+                    images = split and off in (None, "narrow_images") and (B % 128 == 0 or ragged)
+                    want = Schedule(images=images, whole=images and off is None, ragged=ragged, passes=kw.get("gemm_passes", 3))
+                    assert got == want and all(type(v) is bool for v in got[:3]), (kw, off, B, flat is big, got, want)
+                    assert ws.ragged is ragged and vars(ws) == dict(B=B, ragged=ragged)
+                    assert alg._wants_ragged(B, flat) == (B % 128 != 0 and (alg.ragged_images or flat is big))
+                    seen.add(got)
+    if split:
+        assert {(s.images, s.whole, s.ragged) for s in seen} == {(False, False, False), (True, False, False), (True, True, False), (True, True, True)}
+    # the trajectory trainer: whole tiles only, never `whole`, never ragged -- not even for the 2 GiB tensor
+    rec = RecurrentDecoderPPO(ac, device="cpu")
+    assert rec.row_sets is False and PPO.row_sets is True
+    for B in (120, 384, 600):
+        ws = _StandInWs(B, ragged=True)
+        assert rec._resolve_schedule(ws, big) == Schedule(images=split and B == 384, whole=False, ragged=False, passes=3)
+        assert ws.ragged is False and rec._image_mode(ws) is (split and B == 384)
+
+
+def test_both_opt_ins_are_refused_by_one_helper_with_one_text():
+    """gemm_passes=1 and contain_nonfinite=True on a schedule that is not `whole` (120 rows, no ragged_images): DtcError out of
+    PPO._needs_whole_step, the message names the opt-in, the row count, ops.SPLIT and every switch; containment adds its sentence about
+    whole-tensor amax.  On a `whole` schedule the helper lets both through."""
+    from dtc_amd import _ffi, ops
+    from dtc_amd.algorithms import PPO
+    from dtc_amd.algorithms.ppo import Schedule
+    from dtc_amd.modules import ActorCriticDecoder
+    ac = ActorCriticDecoder(53, 1389, 12)
+    small, _ = _rollouts()
+
+    class _Tw:
+        B = 120
+    msgs = {}
+    for what, kw, call in (("gemm_passes=1", dict(gemm_passes=1), lambda alg, tw: alg._gemm_passes_scope(tw)),
+                           ("contain_nonfinite=True", dict(contain_nonfinite=True), lambda alg, tw: alg._contained_perm(tw, torch.arange(480)))):
+        alg, tw = PPO(ac, device="cpu", **kw), _Tw()
+        tw.schedule = alg._resolve_schedule(_StandInWs(120), small)
+        assert not tw.schedule.whole and tw.schedule.passes == kw.get("gemm_passes", 3)
+        with pytest.raises(_ffi.DtcError) as e:
+            call(alg, tw)
+        assert e.traceback[-1].name == "_needs_whole_step"
+        msg = msgs[what] = str(e.value)
+        assert msg.startswith(f"{what} needs the operand-image schedule for the whole step") and "(this one: 120)" in msg
+        assert f"ops.SPLIT = {ops.SPLIT}" in msg and "multiple of 128 rows" in msg
+        assert all(name in msg for name in _SWITCHES + ("ragged_images=True",))
+        tw.schedule = Schedule(True, True, True, tw.schedule.passes)
+        PPO._needs_whole_step(tw, what)
+    assert msgs["contain_nonfinite=True"].endswith("every other schedule reads whole rollout tensors (amax)")
+    assert "amax" not in msgs["gemm_passes=1"]
+    assert msgs["contain_nonfinite=True"].split(" needs ", 1)[1].startswith(msgs["gemm_passes=1"].split(" needs ", 1)[1])
+
+
 def test_relu_mask_ok_no_longer_tests_the_row_count():
     from dtc_amd import ops
     for M in (1, 48, 120, 128, 600, 24576):
