@@ -178,6 +178,12 @@ class DtcRowCopy(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("src_stride_bytes", C.c_int64), ("width_bytes", C.c_int32)]
 
 
+class DtcEnvColumn(C.Structure):
+    """include/dtc_hip.h: one per-env buffer of the storage for dtc_env_columns_repair (rows (o, n) at base + o * outer_stride + n * env_stride)."""
+    _fields_ = [("base", C.c_void_p), ("outer", C.c_int64), ("outer_stride_bytes", C.c_int64), ("env_stride_bytes", C.c_int64),
+                ("width_bytes", C.c_int32)]
+
+
 class DtcProfRec(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("ms_total", C.c_double), ("work", C.c_double),
                 ("launches", C.c_int64), ("bytes", C.c_double)]
@@ -186,7 +192,7 @@ class DtcProfRec(C.Structure):
 ACT = {None: 0, "none": 0, "relu": 1, "crelu": 1, "elu": 2, "selu": 3, "lrelu": 4, "tanh": 5, "sigmoid": 6}
 MAX_OPERAND_ELEMS = (1 << 29) - 1
 
-ABI_VERSION = 19        # DTC_ABI_VERSION of include/dtc_hip.h this binding was written against
+ABI_VERSION = 20        # DTC_ABI_VERSION of include/dtc_hip.h this binding was written against
 
 _SIGS = {
     "dtc_version": (C.c_int, []),
@@ -228,6 +234,11 @@ _SIGS = {
     "dtc_compact_workspace": (C.c_int64, [C.c_int64]),
     "dtc_compact_valid": (C.c_int, [c_u8p, C.c_int64, c_i64p, c_i64p, C.c_void_p, c_stream]),
     "dtc_perm_repair": (C.c_int, [c_i64p, C.c_int64, c_u8p, C.c_int64, c_i64p, c_i64p, c_i64p, c_stream]),
+    "dtc_states_finite": (C.c_int, [c_f32p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, c_u8p, c_stream]),
+    "dtc_env_fold": (C.c_int, [c_u8p, C.c_int64, C.c_int64, c_u8p, c_stream]),
+    "dtc_env_columns_cap": (C.c_int, []),
+    "dtc_env_columns_repair": (C.c_int, [C.POINTER(DtcEnvColumn), C.c_int, c_u8p, c_i64p, C.c_int64, c_stream]),
+    "dtc_contain_envs_abi_sizes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
     "dtc_gather_rows": (C.c_int, [C.c_void_p, c_i64p, C.c_void_p, C.c_int64, C.c_int64, c_stream]),
     "dtc_scatter_rows": (C.c_int, [c_f32p, c_i64p, c_f32p, C.c_int64, C.c_int64, c_stream]),
     "dtc_pack_cols": (C.c_int, [C.POINTER(DtcSegMat), c_f32p, C.c_int64, C.c_int64, C.c_void_p, c_stream]),
@@ -404,6 +415,9 @@ def _check_abi(l):
     theirs = list(sizes[:n])
     mine += [DtcResetRows, DtcResetCfg, DtcResetStep]                     # reported by the reset entry points' own table
     n = l.dtc_env_reset_abi_sizes(sizes, 32)
+    theirs += list(sizes[:n])
+    mine += [DtcEnvColumn]                                                # ... and by the env containment's
+    n = l.dtc_contain_envs_abi_sizes(sizes, 32)
     theirs += list(sizes[:n])
     if l.dtc_version() != ABI_VERSION or theirs != [C.sizeof(t) for t in mine]:
         _lib = None

@@ -319,6 +319,26 @@ class _TrainWorkspace(_StepWorkspace):
                                          lib.dtc_linear_fwd_mse_h2i_parts(B, 693))), dtype=torch.float64, device=dev)
 
 
+def require_env_record(alg):
+    """contain_nonfinite_envs, in front of an update() of any trainer: the storage must hold the env record of THIS rollout."""
+    st = alg.storage
+    if not (st.contain_nonfinite_envs and st.env_record_fresh and st.env_valid is not None):
+        raise _ffi.DtcError("contain_nonfinite_envs=True: the storage holds no env record of this rollout (compute_returns makes it, "
+                            "storage.clear() voids it) -- call compute_returns after the rollout and before update()")
+
+
+def read_env_record(alg):
+    """contain_nonfinite_envs, behind an update()'s one synchronisation (every step has run: the count is a plain read): this rank's
+    repaired envs of the update -> alg.last_nonfinite_envs.  No valid env on this rank: nothing could be repaired from nothing."""
+    st = alg.storage
+    envs, valid = st.env_valid.numel(), int(st.n_valid_envs.item())
+    alg.last_nonfinite_envs = envs - valid
+    if valid < 1:
+        st.clear()
+        raise _ffi.DtcError(f"contain_nonfinite_envs: {valid} valid envs of {envs} on this rank -- with none on a rank nothing can be "
+                            "repaired: the advantage statistics and this update's weights are not finite")
+
+
 class PPO:
     actor_critic: ActorCriticDecoder
     # The mini-batches of update() are row sets of the stored rollout, each run by _vae_step / _ppo_step.  False (RecurrentDecoderPPO):
@@ -328,8 +348,16 @@ class PPO:
     def __init__(self, actor_critic, num_learning_epochs=5, num_mini_batches=4, clip_param=0.2, gamma=0.99, lam=0.95,
                  value_loss_coef=1.0, entropy_coef=0.01, learning_rate=5.e-4, max_grad_norm=1.0,
                  use_clipped_value_loss=True, schedule="adaptive", desired_kl=0.01, device='cpu', *, gemm_passes=3, ragged_images=False,
-                 contain_nonfinite=False):
+                 contain_nonfinite=False, contain_nonfinite_envs=False):
         self.device = device
+        # Envs of the stored rollout that hold anything non-finite are overwritten IN THE STORAGE by valid envs before the update reads it
+        # (opt-in; RolloutStorage._repair_nonfinite_envs, run by compute_returns): update() then is the default update, on any schedule,
+        # any memory type, any row count -- the form of containment the trajectory mini-batches of the recurrent trainers can take.
+        # `last_nonfinite_envs`: this rank's repaired envs of the last update.  False (default): nothing is added.
+        self.contain_nonfinite_envs = bool(contain_nonfinite_envs)
+        self.last_nonfinite_envs = 0
+        if contain_nonfinite and self.contain_nonfinite_envs:
+            raise ValueError("contain_nonfinite and contain_nonfinite_envs: one unit of containment at a time (rows of the update, or envs of the storage)")
         # Rows of the stored rollout with a non-finite element stay out of the update (opt-in): compute_returns takes the advantage
         # statistics over the valid rows only and leaves a validity record (RolloutStorage), update() repairs its permutation so that
         # it names valid rows only -- and reads the rollout through that permutation alone, which holds on the operand-image schedule
@@ -337,7 +365,8 @@ class PPO:
         self.contain_nonfinite = bool(contain_nonfinite)
         self.last_nonfinite_rows = 0
         if self.contain_nonfinite and not self.row_sets:
-            raise TypeError(f"{type(self).__name__} has no contain_nonfinite: the mini-batches of its update() are trajectories, not row sets")
+            raise TypeError(f"{type(self).__name__} has no contain_nonfinite: the mini-batches of its update() are trajectories, not row sets "
+                            "(contain_nonfinite_envs=True contains whole envs in the storage instead)")
         # MFMA passes per product of the update's operand-image schedule (h2i.set_h2i_passes): 3 = two-term fp16 operands, the arithmetic
         # of the 1e-5 contract; 1 (opt-in) = their hi planes alone.  The rollout side (act / evaluate / compute_returns) does not follow it.
         if gemm_passes not in (1, 3):
@@ -450,6 +479,8 @@ class PPO:
                                       obs_history_shape, action_shape, self.device)
         if self.contain_nonfinite:
             self.storage.contain_nonfinite = True
+        if self.contain_nonfinite_envs:
+            self.storage.contain_nonfinite_envs = True
 
     def test_mode(self):
         self.actor_critic.eval()
@@ -1128,6 +1159,8 @@ class PPO:
         so that parity tests can feed both implementations the same numbers."""
         self._require_gpu()
         st, ac = self.storage, self.actor_critic
+        if self.contain_nonfinite_envs:
+            require_env_record(self)
         self._arena()
         dev = ac.std.device
         nmb, epochs = self.num_mini_batches, self.num_learning_epochs
@@ -1175,6 +1208,8 @@ class PPO:
                 raise _ffi.DtcError(f"contain_nonfinite: {valid} valid rows of {rows} on this rank, {job} valid rows in the job -- with none "
                                     "on a rank or fewer than two in the job nothing can be contained: the advantage statistics and "
                                     "this update's weights are not finite")
+        if self.contain_nonfinite_envs:
+            read_env_record(self)
         st.clear()
         if return_stats:
             return out, host, lr_hist.cpu()

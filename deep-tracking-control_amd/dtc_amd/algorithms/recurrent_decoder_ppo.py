@@ -29,7 +29,7 @@ from .._ffi import seg, segmat
 from ..modules.actor_critic_decoder import Dense
 from ..modules.actor_critic_decoder_recurrent import ActorCriticDecoderRecurrent
 from ..utils import split_and_pad_trajectories, true_indices
-from .ppo import PPO, S_GNORM, S_SURR, STAT_COLS, Schedule
+from .ppo import PPO, S_GNORM, S_SURR, STAT_COLS, Schedule, read_env_record, require_env_record
 from .recurrent_heads import GruHead, forward_backward
 from .recurrent_ppo import _share_rule
 
@@ -330,6 +330,8 @@ class RecurrentDecoderPPO(PPO):
         self._require_gpu()
         _share_rule()
         st, ac = self.storage, self.actor_critic
+        if self.contain_nonfinite_envs:
+            require_env_record(self)
         self._arena()
         dev = ac.std.device
         nmb, epochs = self.num_mini_batches, self.num_learning_epochs
@@ -362,5 +364,7 @@ class RecurrentDecoderPPO(PPO):
                 ops.amax_static_clear()          # the storage is about to be refilled: its amax slots are void
         host, out = self._read_back(stats)
         ops.gru_seq_check()                      # (the persistent recurrence launches of this update all ran to their end)
+        if self.contain_nonfinite_envs:
+            read_env_record(self)
         st.clear()
         return (out, host) if return_stats else out

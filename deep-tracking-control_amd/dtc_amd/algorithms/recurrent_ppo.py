@@ -23,7 +23,7 @@ from ..storage import RolloutStorage
 from ..utils import UpdateSlots, true_indices
 import os
 
-from .ppo import FusedAdam, S_ENTROPY, S_GNORM, S_KL, S_SURR, S_VALUE, STAT_COLS, _StepWorkspace
+from .ppo import FusedAdam, S_ENTROPY, S_GNORM, S_KL, S_SURR, S_VALUE, STAT_COLS, _StepWorkspace, read_env_record, require_env_record
 from .recurrent_heads import GruHead, forward_backward
 
 
@@ -40,8 +40,11 @@ class RecurrentPPO:
 
     def __init__(self, actor_critic, num_learning_epochs=5, num_mini_batches=4, clip_param=0.2, gamma=0.99, lam=0.95,
                  value_loss_coef=1.0, entropy_coef=0.01, learning_rate=5.e-4, max_grad_norm=1.0,
-                 use_clipped_value_loss=True, schedule="adaptive", desired_kl=0.01, device='cpu'):
+                 use_clipped_value_loss=True, schedule="adaptive", desired_kl=0.01, device='cpu', *, contain_nonfinite_envs=False):
         self.device = device
+        # PPO's keyword of the same name: envs that hold anything non-finite are overwritten in the storage by valid ones before update()
+        self.contain_nonfinite_envs = bool(contain_nonfinite_envs)
+        self.last_nonfinite_envs = 0
         self.desired_kl, self.schedule, self.learning_rate = desired_kl, schedule, learning_rate
         self.actor_critic = actor_critic
         self.actor_critic.to(self.device)
@@ -82,6 +85,8 @@ class RecurrentPPO:
     def init_storage(self, num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape):
         self.storage = RolloutStorage(num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, [1],
                                       action_shape, self.device)
+        if self.contain_nonfinite_envs:
+            self.storage.contain_nonfinite_envs = True
 
     def test_mode(self):
         self.actor_critic.eval()
@@ -338,6 +343,8 @@ class RecurrentPPO:
         self._require_gpu()
         _share_rule()
         st = self.storage
+        if self.contain_nonfinite_envs:
+            require_env_record(self)
         nmb, epochs = self.num_mini_batches, self.num_learning_epochs
         mb = st.num_envs // nmb
         dev = self.actor_critic.std.device
@@ -359,5 +366,7 @@ class RecurrentPPO:
         self.learning_rate = float(self.optimizer.lr_dev.item())
         self.last_update_stats = host
         m = host.double().mean(dim=0)
+        if self.contain_nonfinite_envs:
+            read_env_record(self)
         st.clear()
         return float(m[S_VALUE]), float(m[S_SURR])

@@ -91,13 +91,71 @@ def compact_valid(row_valid, valid_list=None, n_valid=None, ws=None):
     return valid_list, n_valid
 
 
-def perm_repair(perm, row_valid, valid_list, n_valid) -> torch.Tensor:
+def perm_repair(perm, row_valid, valid_list, n_valid, out: torch.Tensor | None = None) -> torch.Tensor:
     """int64 [len(perm)]: perm[j] where that row is valid, valid_list[perm[j] % n_valid] otherwise."""
-    out = torch.empty_like(perm)
+    out = torch.empty_like(perm) if out is None else out
+    if out.shape != perm.shape:
+        raise _ffi.DtcError(f"perm_repair: out is int64 {tuple(perm.shape)}, got {tuple(out.shape)}")
     check(lib().dtc_perm_repair(cptr(perm, torch.int64), perm.numel(), cptr(row_valid, torch.uint8), row_valid.numel(),
                                 cptr(valid_list, torch.int64), cptr(n_valid, torch.int64), cptr(out, torch.int64), stream()),
           "dtc_perm_repair")
     return out
+
+
+# containment of non-finite rollout envs (csrc/contain_envs.hip)
+def states_finite(states: torch.Tensor, row_valid: torch.Tensor) -> torch.Tensor:
+    """row_valid (uint8 [T * N]) &= every layer's state of env n at step t is finite, for one saved-state tensor fp32 [T, L, N, H]."""
+    if states.dim() != 4:
+        raise _ffi.DtcError(f"states_finite: the saved states are [T, L, N, H], got {tuple(states.shape)}")
+    T, L, N, H = states.shape
+    if row_valid.numel() != T * N:
+        raise _ffi.DtcError(f"states_finite: the record has {row_valid.numel()} rows, the states {T * N}")
+    check(lib().dtc_states_finite(cptr(states, f32), T, L, N, H, cptr(row_valid, torch.uint8), stream()), "dtc_states_finite")
+    return row_valid
+
+
+def env_fold(row_valid: torch.Tensor, T: int, N: int, env_valid: torch.Tensor | None = None) -> torch.Tensor:
+    """uint8 [N]: env_valid[n] = AND over t of row_valid[t * N + n]."""
+    if row_valid.numel() != T * N:
+        raise _ffi.DtcError(f"env_fold: the record has {row_valid.numel()} rows, not {T} x {N}")
+    env_valid = torch.empty(N, dtype=torch.uint8, device=row_valid.device) if env_valid is None else env_valid
+    if env_valid.numel() != N:
+        raise _ffi.DtcError(f"env_fold: env_valid is uint8 [{N}], got {tuple(env_valid.shape)}")
+    check(lib().dtc_env_fold(cptr(row_valid, torch.uint8), T, N, cptr(env_valid, torch.uint8), stream()), "dtc_env_fold")
+    return env_valid
+
+
+def env_columns(tensors, N: int):
+    """The DtcEnvColumn array of per-env tensors: [T, N, ...] (outer = T), saved states [T, L, N, H] given as (tensor, "states")
+    (outer = T * L) and [N, ...] given as (tensor, "env") (outer = 1).  Every tensor is contiguous; the array keeps them alive."""
+    tensors = list(tensors)
+    items = (_ffi.DtcEnvColumn * max(1, len(tensors)))()
+    keep = []
+    for it, t in zip(items, tensors):
+        t, kind = t if isinstance(t, tuple) else (t, "steps")
+        env_dim = {"steps": 1, "states": 2, "env": 0}[kind]
+        if not t.is_contiguous() or t.dim() <= env_dim or t.shape[env_dim] != N:
+            raise _ffi.DtcError(f"env_columns: a contiguous tensor with {N} envs in dimension {env_dim} is needed, got {tuple(t.shape)}")
+        inner = 1
+        for s in t.shape[env_dim + 1:]:
+            inner *= s
+        width = inner * t.element_size()
+        if not 1 <= width < 2 ** 31:
+            raise _ffi.DtcError(f"env_columns: {width} bytes per env and outer index")
+        it.base, it.outer = ptr(t), t.numel() // (N * inner)
+        it.outer_stride_bytes, it.env_stride_bytes, it.width_bytes = N * width, width, width
+        keep.append(t)
+    items._keep = keep
+    return items, len(tensors)
+
+
+def env_columns_repair(items, count: int, env_valid: torch.Tensor, env_src: torch.Tensor):
+    """Column env_src[n] over column n of every item, for every env n with env_valid[n] == 0 (one launch of a fixed grid)."""
+    N = env_valid.numel()
+    if env_src.numel() != N:
+        raise _ffi.DtcError(f"env_columns_repair: env_src has {env_src.numel()} entries, env_valid {N}")
+    check(lib().dtc_env_columns_repair(items, count, cptr(env_valid, torch.uint8), cptr(env_src, torch.int64), N, stream()),
+          "dtc_env_columns_repair")
 
 
 def gather_rows(src: torch.Tensor, idx: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:

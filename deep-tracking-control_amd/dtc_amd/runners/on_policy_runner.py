@@ -153,7 +153,7 @@ class OnPolicyRunner:
             t1 = time.time()
             losses = self.alg.update()           # (value, surrogate, adaptation, decoder, recons, vel, kld) means
             t2 = time.time()
-            finished, self._job_nonfinite = _LOCAL, None
+            finished, self._job_nonfinite, self._job_nonfinite_envs = _LOCAL, None, None
             if dpj and tracking:
                 losses, finished = self._job_means(losses, tracker)
             if logging:
@@ -172,16 +172,23 @@ class OnPolicyRunner:
         local = tuple(float(x) for x in losses) + (0.0,) * (7 - len(losses))
         if self._contains():
             local += (float(self.alg.last_nonfinite_rows),)     # the job's SUM of invalid rows rides in the same all-reduce
+        if self._contains_envs():
+            local += (float(self.alg.last_nonfinite_envs),)     # ... and the job's sum of repaired envs, behind every other entry
         local = torch.tensor(local, dtype=torch.float64, device=self.device)
         total = dp.allreduce_sum_(torch.cat((tracker.sums(), local))).tolist()
         count = total[2]
         finished = (total[0] / count, total[1] / count) if count > 0 else None
         if self._contains():
             self._job_nonfinite = int(total[10])
+        if self._contains_envs():
+            self._job_nonfinite_envs = int(total[-1])
         return tuple(x / dp.world_size() for x in total[3:10]), finished
 
     def _contains(self):
         return bool(getattr(self.alg, "contain_nonfinite", False))
+
+    def _contains_envs(self):
+        return bool(getattr(self.alg, "contain_nonfinite_envs", False))
 
     def log(self, it, last, losses, collection_time, learn_time, tracker, width=80, pad=35, finished=_LOCAL):
         """Writes and prints the scalars of iteration `it` and returns them.  `finished`: the (mean reward, mean episode length) to log
@@ -204,6 +211,10 @@ class OnPolicyRunner:
             # rows of the last update that were not finite and stayed out of it (data parallel: the job's sum, _job_means)
             job = getattr(self, "_job_nonfinite", None)
             scalars['Train/nonfinite_rows'] = self.alg.last_nonfinite_rows if job is None else job
+        if self._contains_envs():
+            # envs of the last rollout that held something non-finite and were overwritten by valid ones (data parallel: the job's sum)
+            job = getattr(self, "_job_nonfinite_envs", None)
+            scalars['Train/nonfinite_envs'] = self.alg.last_nonfinite_envs if job is None else job
         if self.writer is not None:
             for k, v in scalars.items():
                 self.writer.add_scalar(k, v, it)

@@ -164,9 +164,57 @@ class RolloutStorage:
     _SCANNED = ("observations", "next_observations", "privileged_observations", "observation_histories", "actions", "rewards",
                 "values", "actions_log_prob", "mu", "sigma", "base_vel")
 
+    # Containment of non-finite ENVS (contain_nonfinite_envs=True of all three trainers, set by their init_storage): compute_returns
+    # first overwrites, in place and on the device, the column of every env that holds anything non-finite -- stored tensors, saved
+    # hidden states, bootstrap value, return, advantage -- with the column of a valid env, then runs the default path on the clean
+    # storage.  It leaves `env_valid` uint8 [N], `env_src` int64 [N] (n where env n is valid, else valid_envs[n % n_valid_envs]; no valid
+    # env: the identity), `n_valid_envs` int64 [1] on the device and marks them fresh; clear() voids the mark.  Off (default): none exists.
+    contain_nonfinite_envs = False
+    env_valid = env_src = valid_envs = n_valid_envs = None
+    env_record_fresh = False
+
     def clear(self):
         self.step = 0
         self.record_fresh = False
+        self.env_record_fresh = False
+
+    def _saved_states(self):
+        return [s for net in (self.saved_hidden_states_a, self.saved_hidden_states_c) if net is not None for s in net]
+
+    def _repair_nonfinite_envs(self, last_values, gamma, lam):
+        """Record (rows of the eleven stored tensors, of the saved states, of the contained GAE scan -- which also carries a non-finite
+        bootstrap value into its env's rows), fold over t, sources, repair.  Every step is a launch on the current stream; nothing is read
+        back.  `last_values` is repaired in place with the rest."""
+        T, N = self.num_transitions_per_env, self.num_envs
+        dev = last_values.device
+        if self.env_valid is None or self.env_valid.device != dev:
+            self._env_rows = torch.empty(T * N, dtype=torch.uint8, device=dev)
+            self.env_valid = torch.empty(N, dtype=torch.uint8, device=dev)
+            self.env_src = torch.empty(N, dtype=torch.int64, device=dev)
+            self.valid_envs = torch.zeros(N, dtype=torch.int64, device=dev)
+            self.n_valid_envs = torch.zeros(1, dtype=torch.int64, device=dev)
+            self._env_iota = torch.arange(N, dtype=torch.int64, device=dev)
+            self._env_ws = ops.workspace(_ffi.lib().dtc_compact_workspace(N), dev)
+            self._env_stats = torch.zeros(4, dtype=torch.float64, device=dev)
+        rows = self._env_rows
+        rows.fill_(1)
+        ops.rows_finite([self.flat(k) for k in self._SCANNED], out=rows)
+        states = self._saved_states()
+        for s in states:
+            ops.states_finite(s, rows)
+        # (used for what it adds to the record only: returns / advantages are written again by the default path below)
+        ops.gae_contained(self.rewards, self.values, self.dones, last_values, gamma, lam, self.returns, self.advantages, rows, self._env_stats)
+        ops.env_fold(rows, T, N, self.env_valid)
+        ops.compact_valid(self.env_valid, self.valid_envs, self.n_valid_envs, self._env_ws)
+        ops.perm_repair(self._env_iota, self.env_valid, self.valid_envs, self.n_valid_envs, out=self.env_src)
+        # every per-env buffer compute_returns or a trainer's update() reads, in ONE launch (descriptors marshalled once)
+        cols = [getattr(self, k) for k in self._SCANNED] + [self.dones] + [(s, "states") for s in states] + [(last_values, "env")]
+        ptrs = tuple((c[0] if isinstance(c, tuple) else c).data_ptr() for c in cols)
+        plan = getattr(self, "_env_plan", None)
+        if plan is None or plan["ptrs"] != ptrs:           # first use, or a buffer was replaced (.to(), re-assignment, new saved states)
+            plan = self._env_plan = dict(ptrs=ptrs, cols=ops.env_columns(cols, N))
+        ops.env_columns_repair(*plan["cols"], self.env_valid, self.env_src)
+        self.env_record_fresh = True
 
     def _compute_returns_contained(self, last_values, gamma, lam):
         """compute_returns over the valid rows only: scan of the eleven stored tensors, contained GAE, compaction, all-reduce of
@@ -198,6 +246,13 @@ class RolloutStorage:
             self._stats = torch.zeros(4, dtype=torch.float64, device=self.device)
         if self.contain_nonfinite:
             return self._compute_returns_contained(last_values, gamma, lam)
+        if self.contain_nonfinite_envs:
+            # (the storage's own copy of the bootstrap values: repaired with the columns, the caller's tensor stays as it is)
+            if getattr(self, "_env_last", None) is None or self._env_last.device != last_values.device:
+                self._env_last = torch.empty(N, 1, dtype=torch.float32, device=last_values.device)
+            self._env_last.copy_(last_values.reshape(N, 1))
+            last_values = self._env_last
+            self._repair_nonfinite_envs(last_values, gamma, lam)
         ops.gae(self.rewards, self.values, self.dones, last_values.contiguous().float(), gamma, lam, self.returns,
                 self.advantages, self._stats)
         world = dp.world_size()

@@ -38,7 +38,7 @@ extern "C" {
 #define DTC_ACT_SIGMOID 6
 
 /* library / device info ------------------------------------------------------------------ */
-#define DTC_ABI_VERSION 19                  /* bumped whenever a signature or a by-value struct layout changes       */
+#define DTC_ABI_VERSION 20                  /* bumped whenever a signature or a by-value struct layout changes       */
 int dtc_version(void);                       /* == DTC_ABI_VERSION of the build; the host binding refuses a mismatch   */
 /* sizeof() of the structs that cross the boundary, in the order DtcGridCfg, DtcObsCfg, DtcRowCopy, DtcSeg, DtcSegMat,
    DtcFwdLayer, DtcWgradJob, DtcPpoCfg, DtcProfRec, DtcWimgJob, DtcH2iWJob, DtcH2iOperand, DtcWgradH2iJob, DtcEnvStep, DtcH2iFwdLayer, DtcH2iDgradLayer, DtcGruFwdItem, DtcGruBwdItem: the binding compares them with its own layouts at load time (a library
@@ -441,6 +441,40 @@ int dtc_compact_valid(const uint8_t* row_valid, int64_t n, int64_t* valid_list, 
  * [0, R): the entry passes through.) */
 int dtc_perm_repair(const int64_t* perm, int64_t len, const uint8_t* row_valid, int64_t R, const int64_t* valid_list,
                     const int64_t* n_valid, int64_t* out, void* stream);
+
+/* ---- containment of non-finite rollout ENVS (contain_nonfinite_envs=True of all three trainers) -------------------------------
+ * The unit is an env, a column of the [T, N, ...] storage: env n is VALID iff every row t * N + n of the record above is, the record
+ * now also covering the saved hidden states (rollout_storage.py:118-132).  Invalid columns are overwritten in the storage by valid
+ * ones before rollout_storage.py:138-152 runs; the sources are dtc_compact_valid + dtc_perm_repair over the identity permutation:
+ * env_src[n] = n where env n is valid, else valid_list[n % *n_valid] (no valid env: the identity). */
+/* The record of one saved hidden-state tensor, contiguous fp32 [T, L, N, H] (4-byte aligned, any H >= 1, 64-bit flat indices):
+ * row_valid[t * N + n] &= every element of [t, l, n, :] is finite for every layer l -- the finiteness rule and the store-0-only
+ * contract of dtc_rows_finite. */
+int dtc_states_finite(const float* s, int64_t T, int64_t L, int64_t N, int64_t H, uint8_t* row_valid, void* stream);
+/* env_valid[n] = AND over t of row_valid[t * N + n] (every entry written; deterministic). */
+int dtc_env_fold(const uint8_t* row_valid, int64_t T, int64_t N, uint8_t* env_valid, void* stream);
+/* One per-env buffer of the storage as `outer` rows per env: row (o, n) is the width_bytes bytes at
+ * base + o * outer_stride_bytes + n * env_stride_bytes.  [T, N, w]: outer = T; saved states [T, L, N, H]: outer = T * L; [N, w]: outer = 1. */
+typedef struct DtcEnvColumn {
+    void* base;
+    int64_t outer;
+    int64_t outer_stride_bytes;
+    int64_t env_stride_bytes;
+    int32_t width_bytes;
+} DtcEnvColumn;
+/* For every env n with env_valid[n] == 0 and env_src[n] another env of [0, N): rows (o, env_src[n]) copied over rows (o, n) of every
+ * item, bit for bit.  `items` is a HOST array of n_items (1..dtc_env_columns_cap()) descriptors; env_valid / env_src are on the device,
+ * and so is the number of invalid envs: the launch is a fixed grid sized from the device's CU count, which ends after one pass over
+ * env_valid when there is nothing to repair.  16-byte accesses where base, strides and width of an item allow them, else 4-byte or
+ * 1-byte ones; 64-bit byte offsets.  Source columns (valid envs) are never written: the result does not depend on scheduling.
+ * The kernel trusts the descriptors (as dtc_store_transition does); null pointers, n_items outside 1..cap, width_bytes < 1,
+ * outer < 1 and an env stride below the width are rejected with DTC_ERR_ARG before any launch. */
+int dtc_env_columns_cap(void);
+int dtc_env_columns_repair(const DtcEnvColumn* items, int n_items, const uint8_t* env_valid, const int64_t* env_src, int64_t N,
+                           void* stream);
+/* sizeof() of DtcEnvColumn, as dtc_abi_sizes gives them for the older structs (whose table keeps its 18 entries): compared by the
+ * binding at load time. */
+int dtc_contain_envs_abi_sizes(int64_t* out, int cap);
 
 /* ---- mini-batch gather: rollout_storage.py:195-209 (`tensor[batch_idx]`) ------------------ */
 int dtc_gather_rows(const void* src, const int64_t* idx, void* dst, int64_t rows, int64_t row_bytes,
