@@ -77,6 +77,9 @@ int dtc_version(void) { return DTC_ABI_VERSION; }
 static int g_gemm_split = 0;
 void dtc_set_gemm_split(int on) { g_gemm_split = on ? 1 : 0; }
 int dtc_get_gemm_split(void) { return g_gemm_split; }
+static int g_amax_finite_only = 0;
+void dtc_set_amax_finite_only(int on) { g_amax_finite_only = on ? 1 : 0; }
+int dtc_get_amax_finite_only(void) { return g_amax_finite_only; }
 int dtc_abi_sizes(int64_t* out, int cap) {
     const int64_t sz[] = {sizeof(DtcGridCfg), sizeof(DtcObsCfg), sizeof(DtcRowCopy), sizeof(DtcSeg), sizeof(DtcSegMat),
                           sizeof(DtcFwdLayer), sizeof(DtcWgradJob), sizeof(DtcPpoCfg), sizeof(DtcProfRec), sizeof(DtcWimgJob),

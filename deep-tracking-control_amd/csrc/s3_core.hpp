@@ -114,7 +114,8 @@ struct AmaxGroup {
 };
 // block = rows_per_block whole rows of one item (~8192 elements); thread = (row of the pass, column): consecutive lanes read consecutive
 // floats of a row, no division anywhere
-__global__ __launch_bounds__(256) void amax_group_kernel(const AmaxGroup G) {
+// `finite_only` (dtc_set_amax_finite_only): inf / NaN count as 0, the exponent comes from the finite elements
+__global__ __launch_bounds__(256) void amax_group_kernel(const AmaxGroup G, const int finite_only) {
     int i = 0, b = blockIdx.x;
     while (i < G.count - 1 && b >= G.it[i].block_end) ++i;
     if (i > 0) b -= G.it[i - 1].block_end;
@@ -125,7 +126,8 @@ __global__ __launch_bounds__(256) void amax_group_kernel(const AmaxGroup G) {
     for (int row = b * I.rows_per_block + (threadIdx.x >> I.tw_shift); row < r_end; row += rstep) {
         const float* src = I.ptr + (I.idx ? I.idx[row] : (long long)row) * I.ld + I.col0;
         for (int c = c0; c < I.width; c += tw) {
-            const u32 v = abs_bits(src[c]);
+            u32 v = abs_bits(src[c]);
+            v = (finite_only && v >= 0x7f800000u) ? 0u : v;
             m = v > m ? v : m;
         }
     }
@@ -150,7 +152,7 @@ inline bool amax_group_run(const AmaxGroup& G, void* slots, size_t bytes, hipStr
     if (G.count == 0) return true;
     const int words = (int)(bytes / 4);
     hipLaunchKernelGGL(amax_zero_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, (u32*)slots, words);
-    hipLaunchKernelGGL(amax_group_kernel, dim3((unsigned)G.it[G.count - 1].block_end), dim3(256), 0, s, G);
+    hipLaunchKernelGGL(amax_group_kernel, dim3((unsigned)G.it[G.count - 1].block_end), dim3(256), 0, s, G, dtc_get_amax_finite_only());
     return true;
 }
 

@@ -184,6 +184,12 @@ class DtcEnvColumn(C.Structure):
                 ("width_bytes", C.c_int32)]
 
 
+class DtcActItem(C.Structure):
+    """include/dtc_hip.h: one fp32 tensor of a rollout step for dtc_act_contain (element (o, n, j) at base + o * outer_stride + n * env_stride + j)."""
+    _fields_ = [("base", C.c_void_p), ("outer", C.c_int64), ("outer_stride_elems", C.c_int64), ("env_stride_elems", C.c_int64),
+                ("width", C.c_int32), ("mode", C.c_int32)]
+
+
 class DtcProfRec(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("ms_total", C.c_double), ("work", C.c_double),
                 ("launches", C.c_int64), ("bytes", C.c_double)]
@@ -192,7 +198,7 @@ class DtcProfRec(C.Structure):
 ACT = {None: 0, "none": 0, "relu": 1, "crelu": 1, "elu": 2, "selu": 3, "lrelu": 4, "tanh": 5, "sigmoid": 6}
 MAX_OPERAND_ELEMS = (1 << 29) - 1
 
-ABI_VERSION = 20        # DTC_ABI_VERSION of include/dtc_hip.h this binding was written against
+ABI_VERSION = 21        # DTC_ABI_VERSION of include/dtc_hip.h this binding was written against
 
 _SIGS = {
     "dtc_version": (C.c_int, []),
@@ -239,6 +245,9 @@ _SIGS = {
     "dtc_env_columns_cap": (C.c_int, []),
     "dtc_env_columns_repair": (C.c_int, [C.POINTER(DtcEnvColumn), C.c_int, c_u8p, c_i64p, C.c_int64, c_stream]),
     "dtc_contain_envs_abi_sizes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
+    "dtc_act_contain_cap": (C.c_int, []),
+    "dtc_act_contain": (C.c_int, [C.POINTER(DtcActItem), C.c_int, C.c_int64, c_u8p, c_u8p, c_stream]),
+    "dtc_act_contain_abi_sizes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
     "dtc_gather_rows": (C.c_int, [C.c_void_p, c_i64p, C.c_void_p, C.c_int64, C.c_int64, c_stream]),
     "dtc_scatter_rows": (C.c_int, [c_f32p, c_i64p, c_f32p, C.c_int64, C.c_int64, c_stream]),
     "dtc_pack_cols": (C.c_int, [C.POINTER(DtcSegMat), c_f32p, C.c_int64, C.c_int64, C.c_void_p, c_stream]),
@@ -246,6 +255,8 @@ _SIGS = {
                                  C.c_int, c_stream]),
     "dtc_linear_fwd_list": (C.c_int, [C.POINTER(DtcFwdLayer), C.c_int, C.c_int, c_stream]),
     "dtc_set_gemm_split": (None, [C.c_int]),
+    "dtc_set_amax_finite_only": (None, [C.c_int]),
+    "dtc_get_amax_finite_only": (C.c_int, []),
     "dtc_get_gemm_split": (C.c_int, []),
     "dtc_s3_planes_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "dtc_s3_wimage_group": (C.c_int, [C.POINTER(DtcWimgJob), C.c_int, c_stream]),
@@ -418,6 +429,9 @@ def _check_abi(l):
     theirs += list(sizes[:n])
     mine += [DtcEnvColumn]                                                # ... and by the env containment's
     n = l.dtc_contain_envs_abi_sizes(sizes, 32)
+    theirs += list(sizes[:n])
+    mine += [DtcActItem]                                                  # ... and by the rollout-step containment's
+    n = l.dtc_act_contain_abi_sizes(sizes, 32)
     theirs += list(sizes[:n])
     if l.dtc_version() != ABI_VERSION or theirs != [C.sizeof(t) for t in mine]:
         _lib = None

@@ -339,6 +339,42 @@ def read_env_record(alg):
                             "repaired: the advantage statistics and this update's weights are not finite")
 
 
+def require_contained_update(alg):
+    """contain_nonfinite_act, in a trainer's constructor: the repair of a rollout step needs a containment of the update behind it."""
+    if alg.contain_nonfinite_act and not (getattr(alg, "contain_nonfinite", False) or alg.contain_nonfinite_envs):
+        raise ValueError("contain_nonfinite_act=True needs contain_nonfinite_envs=True" + (" or contain_nonfinite=True" if hasattr(alg, "contain_nonfinite") else "")
+                         + ": a repaired step that stays in the update would be recomputed there -- the update reads the inputs the step "
+                         "read and re-runs a recurrence from its saved start state, which reproduces what the step produced")
+
+
+def init_act_containment(alg):
+    """contain_nonfinite_act, in a trainer's init_storage: storage.act_valid uint8 [T, N] (1 = the step of env n at t left act() as computed)
+    and alg.nonfinite_act_envs uint8 [N] (1 = env n was repaired by the LAST act(); one tensor for good, the env side may hold on to it)."""
+    st = alg.storage
+    st.act_valid = torch.ones(st.num_transitions_per_env, st.num_envs, dtype=torch.uint8, device=alg.device)
+    alg.nonfinite_act_envs = torch.zeros(st.num_envs, dtype=torch.uint8, device=alg.device)
+
+
+def contain_act(alg, inputs):
+    """contain_nonfinite_act, behind the policy step of a trainer's act() (and outside a captured graph): ONE launch over what the step
+    read (`inputs`, as the trainer received them) and what it produced.  An env with anything non-finite among them leaves act() with
+    zero actions and a zeroed live recurrent state in every layer of both memories; it is named in alg.nonfinite_act_envs (for the env
+    side to reset) and in storage.act_valid[step] (for compute_returns to keep it out of the update).  Nothing is read back."""
+    tr, st, ac = alg.transition, alg.storage, alg.actor_critic
+    states = []
+    if hasattr(ac, "memory_a"):
+        for h in ac.get_hidden_states():               # the state AFTER this step: a tensor (GRU) or (h, c) (LSTM), [layers, N, H] each
+            states += list(h) if isinstance(h, (tuple, list)) else [h]
+    ops.act_contain(scan=[*inputs, tr.action_mean, tr.values, tr.actions_log_prob], repair=[tr.actions, *states],
+                    act_valid_row=st.act_valid[st.step], env_bad=alg.nonfinite_act_envs)
+
+
+def read_act_record(alg):
+    """contain_nonfinite_act, behind an update()'s one synchronisation: the repaired (step, env) pairs of the rollout just consumed,
+    counted on the device by compute_returns -> alg.last_nonfinite_act."""
+    alg.last_nonfinite_act = int(alg.storage.act_invalid.item())
+
+
 class PPO:
     actor_critic: ActorCriticDecoder
     # The mini-batches of update() are row sets of the stored rollout, each run by _vae_step / _ppo_step.  False (RecurrentDecoderPPO):
@@ -348,8 +384,14 @@ class PPO:
     def __init__(self, actor_critic, num_learning_epochs=5, num_mini_batches=4, clip_param=0.2, gamma=0.99, lam=0.95,
                  value_loss_coef=1.0, entropy_coef=0.01, learning_rate=5.e-4, max_grad_norm=1.0,
                  use_clipped_value_loss=True, schedule="adaptive", desired_kl=0.01, device='cpu', *, gemm_passes=3, ragged_images=False,
-                 contain_nonfinite=False, contain_nonfinite_envs=False):
+                 contain_nonfinite=False, contain_nonfinite_envs=False, contain_nonfinite_act=False):
         self.device = device
+        # An env whose rollout step read or produced anything non-finite leaves act() with zero actions and a cleared live recurrent state,
+        # and is named to the env side (`nonfinite_act_envs`) and to the storage (opt-in; contain_act).  It rests on one of the two
+        # containments of the update below.  `last_nonfinite_act`: this rank's repaired (step, env) pairs of the last update's rollout.
+        # False (default): no launch, no allocation, no `nonfinite_act_envs`.
+        self.contain_nonfinite_act = bool(contain_nonfinite_act)
+        self.last_nonfinite_act = 0
         # Envs of the stored rollout that hold anything non-finite are overwritten IN THE STORAGE by valid envs before the update reads it
         # (opt-in; RolloutStorage._repair_nonfinite_envs, run by compute_returns): update() then is the default update, on any schedule,
         # any memory type, any row count -- the form of containment the trajectory mini-batches of the recurrent trainers can take.
@@ -364,6 +406,7 @@ class PPO:
         # (_contained_perm).  `last_nonfinite_rows`: this rank's invalid rows of the last update.  False (default): nothing is added.
         self.contain_nonfinite = bool(contain_nonfinite)
         self.last_nonfinite_rows = 0
+        require_contained_update(self)
         if self.contain_nonfinite and not self.row_sets:
             raise TypeError(f"{type(self).__name__} has no contain_nonfinite: the mini-batches of its update() are trajectories, not row sets "
                             "(contain_nonfinite_envs=True contains whole envs in the storage instead)")
@@ -481,6 +524,8 @@ class PPO:
             self.storage.contain_nonfinite = True
         if self.contain_nonfinite_envs:
             self.storage.contain_nonfinite_envs = True
+        if self.contain_nonfinite_act:
+            init_act_containment(self)
 
     def test_mode(self):
         self.actor_critic.eval()
@@ -526,9 +571,14 @@ class PPO:
         tr = self.transition
         if self.graph_rollout and type(self).act is PPO.act and not self.actor_critic.is_recurrent:
             out = self._policy_step_graphed(obs, privileged_obs, obs_history, base_vel)
+        elif self.contain_nonfinite_act and self.actor_critic.is_recurrent:
+            with ops.rows_to_themselves():         # (one env's non-finite element must not reach the others' rows: there would be none to keep)
+                out = self._policy_step(obs, privileged_obs, obs_history, base_vel, rew_buf)
         else:
             out = self._policy_step(obs, privileged_obs, obs_history, base_vel, rew_buf)
         tr.actions, tr.values, tr.actions_log_prob, tr.action_mean, tr.action_sigma = out
+        if self.contain_nonfinite_act:
+            contain_act(self, (obs, privileged_obs, obs_history, base_vel))
         tr.observations = obs
         tr.critic_observations = obs
         tr.privileged_observations = privileged_obs
@@ -1199,6 +1249,8 @@ class PPO:
             finally:
                 ops.amax_static_clear()                # the storage is about to be refilled: its amax slots are void
         host, out = self._read_back(stats)
+        if self.contain_nonfinite_act:
+            read_act_record(self)
         if self.contain_nonfinite:
             # (behind the update's one synchronisation: every step has run, the two counts are plain reads)
             rows, valid, job = st.row_valid.numel(), int(st.valid_rows.item()), int(st._stats[1].item())

@@ -29,7 +29,7 @@ from .._ffi import seg, segmat
 from ..modules.actor_critic_decoder import Dense
 from ..modules.actor_critic_decoder_recurrent import ActorCriticDecoderRecurrent
 from ..utils import split_and_pad_trajectories, true_indices
-from .ppo import PPO, S_GNORM, S_SURR, STAT_COLS, Schedule, read_env_record, require_env_record
+from .ppo import PPO, S_GNORM, S_SURR, STAT_COLS, Schedule, read_act_record, read_env_record, require_env_record
 from .recurrent_heads import GruHead, forward_backward
 from .recurrent_ppo import _share_rule
 
@@ -57,7 +57,11 @@ class RecurrentDecoderPPO(PPO):
         self._require_gpu()
         ac = self.actor_critic
         keep = ac.memory_c.clone_hidden(ac.memory_c.hidden_states)
-        last_values = ac.evaluate(last_critic_obs, last_critic_privileged_obs, last_base_vel).detach()
+        if self.contain_nonfinite_act:             # (as in act(): a non-finite last observation costs its own env the bootstrap value, no other)
+            with ops.rows_to_themselves():
+                last_values = ac.evaluate(last_critic_obs, last_critic_privileged_obs, last_base_vel).detach()
+        else:
+            last_values = ac.evaluate(last_critic_obs, last_critic_privileged_obs, last_base_vel).detach()
         ac.memory_c.hidden_states = keep            # the bootstrap value must not advance the critic's state
         self.storage.compute_returns(last_values, self.gamma, self.lam)
 
@@ -364,6 +368,8 @@ class RecurrentDecoderPPO(PPO):
                 ops.amax_static_clear()          # the storage is about to be refilled: its amax slots are void
         host, out = self._read_back(stats)
         ops.gru_seq_check()                      # (the persistent recurrence launches of this update all ran to their end)
+        if self.contain_nonfinite_act:
+            read_act_record(self)
         if self.contain_nonfinite_envs:
             read_env_record(self)
         st.clear()

@@ -23,7 +23,8 @@ from ..storage import RolloutStorage
 from ..utils import UpdateSlots, true_indices
 import os
 
-from .ppo import FusedAdam, S_ENTROPY, S_GNORM, S_KL, S_SURR, S_VALUE, STAT_COLS, _StepWorkspace, read_env_record, require_env_record
+from .ppo import (FusedAdam, S_ENTROPY, S_GNORM, S_KL, S_SURR, S_VALUE, STAT_COLS, _StepWorkspace, contain_act, init_act_containment,
+                  read_act_record, read_env_record, require_contained_update, require_env_record)
 from .recurrent_heads import GruHead, forward_backward
 
 
@@ -40,11 +41,16 @@ class RecurrentPPO:
 
     def __init__(self, actor_critic, num_learning_epochs=5, num_mini_batches=4, clip_param=0.2, gamma=0.99, lam=0.95,
                  value_loss_coef=1.0, entropy_coef=0.01, learning_rate=5.e-4, max_grad_norm=1.0,
-                 use_clipped_value_loss=True, schedule="adaptive", desired_kl=0.01, device='cpu', *, contain_nonfinite_envs=False):
+                 use_clipped_value_loss=True, schedule="adaptive", desired_kl=0.01, device='cpu', *, contain_nonfinite_envs=False,
+                 contain_nonfinite_act=False):
         self.device = device
         # PPO's keyword of the same name: envs that hold anything non-finite are overwritten in the storage by valid ones before update()
         self.contain_nonfinite_envs = bool(contain_nonfinite_envs)
         self.last_nonfinite_envs = 0
+        # ... and PPO's: an env whose rollout step read or produced anything non-finite leaves act() with zero actions and a cleared state
+        self.contain_nonfinite_act = bool(contain_nonfinite_act)
+        self.last_nonfinite_act = 0
+        require_contained_update(self)
         self.desired_kl, self.schedule, self.learning_rate = desired_kl, schedule, learning_rate
         self.actor_critic = actor_critic
         self.actor_critic.to(self.device)
@@ -87,6 +93,8 @@ class RecurrentPPO:
                                       action_shape, self.device)
         if self.contain_nonfinite_envs:
             self.storage.contain_nonfinite_envs = True
+        if self.contain_nonfinite_act:
+            init_act_containment(self)
 
     def test_mode(self):
         self.actor_critic.eval()
@@ -103,10 +111,16 @@ class RecurrentPPO:
             if m.hidden_states is None:
                 m.hidden_states = m.init_hidden(N, obs.device)
         tr.hidden_states = tuple(m.clone_hidden(h) for m, h in zip((ac.memory_a, ac.memory_c), ac.get_hidden_states()))   # BEFORE this step
-        tr.actions = ac.act(obs).detach()
-        tr.values = ac.evaluate(critic_obs).detach()
+        if self.contain_nonfinite_act:
+            with ops.rows_to_themselves():         # (one env's non-finite element must not reach the others' rows: there would be none to keep)
+                tr.actions, tr.values = ac.act(obs).detach(), ac.evaluate(critic_obs).detach()
+        else:
+            tr.actions = ac.act(obs).detach()
+            tr.values = ac.evaluate(critic_obs).detach()
         tr.actions_log_prob = ac.get_actions_log_prob(tr.actions).detach()
         tr.action_mean, tr.action_sigma = ac.action_mean.detach(), ac.action_std.detach()
+        if self.contain_nonfinite_act:
+            contain_act(self, (obs, critic_obs))
         tr.observations, tr.critic_observations, tr.privileged_observations = obs, critic_obs, critic_obs
         tr.observation_histories = torch.zeros(N, 1, device=obs.device)
         tr.base_vel = torch.zeros(N, 3, device=obs.device)
@@ -126,7 +140,11 @@ class RecurrentPPO:
         self._require_gpu()
         ac = self.actor_critic
         keep = ac.memory_c.clone_hidden(ac.memory_c.hidden_states)
-        last_values = ac.evaluate(last_critic_obs).detach()
+        if self.contain_nonfinite_act:             # (as in act(): a non-finite last observation costs its own env the bootstrap value, no other)
+            with ops.rows_to_themselves():
+                last_values = ac.evaluate(last_critic_obs).detach()
+        else:
+            last_values = ac.evaluate(last_critic_obs).detach()
         ac.memory_c.hidden_states = keep            # the bootstrap value must not advance the critic's state
         self.storage.compute_returns(last_values, self.gamma, self.lam)
 
@@ -366,6 +384,8 @@ class RecurrentPPO:
         self.learning_rate = float(self.optimizer.lr_dev.item())
         self.last_update_stats = host
         m = host.double().mean(dim=0)
+        if self.contain_nonfinite_act:
+            read_act_record(self)
         if self.contain_nonfinite_envs:
             read_env_record(self)
         st.clear()

@@ -158,6 +158,48 @@ def env_columns_repair(items, count: int, env_valid: torch.Tensor, env_src: torc
           "dtc_env_columns_repair")
 
 
+# containment of non-finite envs at the rollout step (csrc/contain_act.hip)
+def act_contain(scan=(), repair=(), act_valid_row: torch.Tensor | None = None, env_bad: torch.Tensor | None = None):
+    """One launch over the tensors of a rollout step: env n is bad iff any element of any listed tensor at env n is NaN or +-inf; the
+    `repair` tensors are zeroed IN PLACE at every bad env, the `scan` tensors are only read; act_valid_row[n] = !bad and env_bad[n] = bad
+    (uint8 [N], optional) are written for every env.  Tensors are fp32 on the device with the envs in dimension 0 -- [N], [N, w] --
+    or, 3-D, in dimension 1: live recurrent states [L, N, H].  The innermost stride is 1; a `scan` matrix may have any row stride >= w.
+    Nothing is ever copied: a tensor that does not fit raises ValueError, since zeroing a copy would leave the caller's tensor as it was."""
+    scan, repair = list(scan), list(repair)
+    n_items = len(scan) + len(repair)
+    cap = lib().dtc_act_contain_cap()
+    if not 1 <= n_items <= cap:
+        raise ValueError(f"act_contain takes 1..{cap} tensors, got {n_items}")
+    items = (_ffi.DtcActItem * n_items)()
+    N = None
+    for it, (t, mode) in zip(items, [(t, 0) for t in scan] + [(t, 1) for t in repair]):
+        what = "repair" if mode else "scan"
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"act_contain: a {what} item is a tensor, got {type(t).__name__}")
+        if not t.is_cuda or t.dtype != f32 or not 1 <= t.dim() <= 3 or t.numel() == 0:
+            raise ValueError(f"act_contain: a {what} item is a non-empty fp32 device tensor [N], [N, w] or [L, N, H], got "
+                             f"{tuple(t.shape)} {t.dtype} on {t.device} (nothing is converted or copied on the way to the kernel)")
+        env_dim = 1 if t.dim() == 3 else 0
+        width = t.shape[-1] if t.dim() > 1 else 1
+        if t.dim() > 1 and width > 1 and t.stride(-1) != 1:
+            raise ValueError(f"act_contain: a {what} item has element stride {t.stride(-1)} (shape {tuple(t.shape)}): unit stride is needed, "
+                             "and nothing is copied on the way to the kernel")
+        outer = t.shape[0] if t.dim() == 3 else 1
+        outer_stride = t.stride(0) if outer > 1 else 0
+        env_stride = t.stride(env_dim) if t.shape[env_dim] > 1 else max(t.stride(env_dim), width)     # (one env: the stride is never used)
+        if env_stride < width or (outer > 1 and outer_stride < width):
+            raise ValueError(f"act_contain: a {what} item has shape {tuple(t.shape)} and strides {t.stride()}: its rows overlap")
+        if N is None:
+            N = t.shape[env_dim]
+        if t.shape[env_dim] != N:
+            raise ValueError(f"act_contain: {t.shape[env_dim]} envs in a tensor of shape {tuple(t.shape)}, {N} in the first one")
+        it.base, it.outer, it.outer_stride_elems, it.env_stride_elems, it.width, it.mode = t.data_ptr(), outer, outer_stride, env_stride, width, mode
+    for name, o in (("act_valid_row", act_valid_row), ("env_bad", env_bad)):
+        if o is not None and (not o.is_cuda or o.dtype != torch.uint8 or o.shape != (N,) or not o.is_contiguous()):
+            raise ValueError(f"act_contain: {name} is a contiguous uint8 [{N}] device tensor, got {tuple(o.shape)} {o.dtype} on {o.device}")
+    check(lib().dtc_act_contain(items, n_items, N, ptr(act_valid_row), ptr(env_bad), stream()), "dtc_act_contain")
+
+
 def gather_rows(src: torch.Tensor, idx: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     """src[idx] for a contiguous 2-D+ tensor (rows = dim 0)."""
     assert src.is_contiguous() and idx.dtype == torch.int64 and idx.is_contiguous()
@@ -533,6 +575,20 @@ def pack_cols(X, dst, rows=None):
     check(lib().dtc_pack_cols(X, ptr(dst), dst.stride(0), rows, _amax_out(dst, 0, X.cols) if (SPLIT and H2 and rows == dst.shape[0]) else None,
                               stream()), "dtc_pack_cols")
     return dst
+
+
+class rows_to_themselves:
+    """Context: the two-term fp16 kernels take the exponent of an operand that brings no amax record from its FINITE elements
+    (dtc_set_amax_finite_only), so a non-finite element of one row stays in that row of the product instead of spoiling the one
+    exponent all rows share.  On finite operands nothing changes, bit for bit.  The rollout step of the recurrent models runs inside it
+    when contain_nonfinite_act is on (PPO.act's layer chains are single-pass fp32: every row to itself anyway); nothing else does."""
+
+    def __enter__(self):
+        self.before = lib().dtc_get_amax_finite_only()
+        lib().dtc_set_amax_finite_only(1)
+
+    def __exit__(self, *exc):
+        lib().dtc_set_amax_finite_only(self.before)
 
 
 def linear_fwd(X, W, b, Y, act=None, M=None, mask=None, split=None):

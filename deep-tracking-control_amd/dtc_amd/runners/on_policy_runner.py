@@ -142,6 +142,10 @@ class OnPolicyRunner:
         if init_at_random_ep_len:
             self.env.episode_length_buf = torch.randint_like(self.env.episode_length_buf,
                                                              high=int(self.env.max_episode_length))
+        if self._contains_act():
+            # uint8 [N] on the device, rewritten by every act(): the env (the wrapped one, not the history wrapper) ORs it into its reset
+            # buffer
+            self.env.env.nonfinite_act_envs = self.alg.nonfinite_act_envs
         self.alg.actor_critic.train()
         state = dict(obs_dict=self.env.get_observations(), rew_buf=self.env.get_reward_buf())
         tracker = self.tracker = _EpisodeTracker(self.env.num_envs, self.device) if tracking else None
@@ -153,7 +157,7 @@ class OnPolicyRunner:
             t1 = time.time()
             losses = self.alg.update()           # (value, surrogate, adaptation, decoder, recons, vel, kld) means
             t2 = time.time()
-            finished, self._job_nonfinite, self._job_nonfinite_envs = _LOCAL, None, None
+            finished, self._job_nonfinite, self._job_nonfinite_envs, self._job_nonfinite_act = _LOCAL, None, None, None
             if dpj and tracking:
                 losses, finished = self._job_means(losses, tracker)
             if logging:
@@ -172,8 +176,12 @@ class OnPolicyRunner:
         local = tuple(float(x) for x in losses) + (0.0,) * (7 - len(losses))
         if self._contains():
             local += (float(self.alg.last_nonfinite_rows),)     # the job's SUM of invalid rows rides in the same all-reduce
+        envs_at = 3 + len(local)                                # (position in `total`, behind the tracker's three sums)
         if self._contains_envs():
-            local += (float(self.alg.last_nonfinite_envs),)     # ... and the job's sum of repaired envs, behind every other entry
+            local += (float(self.alg.last_nonfinite_envs),)     # ... and the job's sum of repaired envs, behind every entry above
+        act_at = 3 + len(local)
+        if self._contains_act():
+            local += (float(self.alg.last_nonfinite_act),)      # ... and of repaired rollout steps, behind those
         local = torch.tensor(local, dtype=torch.float64, device=self.device)
         total = dp.allreduce_sum_(torch.cat((tracker.sums(), local))).tolist()
         count = total[2]
@@ -181,7 +189,9 @@ class OnPolicyRunner:
         if self._contains():
             self._job_nonfinite = int(total[10])
         if self._contains_envs():
-            self._job_nonfinite_envs = int(total[-1])
+            self._job_nonfinite_envs = int(total[envs_at])
+        if self._contains_act():
+            self._job_nonfinite_act = int(total[act_at])
         return tuple(x / dp.world_size() for x in total[3:10]), finished
 
     def _contains(self):
@@ -189,6 +199,9 @@ class OnPolicyRunner:
 
     def _contains_envs(self):
         return bool(getattr(self.alg, "contain_nonfinite_envs", False))
+
+    def _contains_act(self):
+        return bool(getattr(self.alg, "contain_nonfinite_act", False))
 
     def log(self, it, last, losses, collection_time, learn_time, tracker, width=80, pad=35, finished=_LOCAL):
         """Writes and prints the scalars of iteration `it` and returns them.  `finished`: the (mean reward, mean episode length) to log
@@ -215,6 +228,10 @@ class OnPolicyRunner:
             # envs of the last rollout that held something non-finite and were overwritten by valid ones (data parallel: the job's sum)
             job = getattr(self, "_job_nonfinite_envs", None)
             scalars['Train/nonfinite_envs'] = self.alg.last_nonfinite_envs if job is None else job
+        if self._contains_act():
+            # (step, env) pairs of the last rollout that act() repaired: zero actions, cleared live state (data parallel: the job's sum)
+            job = getattr(self, "_job_nonfinite_act", None)
+            scalars['Train/nonfinite_act'] = self.alg.last_nonfinite_act if job is None else job
         if self.writer is not None:
             for k, v in scalars.items():
                 self.writer.add_scalar(k, v, it)

@@ -173,10 +173,27 @@ class RolloutStorage:
     env_valid = env_src = valid_envs = n_valid_envs = None
     env_record_fresh = False
 
+    # Containment at the rollout step (contain_nonfinite_act=True of all three trainers, set by their init_storage): `act_valid` uint8 [T, N],
+    # written one row per act() by dtc_act_contain -- 0 where the step of env n at t was repaired (zero actions, cleared live state).  Both
+    # records above START from it: such a step stays out of the update even where its stored bytes look clean (the update would re-run the
+    # recurrence from the saved start state and reproduce what the step produced).  `act_invalid` int64 [] on the device: its zeros, counted
+    # by compute_returns.  clear() refills it with 1.  Off (default): None, and the records start from all ones.
+    act_valid = act_invalid = None
+
     def clear(self):
         self.step = 0
         self.record_fresh = False
         self.env_record_fresh = False
+        if self.act_valid is not None:
+            self.act_valid.fill_(1)
+
+    def _start_record(self, rows):
+        """The record of a rollout before the scans, which can only clear further entries."""
+        if self.act_valid is None:
+            return rows.fill_(1)
+        rows.copy_(self.act_valid.view(-1))
+        self.act_invalid = rows.numel() - self.act_valid.sum(dtype=torch.int64)        # (on the device; read behind update()'s synchronisation)
+        return rows
 
     def _saved_states(self):
         return [s for net in (self.saved_hidden_states_a, self.saved_hidden_states_c) if net is not None for s in net]
@@ -196,8 +213,7 @@ class RolloutStorage:
             self._env_iota = torch.arange(N, dtype=torch.int64, device=dev)
             self._env_ws = ops.workspace(_ffi.lib().dtc_compact_workspace(N), dev)
             self._env_stats = torch.zeros(4, dtype=torch.float64, device=dev)
-        rows = self._env_rows
-        rows.fill_(1)
+        rows = self._start_record(self._env_rows)
         ops.rows_finite([self.flat(k) for k in self._SCANNED], out=rows)
         states = self._saved_states()
         for s in states:
@@ -227,7 +243,7 @@ class RolloutStorage:
             self.valid_list = torch.zeros(R, dtype=torch.int64, device=dev)
             self.valid_rows = torch.zeros(1, dtype=torch.int64, device=dev)
             self._compact_ws = ops.workspace(_ffi.lib().dtc_compact_workspace(R), dev)
-        self.row_valid.fill_(1)
+        self._start_record(self.row_valid)
         ops.rows_finite([self.flat(k) for k in self._SCANNED], out=self.row_valid)
         ops.gae_contained(self.rewards, self.values, self.dones, last_values.contiguous().float(), gamma, lam, self.returns,
                           self.advantages, self.row_valid, self._stats)

@@ -38,7 +38,7 @@ extern "C" {
 #define DTC_ACT_SIGMOID 6
 
 /* library / device info ------------------------------------------------------------------ */
-#define DTC_ABI_VERSION 20                  /* bumped whenever a signature or a by-value struct layout changes       */
+#define DTC_ABI_VERSION 21                  /* bumped whenever a signature or a by-value struct layout changes       */
 int dtc_version(void);                       /* == DTC_ABI_VERSION of the build; the host binding refuses a mismatch   */
 /* sizeof() of the structs that cross the boundary, in the order DtcGridCfg, DtcObsCfg, DtcRowCopy, DtcSeg, DtcSegMat,
    DtcFwdLayer, DtcWgradJob, DtcPpoCfg, DtcProfRec, DtcWimgJob, DtcH2iWJob, DtcH2iOperand, DtcWgradH2iJob, DtcEnvStep, DtcH2iFwdLayer, DtcH2iDgradLayer, DtcGruFwdItem, DtcGruBwdItem: the binding compares them with its own layouts at load time (a library
@@ -476,6 +476,36 @@ int dtc_env_columns_repair(const DtcEnvColumn* items, int n_items, const uint8_t
  * binding at load time. */
 int dtc_contain_envs_abi_sizes(int64_t* out, int cap);
 
+/* ---- containment of non-finite envs AT THE ROLLOUT STEP (contain_nonfinite_act=True of all three trainers) ----------------------
+ * One launch behind the policy step of act(), in front of env.step(): an env whose step consumed or produced anything non-finite
+ * leaves act() with finite (zero) actions and a cleared live recurrent state, and is named in two device-side masks. */
+/* One fp32 tensor with an env dimension as `outer` rows per env: element (o, n, j), j < width, sits at
+ * base + o * outer_stride_elems + n * env_stride_elems + j (counted in 4-byte elements).  [N]: outer = 1, width = 1; [N, w]: outer = 1;
+ * live states [L, N, H]: outer = L.  mode 0: the item is scanned only; mode 1: scanned, then zeroed at every bad env. */
+typedef struct DtcActItem {
+    void* base;
+    int64_t outer;
+    int64_t outer_stride_elems;              /* not read where outer == 1 */
+    int64_t env_stride_elems;
+    int32_t width;
+    int32_t mode;
+} DtcActItem;
+/* For every env n of [0, N): bad(n) = any element of any item at env n, over all outer indices, has all exponent bits set (NaN,
+ * +-inf).  act_valid_row[n] = !bad(n) and env_bad[n] = bad(n) (uint8 on the device, each may be NULL, each written for EVERY env, 0 or
+ * 1); where bad(n), every element of every mode-1 item at env n becomes +0.0f.  Nothing else is written: a good env's bytes stay as
+ * they are in every item, a mode-0 item is never written.  `items` is a HOST array of n_items (1..dtc_act_contain_cap()) descriptors.
+ * One wavefront owns an env: no atomics, no second launch, the result does not depend on scheduling; rows are accessed 16 bytes at a
+ * time over their 16-byte aligned middle, whatever their width and start.  The kernel trusts the descriptors; rejected with
+ * DTC_ERR_ARG before any launch: null `items`, n_items outside 1..cap, N outside 1..2^31, a null or not 4-byte aligned base,
+ * width < 1, outer < 1, env_stride_elems < width, outer > 1 with outer_stride_elems < width, a mode other than 0 / 1, and a call
+ * with both outputs NULL and no mode-1 item (nothing to do); also what would overflow the 64-bit element offsets: outer > 2^20,
+ * env_stride_elems > 2^31, outer_stride_elems > 2^40 (where outer > 1). */
+int dtc_act_contain_cap(void);
+int dtc_act_contain(const DtcActItem* items, int n_items, int64_t N, uint8_t* act_valid_row, uint8_t* env_bad, void* stream);
+/* sizeof() of DtcActItem, in a table of its own (dtc_abi_sizes keeps its 18 entries, dtc_contain_envs_abi_sizes its one): compared by
+ * the binding at load time. */
+int dtc_act_contain_abi_sizes(int64_t* out, int cap);
+
 /* ---- mini-batch gather: rollout_storage.py:195-209 (`tensor[batch_idx]`) ------------------ */
 int dtc_gather_rows(const void* src, const int64_t* idx, void* dst, int64_t rows, int64_t row_bytes,
                     void* stream);
@@ -550,6 +580,15 @@ int dtc_linear_fwd_amax(const DtcSegMat* X, const float* W, const float* b, floa
  * dtc_amd/ops.py sets it from DTC_GEMM_SPLIT. */
 void dtc_set_gemm_split(int on);
 int dtc_get_gemm_split(void);
+/* The two-term fp16 calls scale an operand that brings no amax record by the largest |x| of the tensor, computed by the call.  Off
+ * (default): over every element -- one NaN or inf in the operand makes the exponent, and with it every row of the product, useless.  On:
+ * over the FINITE elements only, so that a non-finite element stays in its row of the product (it converts to fp16 inf / NaN there); on
+ * finite operands both settings give the same bits.  Set around the rollout step by the trainers under contain_nonfinite_act.
+ * It is ONE host variable of the process, read when a call launches its amax kernel: not per thread, not per stream -- a second thread
+ * that launches two-term calls while it is on gets the finite-only amax too -- and a graph captured while it is on keeps the value it
+ * was captured with at every replay, whatever the switch says then. */
+void dtc_set_amax_finite_only(int on);
+int dtc_get_amax_finite_only(void);
 /* Weight image: the W operand of a split-path call as the kernel's LDS planes -- for every 128-column tile and 16-k stage one
  * 12 KiB chunk [plane 3][row 128][16 k bf16], copied into LDS by LDS-DMA (no conversion work for W inside the K loop).  Built by
  * the call itself into `wplanes` (wimage_ready = 0; scratch of dtc_s3_planes_bytes(N, K) bytes -- for the data gradient
