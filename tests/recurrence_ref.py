@@ -179,6 +179,12 @@ def s_rel_bias(db, ref, dZ):
     return _over((db - ref).abs(), dZ.abs().sum(0))
 
 
+def s_rel_terms(got, ref, S):
+    """max |got - ref| / S over the elements with S > 0, for a caller-supplied S of got's shape: the sum of the magnitudes of every
+    element's own terms (a dense layer's |X| |W|^T + |b|), so a small element is judged against what it was added up from."""
+    return _over((_d(got) - _d(ref)).abs(), _d(S))
+
+
 def measure(cell, got, ref):
     """every quantity of `got` (a dict shaped like the reference's) against the fp64 reference `ref`
     -> ({quantity: error}, {quantity: all-zero reference rows}).  hs / cs are measured behind the initial state.
