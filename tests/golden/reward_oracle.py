@@ -9,6 +9,10 @@ reference does, so that it can be matched exactly.
 Inputs `s`: dict of numpy arrays keyed by the env's attribute names.  State `st` (read and written):
 feet_air_time [N,4], last_contacts [N,4] bool, stumble [N,4] uint8 (bit k = the stumble mask pushed k steps ago;
 the 5-deep list of :1485), pitch_est [N].
+
+`term` / `compute_reward` take a working precision `wp`: float64 (the default: the yardstick) or float32, whose distance from
+the float64 run on the same inputs is the yardstick's own fp32 rounding error (tests/reward_cases.py builds the bound of every
+comparison from it).  `state(s, wp)` hands out the state in that precision.
 """
 import itertools
 
@@ -72,31 +76,43 @@ def _quat_rotate_inverse(q, v):
     return v * (2.0 * w * w - 1.0) - np.cross(qv, v) * w * 2.0 + qv * np.sum(qv * v, axis=-1, keepdims=True) * 2.0
 
 
-def _orientation(s, cfg, st):
+def _orientation(s, cfg, st, wp=np.float64):
     """Shared part of _reward_orientation / _reward_orientation_roll (legged_robot.py:1559-1596): updates pitch_est and
     returns the gravity direction of the fitted plane in the estimated base frame."""
-    h = s["measured_heights"].astype(np.float64)
-    ax, by = h @ cfg["plane"][0], h @ cfg["plane"][1]
+    h = s["measured_heights"].astype(wp)
+    plane = np.asarray(cfg["plane"], dtype=wp)
+    ax, by = h @ plane[0], h @ plane[1]
     n = np.sqrt(ax * ax + by * by + 1.0)
     pitch, roll = np.arctan(-ax / n), -np.arctan(-by / n)          # p_norm = -plane_vector
     lim = f32(0.1)
-    pitch_c = np.where((pitch >= -lim) & (pitch <= lim), 0.0, pitch)
-    roll_c = np.where((roll >= -lim) & (roll <= lim), 0.0, roll)
+    pitch_c = np.where((pitch >= -lim) & (pitch <= lim), wp(0.0), pitch)
+    roll_c = np.where((roll >= -lim) & (roll <= lim), wp(0.0), roll)
     st["pitch_est"] = st["pitch_est"] * f32(0.2) + f32(0.8) * pitch_c
     q = _quat_from_euler_xyz(roll_c, st["pitch_est"], np.zeros_like(roll_c))
-    grav = np.tile(np.array([0.0, 0.0, -1.0]), (len(q), 1))
+    grav = np.tile(np.array([0.0, 0.0, -1.0], dtype=wp), (len(q), 1))
     return _quat_rotate_inverse(q, grav)
 
 
-def term(name, s, cfg, st):
-    """Value of `_reward_<name>` (before the scale), float64 [N]; updates `st` as the reference updates the env."""
+def state(s, wp=np.float64):
+    """Copies of the reward state of `s` for `term` / `compute_reward`, the float items in working precision `wp`.  `term`
+    advances feet_air_time and pitch_est in the dtype they come in: handed the env's own fp32 arrays, a float64 run does those
+    updates in fp32."""
+    return {k: (s[k].astype(wp) if s[k].dtype.kind == "f" else s[k].copy()) for k in STATE}
+
+
+def term(name, s, cfg, st, wp=np.float64):
+    """Value of `_reward_<name>` (before the scale), `wp` [N]; updates `st` as the reference updates the env.  `wp` is the
+    working precision: float64 (the yardstick) or float32 (the yardstick's own rounding error: every input, constant and
+    intermediate in fp32, summed in numpy's order).  Constants enter as Python floats rounded to `wp`, which leave an array's
+    dtype alone."""
+    k = lambda x: float(wp(x))                                               # noqa: E731
     F = cfg["feet_indices"]
-    cf = s["contact_forces"].astype(np.float64)
+    cf = s["contact_forces"].astype(wp)
     cff = cf[:, F]
-    cmd = s["commands"].astype(np.float64)
+    cmd = s["commands"].astype(wp)
     cmd_norm = _norm(cmd[:, :2])
-    dt = cfg["dt"]
-    g = lambda k: s[k].astype(np.float64)                                    # noqa: E731
+    dt = k(cfg["dt"])
+    g = lambda key: s[key].astype(wp)                                        # noqa: E731
     if name == "lin_vel_z":                                                  # :1321
         return g("base_lin_vel")[:, 2] ** 2
     if name == "ang_vel_xy":                                                 # :1325
@@ -110,21 +126,21 @@ def term(name, s, cfg, st):
     if name == "action_rate":                                                # :1620 (= :1346)
         return np.sum((g("last_actions") - g("actions")) ** 2, axis=1)
     if name == "collision":                                                  # :1350
-        return np.sum(_norm(cf[:, cfg["penalised_contact_indices"]]) > f32(0.1), axis=1).astype(np.float64)
+        return np.sum(_norm(cf[:, cfg["penalised_contact_indices"]]) > f32(0.1), axis=1).astype(wp)
     if name == "termination":                                                # :1354
-        return (s["reset_buf"].astype(bool) & ~s["time_out_buf"].astype(bool)).astype(np.float64)
+        return (s["reset_buf"].astype(bool) & ~s["time_out_buf"].astype(bool)).astype(wp)
     if name == "dof_pos_limits":                                             # :1358
         q, lim = g("dof_pos"), g("dof_pos_limits")
         return np.sum(-np.minimum(q - lim[:, 0], 0.0) + np.maximum(q - lim[:, 1], 0.0), axis=1)
     if name == "dof_vel_limits":                                             # :1364
-        return np.sum(np.clip(np.abs(g("dof_vel")) - g("dof_vel_limits") * cfg["soft_dof_vel_limit"], 0.0, 1.0), axis=1)
+        return np.sum(np.clip(np.abs(g("dof_vel")) - g("dof_vel_limits") * k(cfg["soft_dof_vel_limit"]), 0.0, 1.0), axis=1)
     if name == "torque_limits":                                              # :1369
-        return np.sum(np.maximum(np.abs(g("torques")) - g("torque_limits") * cfg["soft_torque_limit"], 0.0), axis=1)
+        return np.sum(np.maximum(np.abs(g("torques")) - g("torque_limits") * k(cfg["soft_torque_limit"]), 0.0), axis=1)
     if name == "tracking_lin_vel":                                           # :1373
-        e = np.sum(((cmd[:, :2] - g("base_lin_vel")[:, :2]) / cfg["lin_vel_x_max"]) ** 2, axis=1)
-        return np.exp(-e / cfg["tracking_sigma"])
+        e = np.sum(((cmd[:, :2] - g("base_lin_vel")[:, :2]) / k(cfg["lin_vel_x_max"])) ** 2, axis=1)
+        return np.exp(-e / k(cfg["tracking_sigma"]))
     if name == "tracking_ang_vel":                                           # legged_robot_dtc.py:571 (= :1380)
-        return np.exp(-(cmd[:, 2] - g("base_ang_vel")[:, 2]) ** 2 / cfg["tracking_sigma"])
+        return np.exp(-(cmd[:, 2] - g("base_ang_vel")[:, 2]) ** 2 / k(cfg["tracking_sigma"]))
     if name == "feet_air_time":                                              # :1386-1412
         contact = cff[:, :, 2] > 1.0
         cfilt = contact | st["last_contacts"]
@@ -135,12 +151,12 @@ def term(name, s, cfg, st):
         st["feet_air_time"] = st["feet_air_time"] * ~cfilt
         return rew
     if name in ("stumble", "feet_stumble"):                                  # :1417 / legged_robot_dtc.py:526
-        k = 5.0 if name == "stumble" else 3.0
-        return np.any(_norm(cff[:, :, :2]) > k * np.abs(cff[:, :, 2]), axis=1).astype(np.float64)
+        m = 5.0 if name == "stumble" else 3.0
+        return np.any(_norm(cff[:, :, :2]) > m * np.abs(cff[:, :, 2]), axis=1).astype(wp)
     if name == "stand_still":                                                # :1422
         return np.sum(np.abs(g("dof_pos") - g("default_dof_pos").reshape(1, -1)), axis=1) * (cmd_norm < f32(0.1))
     if name == "feet_contact_forces":                                        # :1426
-        return np.sum(np.maximum(_norm(cff) - cfg["max_contact_force"], 0.0), axis=1)
+        return np.sum(np.maximum(_norm(cff) - k(cfg["max_contact_force"]), 0.0), axis=1)
     if name == "power":                                                      # :1435
         return np.sum(np.maximum(g("torques") * g("dof_vel"), 0.0), axis=1)
     if name == "smooth":                                                     # :1440
@@ -149,7 +165,7 @@ def term(name, s, cfg, st):
         stumb = _norm(cff[:, :, :2]) > 4 * np.abs(cff[:, :, 2])
         st["stumble"] = ((st["stumble"].astype(np.uint8) << 1) | stumb.astype(np.uint8)) & np.uint8(0x1F)
         flag = st["stumble"] != 0
-        return np.sum(~flag & (g("measured_foot_clearance") > f32(0.18)), axis=1).astype(np.float64)
+        return np.sum(~flag & (g("measured_foot_clearance") > f32(0.18)), axis=1).astype(wp)
     if name == "feet_slip":                                                  # :1494
         cfilt = (cff[:, :, 2] > 1.0) | st["last_contacts"]
         return np.sum(cfilt * np.sum(g("foot_velocities")[:, :, :2] ** 2, axis=-1), axis=1)
@@ -157,58 +173,59 @@ def term(name, s, cfg, st):
         return np.sum(g("dof_pos")[:, cfg["hip_indices"]] ** 2, axis=1)
     if name == "powerchange":                                                # :1613 (= :1507)
         smooth_co = np.maximum(cmd[:, 0], 1.0)
-        return (np.sum(np.maximum(g("torques") * g("dof_vel"), 0.0), axis=1) / (g("robot_mass") * 9.815 * smooth_co)) ** 2
+        return (np.sum(np.maximum(g("torques") * g("dof_vel"), 0.0), axis=1) / (g("robot_mass") * k(9.815) * smooth_co)) ** 2
     if name == "pos_acc":                                                    # :1600 (the later definition: half-extents / 2)
-        pts = (np.array(list(itertools.product([-1, 1], repeat=3))) * [0.3, 0.2, 0.15] / 2.0).astype(np.float32).astype(np.float64)
+        pts = (np.array(list(itertools.product([-1, 1], repeat=3))) * [0.3, 0.2, 0.15] / 2.0).astype(np.float32).astype(wp)
         v = g("base_lin_vel")[:, None, :] + np.cross(g("base_ang_vel")[:, None, :], pts[None])
         return np.sum(np.sum(v * v, axis=-1), axis=1)
     if name == "foot_acc":                                                   # :1525
-        mask = np.where(s["terrain_levels"] > 5, f32(0.2), 1.0)
+        mask = np.where(s["terrain_levels"] > 5, f32(0.2), 1.0).astype(wp)
         a = _norm((g("last_foot_velocities") - g("foot_velocities")) / dt)
-        return np.sum(np.maximum(mask[:, None] * (a - cfg["max_acc"]), 0.0), axis=1)
+        return np.sum(np.maximum(mask[:, None] * (a - k(cfg["max_acc"])), 0.0), axis=1)
     if name == "orientation":                                                # :1559
-        p = _orientation(s, cfg, st)
+        p = _orientation(s, cfg, st, wp)
         return (g("projected_gravity")[:, 0] - p[:, 0]) ** 2
     if name == "orientation_roll":                                           # :1579
-        p = _orientation(s, cfg, st)
+        p = _orientation(s, cfg, st, wp)
         return np.abs(g("projected_gravity")[:, 1] - p[:, 1])
     if name == "big_pitch":                                                  # legged_robot_dtc.py:522
-        return (np.abs(g("projected_gravity")[:, 0]) > f32(0.6)).astype(np.float64)
+        return (np.abs(g("projected_gravity")[:, 0]) > f32(0.6)).astype(wp)
     if name == "base_height":                                                # legged_robot_dtc.py:531
         fp = g("foot_positions")
-        return (g("root_states")[:, 2] - np.mean(fp[:, :, 2], axis=-1) - cfg["base_height_target"]) ** 2
+        return (g("root_states")[:, 2] - np.mean(fp[:, :, 2], axis=-1) - k(cfg["base_height_target"])) ** 2
     if name == "foothold_miss":                                              # legged_robot_dtc.py:536
-        return (np.min(g("foot_positions")[:, :, 2], axis=-1) < 0).astype(np.float64)
+        return (np.min(g("foot_positions")[:, :, 2], axis=-1) < 0).astype(wp)
     if name == "soft_tracking_lin_vel":                                      # legged_robot_dtc.py:542 (sic: ONE velocity row)
-        d = (g("cmd_buffer")[-3:, :, :2] - g("lin_vel_buffer")[-3, :, :2]) / cfg["lin_vel_x_max"]
-        return np.mean(np.exp(-np.sum(d * d, axis=-1) / cfg["tracking_sigma"]), axis=0)
+        d = (g("cmd_buffer")[-3:, :, :2] - g("lin_vel_buffer")[-3, :, :2]) / k(cfg["lin_vel_x_max"])
+        return np.mean(np.exp(-np.sum(d * d, axis=-1) / k(cfg["tracking_sigma"])), axis=0)
     if name == "soft_tracking_ang_vel":                                      # legged_robot_dtc.py:555
-        d = ((g("cmd_buffer")[-4:, :, 2] - g("ang_vel_buffer")[-4:, :, 0]) / cfg["ang_vel_yaw_max"]) ** 2
-        d = np.where(d <= f32(0.15 ** 2), 0.0, 1.0)
-        return np.mean(np.exp(-d / cfg["tracking_sigma"]), axis=0)
+        d = ((g("cmd_buffer")[-4:, :, 2] - g("ang_vel_buffer")[-4:, :, 0]) / k(cfg["ang_vel_yaw_max"])) ** 2
+        d = np.where(d <= f32(0.15 ** 2), 0.0, 1.0).astype(wp)
+        return np.mean(np.exp(-d / k(cfg["tracking_sigma"])), axis=0)
     if name == "tracking_optimal_footholds":                                 # legged_robot_dtc.py:577
         fp, opt = g("foot_positions"), g("optimal_footholds_world")
-        r = -np.log(0.8 + _norm(fp[:, :, :2] - opt[:, :, :2]))
-        return np.sum(np.where(s["contact_filt"].astype(bool), r, 0.0), axis=-1)
+        r = -np.log(k(0.8) + _norm(fp[:, :, :2] - opt[:, :, :2]))
+        return np.sum(np.where(s["contact_filt"].astype(bool), r, wp(0.0)), axis=-1)
     raise KeyError(name)
 
 
-def compute_reward(s, cfg, st, episode_sums):
+def compute_reward(s, cfg, st, episode_sums, wp=np.float64):
     """legged_robot.py:274-291.  cfg["scales"]: {name: fp32(scale * dt)} of the active terms in the reference's order
-    (termination included).  Updates `st` and `episode_sums` ({name: float64 [N]}); returns (rew_buf, {name: term * scale})."""
+    (termination included).  Updates `st` and `episode_sums` ({name: `wp` [N]}); returns (rew_buf, {name: term * scale}), all
+    in the working precision `wp` (see `term`)."""
     N = s["root_states"].shape[0]
-    rew = np.zeros(N)
+    rew = np.zeros(N, dtype=wp)
     per = {}
     for name, scale in cfg["scales"].items():
         if name == "termination":
             continue
-        per[name] = term(name, s, cfg, st) * scale
+        per[name] = term(name, s, cfg, st, wp) * float(wp(scale))
         rew = rew + per[name]
         episode_sums[name] = episode_sums[name] + per[name]
     if cfg["only_positive_rewards"]:
         rew = np.maximum(rew, 0.0)
     if "termination" in cfg["scales"]:
-        per["termination"] = term("termination", s, cfg, st) * cfg["scales"]["termination"]
+        per["termination"] = term("termination", s, cfg, st, wp) * float(wp(cfg["scales"]["termination"]))
         rew = rew + per["termination"]
         episode_sums["termination"] = episode_sums["termination"] + per["termination"]
     return rew, per
