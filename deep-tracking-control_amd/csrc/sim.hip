@@ -1,0 +1,342 @@
+// Surrogate legged env for gfx950: the state the env kernels (csrc/foothold.hip, rewards.hip, reset.hip, envstep.hip) run on when no
+// simulator stands behind them.  dtc_sim_step (include/dtc_hip.h states every operation and its order) is one env step as ONE launch:
+// `decimation` substeps of the PD law of LeggedRobot._compute_torques, control type "P" (legged_gym/envs/base/legged_robot.py:610-630),
+// explicit joint integration with hard position limits, legs that are linear in the joint angles around the default pose, a base that
+// only yaws and rides on its stance feet over the int16 terrain table (_get_heights, :1301-1316), its planar twist as the
+// least-squares fit of "stance feet do not slip", then the bookkeeping of post_physics_step up to the planner
+// (legged_robot_dtc.py:66-91, legged_robot.py:534-535 with _resample_commands :573-591, and :562-564).
+//
+// It is a surrogate, not physics.  Deliberately absent: roll and pitch (quaternion x = y = 0, projected gravity (0, 0, -1)), base
+// dynamics (no free flight: at least one foot is always in contact), lag buffers (the current action stands where the reference takes
+// a randomly lagged one), pushes (`forces` are never touched), control types "V" and "T", and the heading command's yaw law
+// (legged_robot.py:537-539), which stays with the caller.
+//
+// One 64-lane wavefront per env, 4 envs per 256-thread workgroup (as csrc/envstep.hip).  Lanes 0..11 own the joints (leg l owns
+// 3l..3l+2) and lane 3l+i computes component i of foot l; the twelve foot components are then broadcast with v_readlane and every lane
+// carries the same base state
+// through the substep, so the whole decimation loop runs in registers: each env row is loaded once, ahead of the loop, and stored once,
+// after it.  Only the terrain table is read inside the loop.  No atomics, no LDS, no scratch (every register array is indexed by
+// unrolled constants).  Latency bound: ~0.8 KB read and ~1.2 KB written per env.  -ffp-contract=off (build.py): every value is one
+// single-rounded fp32 operation in the stated order, sums over legs run in leg order from 0.0f, and tests/sim_oracle.py restates the
+// step in numpy float32 bit for bit.
+#include <cstddef>
+
+#include "common.hpp"
+#include "philox.hpp"
+
+namespace {
+
+struct Span { float span, lo; };            // a range [lo, hi] as fp32 scalars: float32(hi - lo), float32(lo)
+
+struct SimK {
+    int B, C, dec, heading, T;
+    int feet[4], thighs[4];
+    long long resample;
+    float dt, half_dt, action_scale, clip, inertia, eps, weight, rmin2;
+    int rows, cols;
+    float border, hscale, vscale;
+    Span cmd_x, cmd_y, cmd_third;
+    unsigned seed_lo, seed_hi, ctr_lo, ctr_hi;
+};
+
+__device__ __forceinline__ float bcast(float v, int src_lane) {                    // src_lane is wave-uniform
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src_lane));
+}
+
+// _get_heights (legged_robot.py:1301-1316) for one world point; the clamp keeps every index inside the table whatever fx, fy hold
+__device__ __forceinline__ float terrain_height(const int16_t* __restrict__ hs, const SimK& k, float fx, float fy) {
+    const float wx = (fx + k.border) / k.hscale;
+    const float wy = (fy + k.border) / k.hscale;
+    long long cx = (long long)wx, cy = (long long)wy;                              // .long(): truncation toward zero
+    cx = cx < 0 ? 0 : (cx > k.rows - 2 ? k.rows - 2 : cx);
+    cy = cy < 0 ? 0 : (cy > k.cols - 2 ? k.cols - 2 : cy);
+    const int16_t h1 = hs[cx * k.cols + cy], h2 = hs[(cx + 1) * k.cols + cy], h3 = hs[cx * k.cols + cy + 1];
+    int16_t h = h1 < h2 ? h1 : h2;
+    h = h < h3 ? h : h3;
+    return (float)h * k.vscale;
+}
+
+// INVARIANTS of this kernel's signature and launch:
+//  * the descriptor `s` is the FIRST parameter, so it lies at offset 0 of the kernel-argument segment: the rows written after the
+//    loop take their pointers from there (see below).  A parameter put in front of it breaks that silently; keep the order.
+//  * one wavefront owns one env row and no other wavefront touches it (grid = ceil(N / 4) workgroups of 4 wavefronts, n from the
+//    wavefront's index): the ring-buffer shift below has lanes load slot t + 1 and store slot t of the same env, which is right
+//    only because a wavefront's loads issue ahead of its stores and nobody else writes those slots.
+static_assert(offsetof(DtcSimStep, actions_in) == 0 && sizeof(DtcSimStep) % 8 == 0, "descriptor layout the late loads rely on");
+__global__ __launch_bounds__(256) void sim_step_kernel(const DtcSimStep s, const SimK k, int N) {
+    const int lane = threadIdx.x & 63;
+    const int n = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+    if (n >= N) return;
+    const long long e = n;
+    const int D = 12;
+    const bool joint = lane < D;
+
+    // ---- the env's rows and the tables, once
+    float act = 0.f, kp = 0.f, kd = 0.f, strength = 0.f, off = 0.f, limit = 0.f, lo = 0.f, hi = 0.f, dflt = 0.f, q = 0.f, qd = 0.f;
+    float J0 = 0.f, J1 = 0.f, J2 = 0.f, nom = 0.f;                                 // lane 3 l + i: row i of leg l's Jacobian, foot_nominal[l][i]
+    if (joint) {
+        act = s.actions_in[e * D + lane];
+        kp = s.p_gains[lane] * s.Kp_factors[e * D + lane];
+        kd = s.d_gains[lane] * s.Kd_factors[e * D + lane];
+        strength = s.motor_strengths[e * D + lane];
+        off = s.motor_offsets[e * D + lane];
+        limit = s.torque_limits[lane];
+        lo = s.dof_pos_limits[lane * 2];
+        hi = s.dof_pos_limits[lane * 2 + 1];
+        dflt = s.default_dof_pos[lane];
+        q = s.dof_pos[e * s.dof_pos_row_stride + lane * s.dof_pos_elem_stride];
+        qd = s.dof_vel[e * s.dof_vel_row_stride + lane * s.dof_vel_elem_stride];
+        J0 = s.leg_jacobian[lane * 3], J1 = s.leg_jacobian[lane * 3 + 1], J2 = s.leg_jacobian[lane * 3 + 2];
+        nom = s.foot_nominal[lane];
+    }
+    const int leg0 = joint ? (lane / 3) * 3 : 0;                                   // first joint lane of this lane's leg
+    const float* rs = s.root_states + e * 13;
+    float x = rs[0], y = rs[1], z = rs[2], qz = rs[5], qw = rs[6];
+    float old_ang = 0.f;
+    if (lane < 3) old_ang = s.base_ang_vel[e * 3 + lane];
+    const long long elen = s.episode_length_buf[e] + 1;
+    unsigned char last_c = 0;
+    if (lane < 4) last_c = s.last_contacts[e * 4 + lane];
+
+    const float a = fminf(fmaxf(act, -k.clip), k.clip);
+    const float goal = fminf(fmaxf(a * k.action_scale + dflt, lo), hi);
+
+    float tau = 0.f, p[4][3], u[4][3], w = 0.f, vbx = 0.f, vby = 0.f, vz = 0.f, nc = 0.f;
+    bool ct[4];
+#pragma unroll
+    for (int l = 0; l < 4; ++l) {
+        ct[l] = false;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) p[l][i] = 0.f, u[l][i] = 0.f;
+    }
+    for (int it = 0; it < k.dec; ++it) {
+        // 1. PD law, 2. joint integration with hard limits (joint lanes)
+        tau = fminf(fmaxf(((kp * ((goal - q) + off)) - kd * qd) * strength, -limit), limit);
+        qd = qd + (tau / k.inertia) * k.dt;
+        q = q + qd * k.dt;
+        if (q < lo) q = lo, qd = 0.f;
+        if (q > hi) q = hi, qd = 0.f;
+        const float dq = q - dflt;
+        // 3. linear leg kinematics: lane 3 l + i computes component i of leg l, then every lane takes all twelve
+        const float a0 = __shfl(dq, leg0, 64), a1 = __shfl(dq, leg0 + 1, 64), a2 = __shfl(dq, leg0 + 2, 64);
+        const float v0 = __shfl(qd, leg0, 64), v1 = __shfl(qd, leg0 + 1, 64), v2 = __shfl(qd, leg0 + 2, 64);
+        const float pl = nom + ((J0 * a0 + J1 * a1) + J2 * a2);
+        const float ul = (J0 * v0 + J1 * v1) + J2 * v2;
+#pragma unroll
+        for (int l = 0; l < 4; ++l)
+#pragma unroll
+            for (int i = 0; i < 3; ++i) p[l][i] = bcast(pl, 3 * l + i), u[l][i] = bcast(ul, 3 * l + i);
+        // 4. yaw-only base, 5. terrain under each foot, 6. support and contact
+        const float c = 1.0f - 2.0f * (qz * qz), sn = 2.0f * (qz * qw);
+        float h[4];
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            const float fx = x + (c * p[l][0] - sn * p[l][1]);
+            const float fy = y + (sn * p[l][0] + c * p[l][1]);
+            h[l] = terrain_height(s.height_samples, k, fx, fy);
+        }
+        float bz = h[0] - p[0][2];
+#pragma unroll
+        for (int l = 1; l < 4; ++l) bz = fmaxf(bz, h[l] - p[l][2]);
+        nc = 0.f;
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            ct[l] = ((bz + p[l][2]) - h[l]) <= k.eps;
+            nc = nc + (ct[l] ? 1.0f : 0.0f);
+        }
+        // 7. base twist: planar least squares of v_b + w z^ x p_l + u_l = 0 over the stance feet
+        float spx = 0.f, spy = 0.f, sux = 0.f, suy = 0.f;
+#pragma unroll
+        for (int l = 0; l < 4; ++l)
+            if (ct[l]) spx = spx + p[l][0], spy = spy + p[l][1], sux = sux + u[l][0], suy = suy + u[l][1];
+        const float pmx = spx / nc, pmy = spy / nc, umx = sux / nc, umy = suy / nc;
+        float num = 0.f, den = 0.f;
+#pragma unroll
+        for (int l = 0; l < 4; ++l)
+            if (ct[l]) {
+                const float dpx = p[l][0] - pmx, dpy = p[l][1] - pmy, dux = u[l][0] - umx, duy = u[l][1] - umy;
+                num = num + (dpx * duy - dpy * dux);
+                den = den + (dpx * dpx + dpy * dpy);
+            }
+        w = den > k.rmin2 ? -(num / den) : 0.0f;
+        vbx = (-umx) + w * pmy;
+        vby = (-umy) - w * pmx;
+        // 8. integrate the base
+        x = x + (c * vbx - sn * vby) * k.dt;
+        y = y + (sn * vbx + c * vby) * k.dt;
+        vz = (bz - z) / k.dt;
+        z = bz;
+        const float ee = k.half_dt * w;
+        const float zn = qz + ee * qw, wn = qw - ee * qz;
+        const float r = sqrtf(zn * zn + wn * wn);
+        qz = zn / r;
+        qw = wn / r;
+    }
+
+    // ---- the env's rows, once.  Every load of the bookkeeping below that another lane's store could change is issued first.
+    // The 39 pointers of the descriptor and the constants do not fit the scalar registers at once: the rows written from here on take
+    // their pointers from the kernel-argument segment (the descriptor is its first member) behind a barrier the compiler cannot
+    // hoist the loads across, so they are not held through the loop above.
+    unsigned long long args = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(args));
+    const __attribute__((address_space(4))) DtcSimStep* o = (const __attribute__((address_space(4))) DtcSimStep*)args;
+    const int C = k.C, T = k.T;
+    const float cmd_old = lane < C ? o->commands[e * C + lane] : 0.f;               // the commands as they stand (cmd_buffer[-1])
+    const float c = 1.0f - 2.0f * (qz * qz), sn = 2.0f * (qz * qw);
+    const float Vx = c * vbx - sn * vby, Vy = sn * vbx + c * vby;
+    const float fz = k.weight / nc;
+
+    if (joint) {
+        o->dof_pos[e * o->dof_pos_row_stride + lane * o->dof_pos_elem_stride] = q;
+        o->dof_vel[e * o->dof_vel_row_stride + lane * o->dof_vel_elem_stride] = qd;
+        o->torques[e * D + lane] = tau;
+        o->actions[e * D + lane] = a;
+    }
+    if (lane < 13) {
+        float v = 0.f;
+        v = lane == 0 ? x : v, v = lane == 1 ? y : v, v = lane == 2 ? z : v, v = lane == 5 ? qz : v, v = lane == 6 ? qw : v;
+        v = lane == 7 ? Vx : v, v = lane == 8 ? Vy : v, v = lane == 9 ? vz : v, v = lane == 12 ? w : v;
+        o->root_states[e * 13 + lane] = v;
+    }
+    if (lane < 3) {
+        o->base_lin_vel[e * 3 + lane] = lane == 0 ? vbx : (lane == 1 ? vby : vz);
+        o->last_base_ang_vel[e * 3 + lane] = old_ang;
+        o->base_ang_vel[e * 3 + lane] = lane == 2 ? w : 0.0f;
+        o->projected_gravity[e * 3 + lane] = lane == 2 ? -1.0f : 0.0f;
+        o->base_pos[e * 3 + lane] = lane == 0 ? x : (lane == 1 ? y : z);
+    }
+    if (lane < 4) o->base_quat[e * 4 + lane] = lane == 2 ? qz : (lane == 3 ? qw : 0.0f);
+    // foot rows (lanes 16 + 6 l + i: position i < 3, velocity i >= 3) and thigh rows (lanes 40 + 3 l + i) of rigid_body_state
+#pragma unroll
+    for (int l = 0; l < 4; ++l) {
+        const float rx = u[l][0] - w * p[l][1], ry = u[l][1] + w * p[l][0];
+        const float f0 = x + (c * p[l][0] - sn * p[l][1]), f1 = y + (sn * p[l][0] + c * p[l][1]), f2 = z + p[l][2];
+        const float g0 = Vx + (c * rx - sn * ry), g1 = Vy + (sn * rx + c * ry), g2 = vz + u[l][2];
+        const int i = lane - (16 + 6 * l);
+        if (i >= 0 && i < 6) {
+            const float v = i == 0 ? f0 : (i == 1 ? f1 : (i == 2 ? f2 : (i == 3 ? g0 : (i == 4 ? g1 : g2))));
+            o->rigid_body_state[(e * k.B + k.feet[l]) * 13 + (i < 3 ? i : i + 4)] = v;
+        }
+    }
+    if (lane >= 40 && lane < 52) {
+        const int l = (lane - 40) / 3, m = lane - 40 - 3 * l;
+        const float hx = o->hip_offset[l * 3], hy = o->hip_offset[l * 3 + 1], hz = o->hip_offset[l * 3 + 2];
+        const float t0 = x + (c * hx - sn * hy), t1 = y + (sn * hx + c * hy), t2 = z + hz;
+        const float v = m == 0 ? t0 : (m == 1 ? t1 : t2);
+#pragma unroll
+        for (int ll = 0; ll < 4; ++ll)                                             // constant index into the by-value struct
+            if (l == ll) o->rigid_body_state[(e * k.B + k.thighs[ll]) * 13 + m] = v;
+    }
+    for (int i = lane; i < k.B * 3; i += 64) {
+        float v = 0.f;
+#pragma unroll
+        for (int l = 0; l < 4; ++l) v = (i == k.feet[l] * 3 + 2 && ct[l]) ? fz : v;
+        o->contact_forces[e * k.B * 3 + i] = v;
+    }
+
+    // ---- bookkeeping, in the reference's order: episode length, the ring buffers [T, N, .] (each env shifts its own T entries:
+    // 64 entries are loaded, then stored one slot down), the command resample, the contact filter
+    for (int i0 = 0; i0 < T * 2; i0 += 64) {
+        const int i = i0 + lane, t = i >> 1, col = i & 1;
+        if (i < T * 2) {
+            const float v = t + 1 < T ? o->lin_vel_buffer[((long long)(t + 1) * N + e) * 2 + col] : (col == 0 ? vbx : vby);
+            o->lin_vel_buffer[((long long)t * N + e) * 2 + col] = v;
+        }
+    }
+    for (int i0 = 0; i0 < T; i0 += 64) {
+        const int t = i0 + lane;
+        if (t < T) {
+            const float v = t + 1 < T ? o->ang_vel_buffer[(long long)(t + 1) * N + e] : w;
+            o->ang_vel_buffer[(long long)t * N + e] = v;
+        }
+    }
+    for (int i0 = 0; i0 < T * C; i0 += 64) {
+        const int i = i0 + lane, t = i / C, col = i - t * C;
+        const float newest = __shfl(cmd_old, col, 64);                             // by every lane: the source lanes must be active
+        if (i < T * C) {
+            const float v = t + 1 < T ? o->cmd_buffer[((long long)(t + 1) * N + e) * C + col] : newest;
+            o->cmd_buffer[((long long)t * N + e) * C + col] = v;
+        }
+    }
+    if (lane == 0) {
+        o->episode_length_buf[e] = elen;
+        if (elen % k.resample == 0) {                                              // _resample_commands, :573-591
+            float u0, u1, u2;
+            if (o->u_cmd) {
+                u0 = o->u_cmd[e * 3], u1 = o->u_cmd[e * 3 + 1], u2 = o->u_cmd[e * 3 + 2];
+            } else {
+                const U4 r = philox4x32_10(U4{(unsigned)n, 0u, k.ctr_lo, k.ctr_hi}, k.seed_lo, k.seed_hi);
+                u0 = (float)(r.x >> 8) * 5.9604644775390625e-08f;                  // [0, 1): 24 uniform bits
+                u1 = (float)(r.y >> 8) * 5.9604644775390625e-08f;
+                u2 = (float)(r.z >> 8) * 5.9604644775390625e-08f;
+            }
+            const float cx = k.cmd_x.span * u0 + k.cmd_x.lo;
+            const float cy = k.cmd_y.span * u1 + k.cmd_y.lo;
+            const float keep = sqrtf(cx * cx + cy * cy) > 0.1f ? 1.f : 0.f;
+            float* cm = o->commands + e * C;
+            cm[k.heading ? 3 : 2] = k.cmd_third.span * u2 + k.cmd_third.lo;
+            cm[0] = cx * keep;
+            cm[1] = cy * keep;
+        }
+    }
+    if (lane < 4) {                                                                // legged_robot.py:562-564
+        const unsigned stance = (ct[0] ? 1u : 0u) | (ct[1] ? 2u : 0u) | (ct[2] ? 4u : 0u) | (ct[3] ? 8u : 0u);
+        const bool contact = (((stance >> lane) & 1u) ? fz : 0.0f) > 1.0f;
+        o->contact_filt[e * 4 + lane] = (contact || last_c != 0) ? 1 : 0;
+        o->last_contacts[e * 4 + lane] = contact ? 1 : 0;
+    }
+}
+
+Span span_of(const double r[2]) { return Span{(float)(r[1] - r[0]), (float)r[0]}; }
+
+}  // namespace
+
+extern "C" int dtc_sim_abi_sizes(int64_t* out, int cap) {
+    const int64_t sz[] = {sizeof(DtcSimCfg), sizeof(DtcSimStep)};
+    for (int i = 0; i < 2 && i < cap && out; ++i) out[i] = sz[i];
+    return 2;
+}
+
+extern "C" int dtc_sim_step(const DtcSimStep* st, const DtcSimCfg* cfg, int N, void* stream) {
+    DTC_REQUIRE(st && cfg, "null descriptor");
+    DTC_REQUIRE(N > 0 && N <= (1 << 24), "N %d outside 1..2^24", N);
+    const DtcSimStep& s = *st;
+    const DtcSimCfg& c = *cfg;
+    DTC_REQUIRE(c.num_dof == 12, "num_dof %d: the surrogate has four legs of three joints", c.num_dof);
+    DTC_REQUIRE(c.num_bodies >= 1 && c.num_bodies <= (1 << 16), "num_bodies %d", c.num_bodies);
+    for (int l = 0; l < 4; ++l)
+        DTC_REQUIRE(c.feet[l] >= 0 && c.feet[l] < c.num_bodies && c.thighs[l] >= 0 && c.thighs[l] < c.num_bodies,
+                    "leg %d: foot body %d / thigh body %d outside 0..%d", l, c.feet[l], c.thighs[l], c.num_bodies - 1);
+    DTC_REQUIRE(c.num_commands >= (c.heading_command ? 4 : 3) && c.num_commands <= 64, "num_commands %d", c.num_commands);
+    DTC_REQUIRE(c.decimation >= 1 && c.decimation <= 64, "decimation %d outside 1..64", c.decimation);
+    DTC_REQUIRE(c.buffer_len >= 1 && c.buffer_len <= 64, "buffer_len %d outside 1..64", c.buffer_len);
+    DTC_REQUIRE(c.resampling_steps >= 1, "resampling_steps %lld", (long long)c.resampling_steps);
+    DTC_REQUIRE(c.sim_dt > 0.f && c.joint_inertia > 0.f && c.clip_actions >= 0.f && c.r_min >= 0.f, "sim_dt / joint_inertia / clip_actions / r_min");
+    DTC_REQUIRE(c.rows >= 2 && c.cols >= 2 && (int64_t)c.rows * c.cols < ((int64_t)1 << 31) && c.horizontal_scale > 0.f, "terrain table %d x %d",
+                c.rows, c.cols);
+    DTC_REQUIRE(s.actions_in && s.Kp_factors && s.Kd_factors && s.motor_strengths && s.motor_offsets && s.height_samples, "null per-env input");
+    DTC_REQUIRE(s.p_gains && s.d_gains && s.torque_limits && s.default_dof_pos && s.dof_pos_limits && s.hip_offset && s.foot_nominal &&
+                s.leg_jacobian, "null table");
+    DTC_REQUIRE(s.dof_pos && s.dof_vel && s.root_states && s.base_ang_vel && s.commands && s.episode_length_buf && s.last_contacts &&
+                s.lin_vel_buffer && s.ang_vel_buffer && s.cmd_buffer, "null state tensor");
+    DTC_REQUIRE(s.rigid_body_state && s.contact_forces && s.torques && s.actions && s.base_lin_vel && s.last_base_ang_vel &&
+                s.projected_gravity && s.base_pos && s.base_quat && s.contact_filt, "null output tensor");
+    // strided dof tensors: positive strides, rows that do not overlap
+    DTC_REQUIRE(s.dof_pos_elem_stride >= 1 && s.dof_pos_row_stride >= (c.num_dof - 1) * s.dof_pos_elem_stride + 1 &&
+                s.dof_vel_elem_stride >= 1 && s.dof_vel_row_stride >= (c.num_dof - 1) * s.dof_vel_elem_stride + 1, "dof_pos / dof_vel strides");
+
+    SimK k{};
+    k.B = c.num_bodies, k.C = c.num_commands, k.dec = c.decimation, k.heading = c.heading_command != 0, k.T = c.buffer_len;
+    for (int l = 0; l < 4; ++l) k.feet[l] = c.feet[l], k.thighs[l] = c.thighs[l];
+    k.resample = c.resampling_steps;
+    k.dt = c.sim_dt, k.half_dt = 0.5f * c.sim_dt, k.action_scale = c.action_scale, k.clip = c.clip_actions, k.inertia = c.joint_inertia;
+    k.eps = c.contact_eps, k.weight = c.weight, k.rmin2 = c.r_min * c.r_min;
+    k.rows = c.rows, k.cols = c.cols, k.border = c.border_size, k.hscale = c.horizontal_scale, k.vscale = c.vertical_scale;
+    k.cmd_x = span_of(c.lin_vel_x), k.cmd_y = span_of(c.lin_vel_y), k.cmd_third = span_of(c.heading_command ? c.heading : c.ang_vel_yaw);
+    k.seed_lo = (unsigned)c.seed, k.seed_hi = (unsigned)(c.seed >> 32), k.ctr_lo = (unsigned)c.counter, k.ctr_hi = (unsigned)(c.counter >> 32);
+
+    hipStream_t hs = (hipStream_t)stream;
+    dtc::ProfScope prof("sim_step", (double)N * (2048.0 + 12.0 * c.num_bodies + 8.0 * c.buffer_len * (3 + c.num_commands)), hs);
+    hipLaunchKernelGGL(sim_step_kernel, dim3((unsigned)dtc::ceil_div(N, 4)), dim3(256), 0, hs, s, k, N);
+    return dtc::check_launch("sim_step");
+}

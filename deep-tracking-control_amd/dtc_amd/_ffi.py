@@ -174,6 +174,29 @@ class DtcResetStep(C.Structure):
                 [(k, C.c_void_p) for k in ("env_ids", "count", "episode_means", "terrain_level_mean", "workspace")])
 
 
+class DtcSimCfg(C.Structure):
+    """include/dtc_hip.h: the constants and per-call scalars of dtc_sim_step; field order as there."""
+    _fields_ = ([(k, C.c_int32) for k in ("num_dof", "num_bodies", "num_commands", "decimation", "heading_command", "buffer_len")] +
+                [("feet", C.c_int32 * 4), ("thighs", C.c_int32 * 4), ("resampling_steps", C.c_int64)] +
+                [(k, C.c_float) for k in ("sim_dt", "action_scale", "clip_actions", "joint_inertia", "contact_eps", "weight", "r_min")] +
+                [("rows", C.c_int32), ("cols", C.c_int32)] +
+                [(k, C.c_float) for k in ("border_size", "horizontal_scale", "vertical_scale")] +
+                [(k, C.c_double * 2) for k in ("lin_vel_x", "lin_vel_y", "ang_vel_yaw", "heading")] +
+                [("seed", C.c_uint64), ("counter", C.c_uint64)])
+
+
+class DtcSimStep(C.Structure):
+    """include/dtc_hip.h: the buffers of one dtc_sim_step call (device pointers); field order as there."""
+    _fields_ = ([(k, C.c_void_p) for k in ("actions_in", "Kp_factors", "Kd_factors", "motor_strengths", "motor_offsets", "height_samples",
+                                           "u_cmd", "p_gains", "d_gains", "torque_limits", "default_dof_pos", "dof_pos_limits",
+                                           "hip_offset", "foot_nominal", "leg_jacobian", "dof_pos", "dof_vel")] +
+                [(k, C.c_int64) for k in ("dof_pos_row_stride", "dof_pos_elem_stride", "dof_vel_row_stride", "dof_vel_elem_stride")] +
+                [(k, C.c_void_p) for k in ("root_states", "base_ang_vel", "commands", "episode_length_buf", "last_contacts",
+                                           "lin_vel_buffer", "ang_vel_buffer", "cmd_buffer", "rigid_body_state", "contact_forces",
+                                           "torques", "actions", "base_lin_vel", "last_base_ang_vel", "projected_gravity", "base_pos",
+                                           "base_quat", "contact_filt")])
+
+
 class DtcRowCopy(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("src_stride_bytes", C.c_int64), ("width_bytes", C.c_int32)]
 
@@ -198,7 +221,7 @@ class DtcProfRec(C.Structure):
 ACT = {None: 0, "none": 0, "relu": 1, "crelu": 1, "elu": 2, "selu": 3, "lrelu": 4, "tanh": 5, "sigmoid": 6}
 MAX_OPERAND_ELEMS = (1 << 29) - 1
 
-ABI_VERSION = 21        # DTC_ABI_VERSION of include/dtc_hip.h this binding was written against
+ABI_VERSION = 22        # DTC_ABI_VERSION of include/dtc_hip.h this binding was written against
 
 _SIGS = {
     "dtc_version": (C.c_int, []),
@@ -223,6 +246,8 @@ _SIGS = {
     "dtc_env_reset_workspace": (C.c_int64, [C.c_int, C.c_int]),
     "dtc_env_reset_abi_sizes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
     "dtc_env_reset": (C.c_int, [C.POINTER(DtcResetStep), C.POINTER(DtcResetCfg), C.c_int, c_stream]),
+    "dtc_sim_abi_sizes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
+    "dtc_sim_step": (C.c_int, [C.POINTER(DtcSimStep), C.POINTER(DtcSimCfg), C.c_int, c_stream]),
     "dtc_check_termination": (C.c_int, [c_f32p, C.c_int, c_i32p, C.c_int, c_i64p, C.c_int64, c_f32p, c_f32p, c_f32p,
                                         C.POINTER(DtcObsCfg), c_u8p, c_u8p, c_f32p, C.c_int, c_stream]),
     "dtc_store_transition": (C.c_int, [C.POINTER(DtcRowCopy), C.c_int, c_f32p, c_f32p, c_u8p, C.c_float, c_f32p,
@@ -432,6 +457,9 @@ def _check_abi(l):
     theirs += list(sizes[:n])
     mine += [DtcActItem]                                                  # ... and by the rollout-step containment's
     n = l.dtc_act_contain_abi_sizes(sizes, 32)
+    theirs += list(sizes[:n])
+    mine += [DtcSimCfg, DtcSimStep]                                       # ... and by the surrogate env's
+    n = l.dtc_sim_abi_sizes(sizes, 32)
     theirs += list(sizes[:n])
     if l.dtc_version() != ABI_VERSION or theirs != [C.sizeof(t) for t in mine]:
         _lib = None

@@ -1,0 +1,253 @@
+"""SurrogateLeggedEnv: a closed-loop legged env that lives entirely in device memory, with no simulator behind it.
+
+`dtc_sim_step` (csrc/sim.hip) stands where LeggedRobotDTC calls Isaac Gym and fills the tensors the env-side kernels read; the rest
+of `step()` is the reference's post_physics_step on those kernels: `EnvStep` (heights, planner, termination, foothold rewards,
+observations), `EnvRewards`, `EnvReset` on `reset_buf`, `compute_observations(where=reset_buf)`, the step tail
+(legged_robot_dtc.py:215-223) and the observation clip (legged_robot.py:118-121).  Nothing in `step()` reads the device or calls
+`nonzero()`.  The env owns every tensor under the attribute name the reference env uses.
+
+It is a surrogate, not physics (include/dtc_hip.h lists what is absent): it gives the kernels a state that is consistent, evolves,
+responds to actions, terminates and resets, and a reward that depends on what the policy does.
+"""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass, field
+
+import numpy as np
+import torch
+
+from .. import foothold, reset, rewards, sim
+from .vec_env import VecEnv
+
+# raw reward scales (multiplied by dt, as the reference does): a Lite3-style set in which every term reads surrogate state
+_SCALES = dict(action_rate=-0.01, ang_vel_xy=-0.005, dof_acc=-2.5e-8, dof_pos_limits=-10.0, feet_air_time=1.0, lin_vel_z=-0.2,
+               smooth=-0.0015, torques=-1e-6, tracking_ang_vel=0.5, tracking_lin_vel=1.0, tracking_optimal_footholds=0.2)
+
+
+@dataclass
+class SurrogateConfig:
+    """Defaults: the Lite3 DTC values (53 / 1389 / 12, the 33 x 21 grid, decimation 4, dt 0.005, Kp 25, Kd 0.5, action scale 0.25)."""
+    sim: sim.SimConfig = field(default_factory=sim.SimConfig)
+    obs: foothold.ObsConfig = field(default_factory=foothold.ObsConfig)
+    grid: foothold.GridConfig = field(default_factory=foothold.GridConfig)
+    reward_scales: dict = field(default_factory=lambda: dict(_SCALES))
+    episode_length_s: float = 20.0
+    num_observation_history: int = 5
+    clip_observations: float = 100.0
+    randomize_motor_strength: bool = True
+    add_noise: bool = True                   # observation noise (legged_robot_dtc.py:284-288) when the draws are not given
+    noise_scales: dict = field(default_factory=lambda: dict(ang_vel=0.2, gravity=0.05, dof_pos=0.01, dof_vel=1.5))
+    contain_nonfinite: bool = True           # an env whose dofs or root state are not finite after the surrogate step is reset at once
+    env_spacing: float = 1.0                 # env origins: rows of 32 envs, this far apart, inside the terrain table
+
+    @property
+    def max_episode_length(self) -> int:
+        return int(math.ceil(self.episode_length_s / self.sim.dt))                      # legged_robot.py:_parse_cfg
+
+    def reward_config(self) -> rewards.RewardConfig:
+        dt = self.sim.dt
+        scales = {k: float(np.float32(v * dt)) for k, v in sorted(self.reward_scales.items()) if v != 0}
+        return rewards.RewardConfig(scales=scales, dt=dt, base_height_target=self.obs.base_height_target,
+                                    lin_vel_x_max=self.sim.lin_vel_x[1], ang_vel_yaw_max=self.sim.ang_vel_yaw[1],
+                                    points_x=tuple(self.grid.points_x), points_y=tuple(self.grid.points_y))
+
+    def reset_config(self) -> reset.ResetConfig:
+        s = self.sim
+        init = (0.0, 0.0, s.nominal_height, 0.0, 0.0, 0.0, 1.0) + (0.0,) * 6
+        return reset.ResetConfig(terrain_curriculum=False, custom_origins=False, heading_command=s.heading_command,
+                                 randomize_motor_strength=self.randomize_motor_strength, max_episode_length_s=self.episode_length_s,
+                                 lin_vel_x=s.lin_vel_x, lin_vel_y=s.lin_vel_y, ang_vel_yaw=s.ang_vel_yaw, heading=s.heading,
+                                 base_init_state=init)
+
+
+class _Cfg:
+    """The two config attributes HistoryWrapper and the runner read from an env."""
+
+    def __init__(self, c: SurrogateConfig):
+        self.env = type("env", (), dict(num_observation_history=c.num_observation_history, episode_length_s=c.episode_length_s))
+        self.surrogate = c
+
+
+class SurrogateLeggedEnv(VecEnv):
+    """`num_envs` kinematic quadrupeds over the int16 terrain table `height_samples` (default: flat; `synthetic.reward_table()` is
+    the rough one).  `step(actions, draws=None)`: `draws` is the parity mode -- a dict with any of u_cmd [N,3], u_reset [N,26],
+    u_obs [N,53], u_heights [N,693] (uniform [0,1)) and height_noise (float); what it leaves out is drawn on the device from `seed`
+    (command and reset draws by the kernels' Philox streams, the two observation noises by a seeded device generator); the reset's
+    height_noise is the reference's host draw, np.random.normal(0, 0.02), from a seeded RandomState."""
+
+    def __init__(self, num_envs: int, device="cuda", config: SurrogateConfig | None = None, height_samples: torch.Tensor | None = None,
+                 seed: int = 0):
+        c = self.config = config or SurrogateConfig()
+        dev = torch.device(device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        s = c.sim
+        N, D, B, C, P, T = int(num_envs), 12, int(s.num_bodies), int(s.num_commands), c.grid.num_points, int(s.buffer_len)
+        self.cfg, self.device, self.num_envs, self.num_dof, self.num_bodies, self.num_actions = _Cfg(c), dev, N, D, B, D
+        self.num_obs, self.num_privileged_obs = 9 + 3 * D + c.obs.num_foothold_obs, 2 * P + 3
+        self.num_obs_history = c.num_observation_history * self.num_obs
+        self.max_episode_length, self.dt = c.max_episode_length, s.dt
+        self.height_samples = (sim.flat_table() if height_samples is None else height_samples).to(dev).contiguous()
+        self.sim = sim.SimStep(N, dev, s, self.height_samples, seed=seed)
+        f = dict(dtype=torch.float32, device=dev)
+        z = lambda *shape: torch.zeros(*shape, **f)                                      # noqa: E731
+        t = self.sim.tables
+        self.default_dof_pos, self.dof_pos_limits, self.torque_limits = t["default_dof_pos"].view(1, D), t["dof_pos_limits"], t["torque_limits"]
+        self.p_gains, self.d_gains, self.dof_vel_limits = t["p_gains"], t["d_gains"], torch.full((D,), 30.0, **f)
+        self.feet_indices = torch.tensor(s.feet, dtype=torch.int64, device=dev)
+        self.thigh_indices = torch.tensor(s.thighs, dtype=torch.int64, device=dev)
+        self.termination_contact_indices = torch.tensor([0], dtype=torch.int64, device=dev)
+        self.penalised_contact_indices = torch.tensor([b for l in range(4) for b in (s.thighs[l], s.thighs[l] + 1)], dtype=torch.int64, device=dev)
+        self.hip_indices = torch.tensor([0, 3, 6, 9], dtype=torch.int64, device=dev)
+        self.command_ranges = {k: list(getattr(s, k)) for k in ("lin_vel_x", "lin_vel_y", "ang_vel_yaw", "heading")}
+        # state
+        self.dof_state = z(N, D, 2)
+        self.dof_pos, self.dof_vel = self.dof_state[..., 0], self.dof_state[..., 1]
+        self.root_states, self.rigid_body_state, self.contact_forces = z(N, 13), z(N, B, 13), z(N, B, 3)
+        self.torques, self.actions, self.last_actions, self.last_actions_2, self.last_dof_vel = z(N, D), z(N, D), z(N, D), z(N, D), z(N, D)
+        self.last_root_vel, self.last_foot_velocities = z(N, 6), z(N, 4, 3)
+        self.base_lin_vel, self.base_ang_vel, self.last_base_ang_vel, self.projected_gravity = z(N, 3), z(N, 3), z(N, 3), z(N, 3)
+        self.base_ang_vel_last, self.base_lin_vel_last, self.base_pos, self.base_quat = z(N, 3), z(N, 3), z(N, 3), z(N, 4)
+        self.commands, self.forces, self.height_noise_offset = z(N, C), z(N, B, 3), z(N, P)
+        self.lin_vel_buffer, self.ang_vel_buffer, self.cmd_buffer = z(T, N, 2), z(T, N, 1), z(T, N, C)
+        self.Kp_factors, self.Kd_factors, self.motor_strengths, self.motor_offsets = 1 + z(N, D), 1 + z(N, D), 1 + z(N, D), z(N, D)
+        self.episode_length_buf = torch.zeros(N, dtype=torch.int64, device=dev)
+        self.last_contacts = torch.zeros(N, 4, dtype=torch.bool, device=dev)
+        self.contact_filt = torch.zeros(N, 4, dtype=torch.bool, device=dev)
+        self.robot_mass = torch.full((N,), float(s.mass), **f)
+        self.terrain_levels = torch.zeros(N, dtype=torch.int64, device=dev)
+        i = torch.arange(N, device=dev)
+        self.env_origins = torch.stack([(i % 32) * c.env_spacing, (i // 32 % 24) * c.env_spacing, torch.zeros_like(i)], dim=1).float().contiguous()
+        self.noise_scale_vec = z(self.num_obs)                                           # _get_noise_scale_vec, noise level 1
+        ns, ob = c.noise_scales, c.obs
+        self.noise_scale_vec[0:3], self.noise_scale_vec[3:6] = ns["ang_vel"] * ob.ang_vel, ns["gravity"]
+        self.noise_scale_vec[9:9 + D], self.noise_scale_vec[9 + D:9 + 2 * D] = ns["dof_pos"] * ob.dof_pos, ns["dof_vel"] * ob.dof_vel
+        self.rew_buf = z(N)
+        self.extras = {}
+        self.nonfinite_act_envs = None            # OnPolicyRunner.learn hands the policy-step containment's mask over here
+        # the env-side kernels
+        self.env_step = foothold.EnvStep(N, dev, c.grid, c.obs)
+        self.env_rewards = rewards.EnvRewards(N, dev, c.reward_config(), feet_indices=self.feet_indices,
+                                              penalised_contact_indices=self.penalised_contact_indices, hip_indices=self.hip_indices, num_dof=D)
+        self.feet_air_time, self.pitch_est = self.env_rewards.feet_air_time, self.env_rewards.pitch_est
+        names = self.env_rewards.cfg.names
+        self.episode_sums = {n: self.env_rewards.episode_sums[k] for k, n in enumerate(names)}
+        self.env_reset = reset.EnvReset(N, dev, c.reset_config(), n_sums=len(names), num_dof=D, seed=seed)
+        self._episode = {"rew_" + n: self.env_reset.episode_means[k] for k, n in enumerate(names)}
+        self._height_noise = np.random.RandomState(seed)
+        self._gen = torch.Generator(device=dev).manual_seed(seed) if dev.type == "cuda" else None
+        self._out = self.env_step.out
+        self.reset_buf, self.time_out_buf = self._out["reset_buf"], self._out["time_out_buf"]
+        self.obs_buf, self.privileged_obs_buf = self._out["obs_buf"], self._out["privileged_obs_buf"]
+
+    # ------------------------------------------------------------------ one env step
+    def _observation_inputs(self, draws):
+        if not draws:                            # production mode: seeded device draws, as the reference's two torch.rand_like
+            draws = dict(u_heights=torch.rand(self.num_envs, self.config.grid.num_points, generator=self._gen, device=self.device))
+            if self.config.add_noise:
+                draws["u_obs"] = torch.rand(self.num_envs, self.num_obs, generator=self._gen, device=self.device)
+        return dict(base_ang_vel=self.base_ang_vel, projected_gravity=self.projected_gravity, commands=self.commands, dof_pos=self.dof_pos,
+                    default_dof_pos=self.default_dof_pos, dof_vel=self.dof_vel, actions=self.actions, forces=self.forces,
+                    root_states=self.root_states, height_noise_offset=self.height_noise_offset, u_obs=draws.get("u_obs"),
+                    noise_scale_vec=self.noise_scale_vec if draws.get("u_obs") is not None else None, u_heights=draws.get("u_heights"))
+
+    def _reset_envs(self, draws):
+        """reset_idx for the envs named in reset_buf (legged_robot.py:200-272), one dtc_env_reset call."""
+        hn = draws.get("height_noise")
+        self.env_reset(reset_buf=self.reset_buf, root_states=self.root_states, env_origins=self.env_origins, commands=self.commands,
+                       dof_pos=self.dof_pos, dof_vel=self.dof_vel, default_dof_pos=self.default_dof_pos.reshape(-1), forces=self.forces,
+                       motor_strengths=self.motor_strengths, Kp_factors=self.Kp_factors, Kd_factors=self.Kd_factors,
+                       height_noise_offset=self.height_noise_offset, episode_sums=self.env_rewards.episode_sums, stumble=self.env_rewards.stumble,
+                       last_actions=self.last_actions, last_actions_2=self.last_actions_2, last_dof_vel=self.last_dof_vel,
+                       feet_air_time=self.feet_air_time, pitch_est=self.pitch_est, base_ang_vel_last=self.base_ang_vel_last,
+                       base_lin_vel_last=self.base_lin_vel_last, episode_length_buf=self.episode_length_buf, contact_filt=self.contact_filt,
+                       last_contacts=self.last_contacts, lin_vel_buffer=self.lin_vel_buffer, ang_vel_buffer=self.ang_vel_buffer,
+                       cmd_buffer=self.cmd_buffer, u=draws.get("u_reset"), command_ranges=self.command_ranges,
+                       height_noise=float(self._height_noise.normal(0, 0.02)) if hn is None else float(hn))
+
+    def step(self, actions: torch.Tensor, draws: dict | None = None):
+        draws = draws or {}
+        c, s = self.config, self.config.sim
+        # 1. the surrogate's physics and the bookkeeping up to the planner
+        self.sim.step(self, actions.to(self.device, torch.float32).contiguous(), draws.get("u_cmd"))
+        if s.heading_command:                                                            # legged_robot.py:537-539, yaw-only base
+            heading = torch.atan2(2.0 * self.base_quat[:, 2] * self.base_quat[:, 3], 1.0 - 2.0 * self.base_quat[:, 2] * self.base_quat[:, 2])
+            d = self.commands[:, 3] - heading
+            d = torch.remainder(d + math.pi, 2 * math.pi) - math.pi                      # wrap_to_pi
+            self.commands[:, 2] = torch.clip(0.5 * d, -1.5, 1.5)
+        bad = None
+        if c.contain_nonfinite:
+            # a non-finite env (its own divergence, or NaN written into its state) would carry NaN into the rewards, the episode
+            # sums and every later step: its rows are zeroed here, ahead of every consumer, and it is reset in this step
+            bad = ~(torch.isfinite(self.dof_state).flatten(1).all(dim=1) & torch.isfinite(self.root_states).all(dim=1))
+            for t in (self.dof_state, self.root_states, self.rigid_body_state, self.contact_forces, self.torques, self.base_lin_vel,
+                      self.base_ang_vel, self.last_base_ang_vel, self.base_pos, self.base_quat):
+                t.masked_fill_(bad.view(-1, *([1] * (t.dim() - 1))), 0.0)
+            for t in (self.lin_vel_buffer, self.ang_vel_buffer, self.cmd_buffer):
+                t.masked_fill_(bad.view(1, -1, 1), 0.0)
+        self.foot_positions = self.rigid_body_state[:, self.feet_indices, 0:3]
+        self.foot_velocities = self.rigid_body_state[:, self.feet_indices, 7:10]
+        self.hip_positions = self.rigid_body_state[:, self.thigh_indices, 0:3]
+        # 2. heights, planner, termination, foothold rewards, observations
+        obs_in = self._observation_inputs(draws)
+        o = self.env_step(thigh_pos=self.hip_positions, contact_forces=self.contact_forces,
+                          termination_contact_indices=self.termination_contact_indices, episode_length_buf=self.episode_length_buf,
+                          max_episode_length=self.max_episode_length, foot_positions=self.foot_positions, contact_filt=self.contact_filt,
+                          height_samples=self.height_samples, border_size=s.border_size, horizontal_scale=s.horizontal_scale,
+                          vertical_scale=s.vertical_scale, **obs_in)
+        self.measured_heights, self.foothold_obs, self.optimal_footholds_world = o["measured_heights"], o["foothold_obs"], o["optimal_footholds_world"]
+        if bad is not None:
+            self.reset_buf |= bad.to(torch.uint8)
+        if self.nonfinite_act_envs is not None:
+            self.reset_buf |= self.nonfinite_act_envs                                    # envs whose policy step was repaired
+        # 3. the reward terms
+        self.env_rewards(last_contacts=self.last_contacts, out=self.rew_buf, height_samples=self.height_samples, border_size=s.border_size,
+                         horizontal_scale=s.horizontal_scale, vertical_scale=s.vertical_scale, root_states=self.root_states,
+                         base_lin_vel=self.base_lin_vel, base_ang_vel=self.base_ang_vel, projected_gravity=self.projected_gravity,
+                         commands=self.commands, dof_pos=self.dof_pos, default_dof_pos=self.default_dof_pos.reshape(-1), dof_vel=self.dof_vel,
+                         last_dof_vel=self.last_dof_vel, torques=self.torques, actions=self.actions, last_actions=self.last_actions,
+                         last_actions_2=self.last_actions_2, contact_forces=self.contact_forces, foot_positions=self.foot_positions,
+                         foot_velocities=self.foot_velocities, last_foot_velocities=self.last_foot_velocities,
+                         optimal_footholds_world=self.optimal_footholds_world, contact_filt=self.contact_filt,
+                         measured_heights=self.measured_heights, reset_buf=self.reset_buf, time_out_buf=self.time_out_buf,
+                         robot_mass=self.robot_mass, terrain_levels=self.terrain_levels, dof_pos_limits=self.dof_pos_limits,
+                         dof_vel_limits=self.dof_vel_limits, torque_limits=self.torque_limits, cmd_buffer=self.cmd_buffer,
+                         lin_vel_buffer=self.lin_vel_buffer, ang_vel_buffer=self.ang_vel_buffer)
+        # 4. reset, 5. the observation rows of the reset envs: their new dofs, root state and commands, the stale derived quantities
+        self._reset_envs(draws)
+        foothold.compute_observations(foothold_obs=self.foothold_obs, measured_heights=self.measured_heights, cfg=c.obs, where=self.reset_buf,
+                                      out=self._out, **obs_in)
+        # 6. the step tail (legged_robot_dtc.py:215-223)
+        self.last_actions_2.copy_(self.last_actions)
+        self.last_actions.copy_(self.actions)
+        self.last_dof_vel.copy_(self.dof_vel)
+        self.last_root_vel.copy_(self.root_states[:, 7:13])
+        self.last_foot_velocities.copy_(self.foot_velocities)
+        self.base_ang_vel_last.copy_(self.base_ang_vel)
+        self.base_lin_vel_last.copy_(self.base_lin_vel)
+        # 7. the observation clip (legged_robot.py:118-121)
+        self.obs_buf = torch.clip(self._out["obs_buf"], -c.clip_observations, c.clip_observations)
+        self.privileged_obs_buf = torch.clip(self._out["privileged_obs_buf"], -c.clip_observations, c.clip_observations)
+        self.extras = {"time_outs": self.time_out_buf.bool(), "episode": dict(self._episode)}
+        return self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf.bool(), self.extras
+
+    # ------------------------------------------------------------------ the rest of the env contract
+    def reset(self, env_ids=None, draws: dict | None = None):
+        """Reset every env, then one step with zero actions (base_task.py:115-119)."""
+        self.reset_buf.fill_(1)
+        self._reset_envs(draws or {})
+        obs, _, _, _, _ = self.step(torch.zeros(self.num_envs, self.num_actions, device=self.device), draws)
+        return obs
+
+    def get_observations(self):
+        return self.obs_buf
+
+    def get_privileged_observations(self):
+        return self.privileged_obs_buf
+
+    def get_base_vel(self):
+        return self.base_lin_vel * self.config.obs.lin_vel                               # legged_robot.py:1429-1431
+
+    def get_reward_buf(self):
+        return self.rew_buf

@@ -1,0 +1,184 @@
+"""Host side of the surrogate legged env step (csrc/sim.hip, `dtc_sim_step`): the state the env kernels run on when no simulator
+stands behind them.  One launch per env step stands where the reference calls Isaac Gym: `decimation` substeps of the PD law of
+LeggedRobot._compute_torques (control type "P"), a kinematic quadruped that rides on its stance feet over the int16 terrain table,
+and the bookkeeping of post_physics_step up to the planner.  include/dtc_hip.h states every operation; it is a surrogate, not
+physics (no roll / pitch, no base dynamics, no lag buffers, no pushes, no "V" / "T" control, no heading yaw law).
+
+`SimConfig` holds the constants (Lite3 DTC values), `leg_tables(config)` the three small tables computed once in float64 from a
+two-link leg linearised at the default pose, and `SimStep` runs the launch on an env's own tensors (attribute names as in
+LeggedRobotDTC).
+"""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _ffi
+
+_RANGES = ("lin_vel_x", "lin_vel_y", "ang_vel_yaw", "heading")
+# per-env tensors of the env that dtc_sim_step reads or writes: name -> (trailing shape given D, B, C; dtype)
+_ENV_TENSORS = dict(Kp_factors=("D", torch.float32), Kd_factors=("D", torch.float32), motor_strengths=("D", torch.float32),
+                    motor_offsets=("D", torch.float32), root_states=(13, torch.float32), base_ang_vel=(3, torch.float32),
+                    commands=("C", torch.float32), episode_length_buf=((), torch.int64), last_contacts=(4, torch.bool),
+                    rigid_body_state=("B", 13, torch.float32), contact_forces=("B", 3, torch.float32), torques=("D", torch.float32),
+                    actions=("D", torch.float32), base_lin_vel=(3, torch.float32), last_base_ang_vel=(3, torch.float32),
+                    projected_gravity=(3, torch.float32), base_pos=(3, torch.float32), base_quat=(4, torch.float32),
+                    contact_filt=(4, torch.bool))
+_RING_BUFFERS = dict(lin_vel_buffer=2, ang_vel_buffer=1, cmd_buffer="C")
+
+
+@dataclass
+class SimConfig:
+    """Constants of the surrogate step (names as in DtcSimCfg, include/dtc_hip.h); defaults: the Lite3 DTC values."""
+    sim_dt: float = 0.005
+    decimation: int = 4
+    action_scale: float = 0.25
+    clip_actions: float = 100.0
+    stiffness: float = 25.0
+    damping: float = 0.5
+    torque_limit: float = 24.0
+    joint_inertia: float = 0.05              # kg m^2 seen by every joint: the PD loop is well damped at sim_dt (kp / I = 500 s^-2)
+    joint_range: float = 1.0                 # position limits: default +- joint_range (a full crouch sinks the base below 0.15 m)
+    contact_eps: float = 0.005               # a foot within 5 mm of the ground under the support plane is in contact
+    mass: float = 12.0
+    gravity: float = 9.81
+    r_min: float = 0.05                      # a stance whose feet lie within r_min of their centroid gives no yaw rate
+    default_dof_pos: tuple = (0.0, -0.8, 1.6) * 4
+    hip_offset: tuple = ((0.17, 0.1, 0.0), (0.17, -0.1, 0.0), (-0.17, 0.1, 0.0), (-0.17, -0.1, 0.0))       # FL, FR, HL, HR
+    link_lengths: tuple = (0.2, 0.2)
+    num_bodies: int = 17                     # base, then (hip, thigh, shank, foot) per leg
+    feet: tuple = (4, 8, 12, 16)
+    thighs: tuple = (2, 6, 10, 14)
+    num_commands: int = 4
+    heading_command: bool = False
+    resampling_time: float = 10.0
+    buffer_len: int = 10
+    lin_vel_x: tuple = (-0.75, 0.75)
+    lin_vel_y: tuple = (-0.75, 0.75)
+    ang_vel_yaw: tuple = (-0.5, 0.5)
+    heading: tuple = (-3.14, 3.14)
+    border_size: float = 20.0
+    horizontal_scale: float = 0.05
+    vertical_scale: float = 0.005
+
+    @property
+    def dt(self) -> float:
+        return self.sim_dt * self.decimation
+
+    @property
+    def resampling_steps(self) -> int:
+        return int(self.resampling_time / self.dt)                      # legged_robot.py:534
+
+    @property
+    def nominal_height(self) -> float:
+        """Base height over flat ground at the default pose."""
+        return -float(leg_tables(self)["foot_nominal"][0, 2])
+
+
+def leg_tables(config: SimConfig) -> dict:
+    """hip_offset [4,3], foot_nominal [4,3], leg_jacobian [4,3,3] (float64): a leg is an abduction joint about x followed by two
+    pitch joints with links l1, l2; foot = hip + (xs, -zs sin(a), zs cos(a)) with xs = -l1 sin(t1) - l2 sin(t1 + t2),
+    zs = -l1 cos(t1) - l2 cos(t1 + t2); the Jacobian is taken at the default pose."""
+    l1, l2 = config.link_lengths
+    hip = np.asarray(config.hip_offset, dtype=np.float64)
+    q0 = np.asarray(config.default_dof_pos, dtype=np.float64).reshape(4, 3)
+    nominal, jac = np.zeros((4, 3)), np.zeros((4, 3, 3))
+    for l in range(4):
+        a, t1, t2 = q0[l]
+        xs = -l1 * math.sin(t1) - l2 * math.sin(t1 + t2)
+        zs = -l1 * math.cos(t1) - l2 * math.cos(t1 + t2)
+        dxs = (-l1 * math.cos(t1) - l2 * math.cos(t1 + t2), -l2 * math.cos(t1 + t2))
+        dzs = (l1 * math.sin(t1) + l2 * math.sin(t1 + t2), l2 * math.sin(t1 + t2))
+        nominal[l] = hip[l] + (xs, -zs * math.sin(a), zs * math.cos(a))
+        jac[l, :, 0] = (0.0, -zs * math.cos(a), -zs * math.sin(a))
+        for k in range(2):
+            jac[l, :, 1 + k] = (dxs[k], -dzs[k] * math.sin(a), dzs[k] * math.cos(a))
+    return dict(hip_offset=hip, foot_nominal=nominal, leg_jacobian=jac)
+
+
+def joint_tables(config: SimConfig) -> dict:
+    """p_gains, d_gains, torque_limits, default_dof_pos [12] and dof_pos_limits [12,2] (float64)."""
+    d = np.asarray(config.default_dof_pos, dtype=np.float64)
+    return dict(p_gains=np.full(12, config.stiffness), d_gains=np.full(12, config.damping), torque_limits=np.full(12, config.torque_limit),
+                default_dof_pos=d, dof_pos_limits=np.stack([d - config.joint_range, d + config.joint_range], axis=1))
+
+
+def flat_table(rows: int = 1400, cols: int = 900, device="cpu") -> torch.Tensor:
+    """The flat int16 terrain table."""
+    return torch.zeros(rows, cols, dtype=torch.int16, device=device)
+
+
+class SimStep:
+    """`dtc_sim_step` for `num_envs` envs over the terrain table `height_samples` [rows, cols] int16.  Owns the small device tables
+    (`tables`: float32 copies of `leg_tables` / `joint_tables`).  `step(env, actions, u_cmd=None)` runs one env step in place on the
+    tensors of `env`; with `u_cmd` left out the kernel draws the command resamples itself (Philox, keyed by `seed` and a call
+    counter)."""
+
+    def __init__(self, num_envs: int, device, config: SimConfig, height_samples: torch.Tensor, *, seed: int = 0, tables: dict | None = None):
+        dev = torch.device(device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if num_envs < 1 or len(config.default_dof_pos) != 12:
+            raise ValueError("SimStep: >= 1 env and four legs of three joints are supported")
+        if height_samples.dtype != torch.int16 or height_samples.dim() != 2 or min(height_samples.shape) < 2:
+            raise ValueError("SimStep: height_samples must be an int16 table of at least 2 x 2")
+        self.N, self.device, self.cfg, self.seed, self.counter = int(num_envs), dev, config, int(seed), 0
+        self.height_samples = height_samples.to(dev).contiguous()
+        t = dict(leg_tables(config), **joint_tables(config)) if tables is None else tables
+        self.tables = {k: torch.as_tensor(np.asarray(v), dtype=torch.float32).to(dev).contiguous() for k, v in t.items()}
+
+    def cfg_struct(self) -> "_ffi.DtcSimCfg":
+        k, c = self.cfg, _ffi.DtcSimCfg()
+        c.num_dof, c.num_bodies, c.num_commands, c.decimation = 12, int(k.num_bodies), int(k.num_commands), int(k.decimation)
+        c.heading_command, c.buffer_len, c.resampling_steps = int(k.heading_command), int(k.buffer_len), int(k.resampling_steps)
+        for l in range(4):
+            c.feet[l], c.thighs[l] = int(k.feet[l]), int(k.thighs[l])
+        c.sim_dt, c.action_scale, c.clip_actions, c.joint_inertia = k.sim_dt, k.action_scale, k.clip_actions, k.joint_inertia
+        c.contact_eps, c.weight, c.r_min = k.contact_eps, float(np.float32(k.mass * k.gravity)), k.r_min
+        c.rows, c.cols = int(self.height_samples.shape[0]), int(self.height_samples.shape[1])
+        c.border_size, c.horizontal_scale, c.vertical_scale = k.border_size, k.horizontal_scale, k.vertical_scale
+        for name in _RANGES:
+            lo, hi = getattr(k, name)
+            getattr(c, name)[0], getattr(c, name)[1] = float(lo), float(hi)
+        c.seed, c.counter = self.seed, self.counter
+        return c
+
+    def _check(self, name, t, tail, dtype):
+        if not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != dtype or tuple(t.shape) != tail or not t.is_contiguous():
+            raise _ffi.DtcError(f"SimStep: {name} must be a contiguous {dtype} tensor of shape {tail} on {self.device}")
+
+    def step(self, env, actions: torch.Tensor, u_cmd: torch.Tensor | None = None):
+        k, N = self.cfg, self.N
+        dims = dict(D=12, B=int(k.num_bodies), C=int(k.num_commands))
+        s = _ffi.DtcSimStep()
+        self._check("actions", actions, (N, 12), torch.float32)
+        s.actions_in = _ffi.ptr(actions)
+        for name, (*tail, dtype) in _ENV_TENSORS.items():
+            tail = tuple(v for t in tail for v in (t if isinstance(t, tuple) else (t,)))
+            t = getattr(env, name)
+            self._check(name, t, (N,) + tuple(dims.get(v, v) for v in tail), dtype)
+            setattr(s, name, _ffi.ptr(t))
+        for name, width in _RING_BUFFERS.items():
+            t = getattr(env, name)
+            self._check(name, t, (int(k.buffer_len), N, dims.get(width, width)), torch.float32)
+            setattr(s, name, _ffi.ptr(t))
+        for name in ("dof_pos", "dof_vel"):                              # the two interleaved views of dof_state [N,D,2], or dense
+            t = getattr(env, name)
+            if not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != torch.float32 or tuple(t.shape) != (N, 12):
+                raise _ffi.DtcError(f"SimStep: {name} must be a float32 tensor of shape {(N, 12)} on {self.device}")
+            setattr(s, name, _ffi.ptr(t))
+            setattr(s, name + "_row_stride", t.stride(0))
+            setattr(s, name + "_elem_stride", t.stride(1))
+        if u_cmd is not None:
+            self._check("u_cmd", u_cmd, (N, 3), torch.float32)
+            s.u_cmd = _ffi.ptr(u_cmd)
+        s.height_samples = _ffi.ptr(self.height_samples)
+        for name, t in self.tables.items():
+            setattr(s, name, _ffi.ptr(t))
+        c = self.cfg_struct()
+        _ffi.check(_ffi.lib().dtc_sim_step(s, c, N, _ffi.stream()), "dtc_sim_step")
+        if u_cmd is None:
+            self.counter += 1

@@ -1,0 +1,254 @@
+"""First closed-loop measurements: `OnPolicyRunner.learn` on `SurrogateLeggedEnv`, PPO with default arithmetic and with
+`gemm_passes=1`, fixed seeds.  Nothing here has a target.
+
+    python deep-tracking-control_amd/tools/closed_loop.py [--envs 4096] [--iters 10] [--out profiles/closed_loop.txt]
+    python deep-tracking-control_amd/tools/closed_loop.py --signal        # + the learning-signal run: 256 envs, 30 iterations
+
+Per run and iteration: the mean step reward (mean of rew_buf over the iteration's 24 steps and all envs), the mean episode length
+(the runner's tracker: the last <= 100 finished episodes; "-" before the first one ends) and the mean length of the episodes in flight.
+Timing, three interleaved rounds (default, one pass, default, ...), each figure with its spread (min .. max of the three):
+  * env-steps/s of the whole loop: host-clock window around learn(iters), closed by one device synchronise, nothing inside it;
+  * time per iteration of env.step(), alg.act() and alg.update(): a second learn(iters) in which each of the three calls is a
+    host-clock window that ends in a device synchronise (so the three do not overlap, and their sum exceeds the whole loop's time);
+  * dtc_sim_step beside the torch restatement of the same step (below: the same arithmetic as torch ops on the same tensors, checked
+    against the kernel to 1e-5 before it is timed), alternating, median of --calls windows each.
+"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+
+from dtc_amd.env import SurrogateConfig, SurrogateLeggedEnv  # noqa: E402
+from dtc_amd.runners import OnPolicyRunner  # noqa: E402
+from dtc_amd.runners.on_policy_runner import _EpisodeTracker  # noqa: E402
+
+DEV = "cuda"
+STEPS = 24
+RUNS = (("default", {}), ("gemm_passes=1", dict(gemm_passes=1)))
+
+
+def make(num_envs, algo, seed=11):
+    torch.manual_seed(seed)
+    env = SurrogateLeggedEnv(num_envs, DEV, SurrogateConfig(), seed=5)
+    runner = dict(policy_class_name="ActorCriticDecoder", algorithm_class_name="PPO", num_steps_per_env=STEPS, save_interval=10 ** 9)
+    return OnPolicyRunner(env, dict(runner=runner, algorithm=dict(algo), policy=dict()), log_dir=None, device=DEV), env
+
+
+class Watch:
+    """Wraps env.step of a runner: per-iteration reward and episode statistics on the device, no host read inside an iteration."""
+
+    def __init__(self, r, env):
+        self.env, self.tracker = env, _EpisodeTracker(env.num_envs, DEV)
+        self.sum, self.rows = torch.zeros((), dtype=torch.float64, device=DEV), []
+        inner = r.env.step
+
+        def step(actions):
+            out = inner(actions)
+            self.sum += out[1].double().mean()
+            self.tracker.step(out[1], out[2])
+            return out
+        object.__setattr__(r.env, "step", step)              # on the wrapper itself: its __setattr__ would hand it to the env
+
+    def close_iteration(self):
+        m = self.tracker.means()
+        self.rows.append((float(self.sum) / STEPS, None if m is None else m[1], float(self.env.episode_length_buf.float().mean())))
+        self.sum.zero_()
+
+
+def learning_curve(num_envs, iters, algo):
+    r, env = make(num_envs, algo)
+    w = Watch(r, env)
+    for _ in range(iters):
+        r.learn(1)
+        w.close_iteration()
+    return w.rows
+
+
+def timed(fn, acc):
+    def f(*a, **k):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn(*a, **k)
+        torch.cuda.synchronize()
+        acc.append(time.perf_counter() - t0)
+        return out
+    return f
+
+
+def timing_round(num_envs, iters, algo):
+    r, env = make(num_envs, algo)
+    r.learn(2)                                                # warm-up: allocations, first launches
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    r.learn(iters)
+    torch.cuda.synchronize()
+    whole = time.perf_counter() - t0
+    t_env, t_act, t_upd = [], [], []
+    object.__setattr__(r.env, "step", timed(r.env.step, t_env))
+    r.alg.act, r.alg.update = timed(r.alg.act, t_act), timed(r.alg.update, t_upd)
+    r.learn(iters)
+    return dict(steps_per_s=num_envs * STEPS * iters / whole, env_ms=1e3 * sum(t_env) / iters, act_ms=1e3 * sum(t_act) / iters,
+                update_ms=1e3 * sum(t_upd) / iters)
+
+
+def torch_sim_step(env, actions, u_cmd):
+    """dtc_sim_step as torch ops (include/dtc_hip.h states the arithmetic), in place on the env's tensors."""
+    c, t = env.config.sim, env.sim.tables
+    N, dt = env.num_envs, c.sim_dt
+    lo, hi, dflt = t["dof_pos_limits"][:, 0], t["dof_pos_limits"][:, 1], t["default_dof_pos"]
+    J, nom, hip = t["leg_jacobian"], t["foot_nominal"], t["hip_offset"]
+    a = torch.clip(actions, -c.clip_actions, c.clip_actions)
+    goal = torch.clip(a * c.action_scale + dflt, lo, hi)
+    q, qd = env.dof_pos.clone(), env.dof_vel.clone()
+    x, y, z, qz, qw = (env.root_states[:, i].clone() for i in (0, 1, 2, 5, 6))
+    kp, kd = t["p_gains"] * env.Kp_factors, t["d_gains"] * env.Kd_factors
+    hs = env.height_samples
+    for _ in range(c.decimation):
+        tau = torch.clip((kp * (goal - q + env.motor_offsets) - kd * qd) * env.motor_strengths, -t["torque_limits"], t["torque_limits"])
+        qd = qd + tau / c.joint_inertia * dt
+        q = q + qd * dt
+        out = (q < lo) | (q > hi)
+        q, qd = torch.clip(q, lo, hi), torch.where(out, torch.zeros_like(qd), qd)
+        p = nom + torch.einsum("lik,nlk->nli", J, (q - dflt).view(N, 4, 3))
+        u = torch.einsum("lik,nlk->nli", J, qd.view(N, 4, 3))
+        cs, sn = 1 - 2 * qz * qz, 2 * qz * qw
+        fx = x[:, None] + cs[:, None] * p[..., 0] - sn[:, None] * p[..., 1]
+        fy = y[:, None] + sn[:, None] * p[..., 0] + cs[:, None] * p[..., 1]
+        ix = ((fx + c.border_size) / c.horizontal_scale).long().clip(0, hs.shape[0] - 2)
+        iy = ((fy + c.border_size) / c.horizontal_scale).long().clip(0, hs.shape[1] - 2)
+        h = torch.min(torch.min(hs[ix, iy], hs[ix + 1, iy]), hs[ix, iy + 1]).float() * c.vertical_scale
+        bz = (h - p[..., 2]).max(dim=1).values
+        ct = (bz[:, None] + p[..., 2] - h) <= c.contact_eps
+        m = ct.float()
+        nc = m.sum(1)
+        pm = (p[..., :2] * m[..., None]).sum(1) / nc[:, None]
+        um = (u[..., :2] * m[..., None]).sum(1) / nc[:, None]
+        dp, du = p[..., :2] - pm[:, None], u[..., :2] - um[:, None]
+        num = ((dp[..., 0] * du[..., 1] - dp[..., 1] * du[..., 0]) * m).sum(1)
+        den = ((dp * dp).sum(-1) * m).sum(1)
+        w = torch.where(den > c.r_min ** 2, -num / den.clamp_min(1e-30), torch.zeros_like(den))
+        vbx, vby = -um[:, 0] + w * pm[:, 1], -um[:, 1] - w * pm[:, 0]
+        x, y = x + (cs * vbx - sn * vby) * dt, y + (sn * vbx + cs * vby) * dt
+        vz, z = (bz - z) / dt, bz
+        zn, wn = qz + 0.5 * dt * w * qw, qw - 0.5 * dt * w * qz
+        r = torch.sqrt(zn * zn + wn * wn)
+        qz, qw = zn / r, wn / r
+    cs, sn = 1 - 2 * qz * qz, 2 * qz * qw
+    Vx, Vy = cs * vbx - sn * vby, sn * vbx + cs * vby
+    zero = torch.zeros_like(x)
+    env.dof_pos.copy_(q), env.dof_vel.copy_(qd), env.torques.copy_(tau), env.actions.copy_(a)
+    env.root_states.copy_(torch.stack([x, y, z, zero, zero, qz, qw, Vx, Vy, vz, zero, zero, w], dim=1))
+    env.last_base_ang_vel.copy_(env.base_ang_vel)
+    env.base_lin_vel.copy_(torch.stack([vbx, vby, vz], dim=1)), env.base_ang_vel.copy_(torch.stack([zero, zero, w], dim=1))
+    env.projected_gravity.copy_(torch.stack([zero, zero, zero - 1], dim=1))
+    env.base_quat.copy_(torch.stack([zero, zero, qz, qw], dim=1)), env.base_pos.copy_(torch.stack([x, y, z], dim=1))
+    rot = lambda vx, vy: (cs[:, None] * vx - sn[:, None] * vy, sn[:, None] * vx + cs[:, None] * vy)         # noqa: E731
+    fx, fy = rot(p[..., 0], p[..., 1])
+    gx, gy = rot(u[..., 0] - w[:, None] * p[..., 1], u[..., 1] + w[:, None] * p[..., 0])
+    env.rigid_body_state[:, env.feet_indices, 0:3] = torch.stack([x[:, None] + fx, y[:, None] + fy, z[:, None] + p[..., 2]], dim=-1)
+    env.rigid_body_state[:, env.feet_indices, 7:10] = torch.stack([Vx[:, None] + gx, Vy[:, None] + gy, vz[:, None] + u[..., 2]], dim=-1)
+    tx, ty = rot(hip[None, :, 0], hip[None, :, 1])
+    env.rigid_body_state[:, env.thigh_indices, 0:3] = torch.stack([x[:, None] + tx, y[:, None] + ty, z[:, None] + hip[None, :, 2]], dim=-1)
+    env.contact_forces.zero_()
+    env.contact_forces[:, env.feet_indices, 2] = m * (c.mass * c.gravity / nc)[:, None]
+    env.episode_length_buf += 1
+    for buf, new in ((env.lin_vel_buffer, torch.stack([vbx, vby], dim=1)), (env.ang_vel_buffer, w[:, None]), (env.cmd_buffer, env.commands)):
+        buf[:-1] = buf[1:].clone()
+        buf[-1] = new
+    ids = (env.episode_length_buf % c.resampling_steps == 0).nonzero(as_tuple=False).flatten()             # as the reference: a host read
+    if len(ids):
+        span = lambda r, v: (r[1] - r[0]) * v + r[0]                                                         # noqa: E731
+        env.commands[ids, 0], env.commands[ids, 1] = span(c.lin_vel_x, u_cmd[ids, 0]), span(c.lin_vel_y, u_cmd[ids, 1])
+        env.commands[ids, 3 if c.heading_command else 2] = span(c.heading if c.heading_command else c.ang_vel_yaw, u_cmd[ids, 2])
+        env.commands[ids, :2] *= (torch.norm(env.commands[ids, :2], dim=1) > 0.1).unsqueeze(1)
+    contact = env.contact_forces[:, env.feet_indices, 2] > 1.
+    env.contact_filt.copy_(contact | env.last_contacts)
+    env.last_contacts.copy_(contact)
+
+
+CHECKED = ("dof_state", "root_states", "torques", "base_lin_vel", "base_ang_vel", "rigid_body_state", "contact_forces", "commands",
+           "lin_vel_buffer", "cmd_buffer", "contact_filt", "episode_length_buf")
+
+
+def sim_step_probe(num_envs, calls):
+    envs = [SurrogateLeggedEnv(num_envs, DEV, SurrogateConfig(), seed=5) for _ in range(2)]
+    g = torch.Generator(device=DEV).manual_seed(3)
+    for e in envs:
+        e.reset()
+    worst = 0.0
+    for _ in range(5):                                         # same steps both ways, compared
+        a, u = torch.randn(num_envs, 12, generator=g, device=DEV), torch.rand(num_envs, 3, generator=g, device=DEV)
+        envs[0].sim.step(envs[0], a, u)
+        torch_sim_step(envs[1], a, u)
+        for name in CHECKED:
+            x, y = getattr(envs[0], name).double(), getattr(envs[1], name).double()
+            worst = max(worst, float(((x - y).abs() / (1 + y.abs())).max()))
+        for name in CHECKED:                                   # keep the two on one trajectory
+            getattr(envs[1], name).copy_(getattr(envs[0], name))
+    assert worst <= 1e-5, f"the torch restatement differs from dtc_sim_step by {worst:.2e}"
+    t_k, t_t = [], []
+    for i in range(calls + 20):
+        a, u = torch.randn(num_envs, 12, generator=g, device=DEV), torch.rand(num_envs, 3, generator=g, device=DEV)
+        for acc, fn, e in ((t_k, lambda: envs[0].sim.step(envs[0], a, u), 0), (t_t, lambda: torch_sim_step(envs[1], a, u), 1)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if i >= 20:
+                acc.append(1e6 * (time.perf_counter() - t0))
+    return statistics.median(t_k), statistics.median(t_t), worst
+
+
+def spread(vals, fmt="{:.1f}"):
+    return f"{fmt.format(statistics.median(vals))} ({fmt.format(min(vals))} .. {fmt.format(max(vals))})"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--calls", type=int, default=200)
+    ap.add_argument("--signal", action="store_true")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    lines = [f"closed loop on SurrogateLeggedEnv: {args.envs} envs x {STEPS} steps per iteration, {args.iters} iterations, PPO, fixed seeds",
+             "", "iteration: mean step reward | mean episode length (finished, last <= 100) | mean length in flight"]
+    for tag, algo in RUNS:
+        lines.append(f"  {tag}")
+        for i, (rw, ln, fl) in enumerate(learning_curve(args.envs, args.iters, algo), 1):
+            lines.append(f"    {i:3d}  {rw:+.6f} | {'-' if ln is None else f'{ln:.1f}'} | {fl:.1f}")
+    rounds = {tag: [] for tag, _ in RUNS}
+    for _ in range(3):
+        for tag, algo in RUNS:
+            rounds[tag].append(timing_round(args.envs, args.iters, algo))
+    lines += ["", "three interleaved rounds, median (min .. max):"]
+    for tag, _ in RUNS:
+        rs = rounds[tag]
+        lines.append(f"  {tag:14s} env-steps/s, whole loop {spread([r['steps_per_s'] for r in rs], '{:.0f}')}")
+        lines.append(f"  {'':14s} ms per iteration, each call closed by a synchronise: env.step x{STEPS} {spread([r['env_ms'] for r in rs], '{:.2f}')}"
+                     f" | act() x{STEPS} {spread([r['act_ms'] for r in rs], '{:.2f}')} | update() {spread([r['update_ms'] for r in rs], '{:.2f}')}")
+    probes = [sim_step_probe(args.envs, args.calls) for _ in range(3)]
+    lines += ["", f"one surrogate step at {args.envs} envs, us per call (host clock, closed by a synchronise), three rounds:",
+              f"  dtc_sim_step (one launch)      {spread([p[0] for p in probes])}",
+              f"  torch restatement of the step  {spread([p[1] for p in probes])}   (largest difference to the kernel: {max(p[2] for p in probes):.1e})"]
+    if args.signal:
+        rows = learning_curve(256, 30, {})
+        first, last = statistics.mean(r[0] for r in rows[:5]), statistics.mean(r[0] for r in rows[25:30])
+        lines += ["", "learning signal: 256 envs, 30 iterations, default arithmetic, mean step reward per iteration:",
+                  "  " + " ".join(f"{r[0]:+.5f}" for r in rows),
+                  f"  iterations 1-5: {first:+.6f}   iterations 26-30: {last:+.6f}   difference: {last - first:+.6f}"]
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text)
+
+
+if __name__ == "__main__":
+    main()

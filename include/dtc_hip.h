@@ -5,6 +5,10 @@
  * in deep-tracking-control_amd/dtc_amd keep the reference's signatures and call these through
  * ctypes with `tensor.data_ptr()` (INTEGRATION.md shows the binding).
  *
+ * One entry point has no counterpart in the reference: dtc_sim_step, a kinematic surrogate of the simulator behind env.step()
+ * that fills the Isaac Gym tensors the env-side entry points read, so they can run closed loop on one GPU.  It is not physics;
+ * its section lists what is absent.
+ *
  * Conventions
  *   - every pointer is a DEVICE pointer unless the parameter is documented as host;
  *   - the caller owns all buffers; nothing is retained after return;
@@ -38,7 +42,7 @@ extern "C" {
 #define DTC_ACT_SIGMOID 6
 
 /* library / device info ------------------------------------------------------------------ */
-#define DTC_ABI_VERSION 21                  /* bumped whenever a signature or a by-value struct layout changes       */
+#define DTC_ABI_VERSION 22                  /* bumped whenever a signature or a by-value struct layout changes       */
 int dtc_version(void);                       /* == DTC_ABI_VERSION of the build; the host binding refuses a mismatch   */
 /* sizeof() of the structs that cross the boundary, in the order DtcGridCfg, DtcObsCfg, DtcRowCopy, DtcSeg, DtcSegMat,
    DtcFwdLayer, DtcWgradJob, DtcPpoCfg, DtcProfRec, DtcWimgJob, DtcH2iWJob, DtcH2iOperand, DtcWgradH2iJob, DtcEnvStep, DtcH2iFwdLayer, DtcH2iDgradLayer, DtcGruFwdItem, DtcGruBwdItem: the binding compares them with its own layouts at load time (a library
@@ -375,6 +379,95 @@ int64_t dtc_env_reset_workspace(int N, int n_sums);
    load time.  Returns the number of entries (written up to `cap`). */
 int dtc_env_reset_abi_sizes(int64_t* out, int cap);
 int dtc_env_reset(const DtcResetStep* st, const DtcResetCfg* cfg, int N, void* stream);
+
+/* ---- surrogate legged env: the state the env kernels above run on, with no simulator ------
+ * dtc_sim_step (csrc/sim.hip) stands where the reference calls Isaac Gym: `decimation` substeps of _compute_torques, control type "P"
+ * (legged_robot.py:610-630, the current action where the reference takes a randomly lagged one), a kinematic quadruped, and the
+ * bookkeeping of post_physics_step up to the planner (legged_robot_dtc.py:66-91, legged_robot.py:534-535, :562-564), as ONE launch,
+ * one wavefront per env, each env row loaded once and stored once.  It is a surrogate, not physics: state that is consistent,
+ * evolves, responds to actions and can terminate.  Absent on purpose: roll and pitch (the quaternion keeps x = y = 0,
+ * projected_gravity is (0, 0, -1)), base dynamics (the base rides on its stance feet), lag buffers, pushes (`forces` are not
+ * touched), control types "V" and "T", and the heading command's yaw law (legged_robot.py:537-539 stays with the caller).
+ *
+ * Every value is a single-rounded fp32 operation in the order below (-ffp-contract=off; tests/sim_oracle.py restates it in numpy
+ * float32, bit for bit).  Joint j = 3 l + k is joint k of leg l; sums over legs run in leg order 0..3 from 0.0f.  Once per step:
+ *   a = min(max(action, -clip_actions), clip_actions)                      -> actions
+ *   goal = min(max(a * action_scale + default, lo), hi);   kp = p_gain * Kp_factor;   kd = d_gain * Kd_factor
+ * One substep:
+ *   1. tau = min(max(((kp * ((goal - q) + offset)) - kd * qd) * strength, -limit), limit)
+ *   2. qd = qd + (tau / joint_inertia) * dt;  q = q + qd * dt;  q < lo: q = lo, qd = 0;  q > hi: q = hi, qd = 0
+ *   3. p_l[i] = foot_nominal[l][i] + ((J[l][i][0] * dq0 + J[l][i][1] * dq1) + J[l][i][2] * dq2),  dq = q - default;
+ *      u_l[i] = (J[l][i][0] * qd0 + J[l][i][1] * qd1) + J[l][i][2] * qd2
+ *   4. c = 1 - 2 * (qz * qz);  s = 2 * (qz * qw);  foot world xy: fx = x + (c * p.x - s * p.y),  fy = y + (s * p.x + c * p.y)
+ *   5. h_l: the _get_heights rule (legged_robot.py:1301-1316) at (fx, fy): index = clamp((long)((f + border) / hscale), 0, size - 2),
+ *      min of the three samples, times vertical_scale
+ *   6. base_z = max_l(h_l - p_l.z);  contact_l = ((base_z + p_l.z) - h_l) <= contact_eps;  n_c = number of contacts (>= 1)
+ *   7. pm = (sum of stance p.xy) / n_c;  um = (sum of stance u.xy) / n_c;  over the stance legs, dp = p - pm, du = u - um:
+ *      num = sum(dp.x * du.y - dp.y * du.x);  den = sum(dp.x * dp.x + dp.y * dp.y);  w = den > r_min * r_min ? -(num / den) : 0
+ *      vb.x = (-um.x) + w * pm.y;  vb.y = (-um.y) - w * pm.x             (the least-squares twist of "stance feet do not slip")
+ *   8. x = x + (c * vb.x - s * vb.y) * dt;  y = y + (s * vb.x + c * vb.y) * dt;  vz = (base_z - z) / dt;  z = base_z
+ *      e = (0.5 * dt) * w;  z' = qz + e * qw;  w' = qw - e * qz;  r = sqrt(z' * z' + w' * w');  qz = z' / r;  qw = w' / r
+ * After the last substep, with c, s of the NEW quaternion and V = (c * vb.x - s * vb.y, s * vb.x + c * vb.y):
+ *   root_states = [x, y, z, 0, 0, qz, qw, V.x, V.y, vz, 0, 0, w];  dof_pos, dof_vel, torques (the last substep's);
+ *   base_lin_vel = (vb.x, vb.y, vz);  last_base_ang_vel = the base_ang_vel found;  base_ang_vel = (0, 0, w);
+ *   projected_gravity = (0, 0, -1);  base_quat = (0, 0, qz, qw);  base_pos = (x, y, z);
+ *   rigid_body_state[foot_l]: columns 0..2 = (x + (c p.x - s p.y), y + (s p.x + c p.y), z + p.z), columns 7..9 = (V.x + (c r.x - s r.y),
+ *   V.y + (s r.x + c r.y), vz + u.z) with r = (u.x - w * p.y, u.y + w * p.x);  rigid_body_state[thigh_l]: columns 0..2 = base + R hip_offset_l;
+ *   the other columns and bodies of rigid_body_state are left alone;
+ *   contact_forces[n] = 0 except [foot_l][2] = contact_l ? weight / n_c : 0.
+ * Then: episode_length_buf += 1; the three time-major ring buffers [T, N, .] shift by one and take (vb.x, vb.y), w and the commands
+ * as they stand; envs with episode_length_buf % resampling_steps == 0 resample their commands as _resample_commands does
+ * (:573-591: x, y, and heading (column 3) or yaw rate (column 2); xy zeroed when their norm is <= 0.1) from u_cmd [N,3] in [0, 1),
+ * or with u_cmd == NULL from Philox4x32-10 (key = seed, counter = (n, 0, call counter), words x, y, z, 24 bits each, as
+ * dtc_env_reset draws); contact = contact_forces[foot, 2] > 1;  contact_filt = contact | last_contacts;  last_contacts = contact.
+ * `st`, `cfg` are HOST pointers; every pointer inside is a DEVICE pointer and, except u_cmd, required. */
+typedef struct DtcSimCfg {
+    int32_t num_dof;                 /* 12: four legs of three joints                                                     */
+    int32_t num_bodies;              /* B: rows of rigid_body_state[n] / contact_forces[n]                                */
+    int32_t num_commands;            /* C: columns of commands / cmd_buffer (>= 3; >= 4 with heading_command)             */
+    int32_t decimation;              /* substeps per env step (1..64)                                                     */
+    int32_t heading_command;         /* the third draw goes to column 3, not 2                                            */
+    int32_t buffer_len;              /* T of the ring buffers (10)                                                        */
+    int32_t feet[4], thighs[4];      /* body indices, leg order                                                           */
+    int64_t resampling_steps;        /* int(cfg.commands.resampling_time / dt) (>= 1)                                     */
+    float sim_dt, action_scale, clip_actions, joint_inertia, contact_eps, weight, r_min;
+    int32_t rows, cols;              /* terrain table [rows, cols] int16 (both >= 2)                                      */
+    float border_size, horizontal_scale, vertical_scale;
+    double lin_vel_x[2], lin_vel_y[2], ang_vel_yaw[2], heading[2];      /* [lo, hi], entering as float32(hi - lo), float32(lo) */
+    uint64_t seed, counter;          /* generated draws only                                                              */
+} DtcSimCfg;
+
+typedef struct DtcSimStep {
+    /* inputs */
+    const float* actions_in;         /* [N,D] the policy's actions                                                        */
+    const float *Kp_factors, *Kd_factors, *motor_strengths, *motor_offsets;       /* [N,D]                                */
+    const int16_t* height_samples;   /* [rows, cols]                                                                      */
+    const float* u_cmd;              /* [N,3] or NULL (generated)                                                         */
+    const float *p_gains, *d_gains, *torque_limits, *default_dof_pos;             /* [D]                                  */
+    const float* dof_pos_limits;     /* [D,2]                                                                             */
+    const float *hip_offset, *foot_nominal;      /* [4,3] base frame                                                      */
+    const float* leg_jacobian;       /* [4,3,3]: d foot_l[i] / d q[3 l + k] at the default pose                           */
+    /* read and written */
+    float *dof_pos, *dof_vel;        /* [N,D] strided as in DtcResetStep                                                  */
+    int64_t dof_pos_row_stride, dof_pos_elem_stride, dof_vel_row_stride, dof_vel_elem_stride;
+    float* root_states;              /* [N,13]                                                                            */
+    float* base_ang_vel;             /* [N,3]                                                                             */
+    float* commands;                 /* [N,C]                                                                             */
+    int64_t* episode_length_buf;     /* [N]                                                                               */
+    uint8_t* last_contacts;          /* [N,4] bool                                                                        */
+    float *lin_vel_buffer, *ang_vel_buffer, *cmd_buffer;       /* [T,N,2], [T,N,1], [T,N,C]                               */
+    /* written */
+    float* rigid_body_state;         /* [N,B,13]: foot and thigh rows                                                     */
+    float* contact_forces;           /* [N,B,3]                                                                           */
+    float *torques, *actions;        /* [N,D]                                                                             */
+    float *base_lin_vel, *last_base_ang_vel, *projected_gravity, *base_pos;       /* [N,3]                                */
+    float* base_quat;                /* [N,4]                                                                             */
+    uint8_t* contact_filt;           /* [N,4] bool                                                                        */
+} DtcSimStep;
+/* sizeof() of DtcSimCfg, DtcSimStep, in a table of their own (dtc_abi_sizes keeps its 18 entries): compared by the binding at load
+   time.  Returns the number of entries (written up to `cap`). */
+int dtc_sim_abi_sizes(int64_t* out, int cap);
+int dtc_sim_step(const DtcSimStep* st, const DtcSimCfg* cfg, int N, void* stream);
 
 /* ---- rollout-side store (row f2) ---------------------------------------------------------
  * RolloutStorage.add_transitions, rsl_rl/rsl_rl/storage/rollout_storage.py:99-116: the 13 `copy_` of one env step as
