@@ -6,10 +6,12 @@
 // least-squares fit of "stance feet do not slip", then the bookkeeping of post_physics_step up to the planner
 // (legged_robot_dtc.py:66-91, legged_robot.py:534-535 with _resample_commands :573-591, and :562-564).
 //
-// It is a surrogate, not physics.  Deliberately absent: roll and pitch (quaternion x = y = 0, projected gravity (0, 0, -1)), base
-// dynamics (no free flight: at least one foot is always in contact), lag buffers (the current action stands where the reference takes
-// a randomly lagged one), pushes (`forces` are never touched), control types "V" and "T", and the heading command's yaw law
-// (legged_robot.py:537-539), which stays with the caller.
+// It is a surrogate, not physics.  dtc_sim_step keeps the base level (quaternion x = y = 0, projected gravity (0, 0, -1));
+// dtc_sim_step_tilt, the other instantiation of the same kernel, lets roll and pitch follow the least-squares plane through the
+// support points the terrain asks of the stance feet -- kinematically: after a reset (identity quaternion) the first fit is one
+// substep with a tilt-rate spike.  Deliberately absent from both: attitude and base dynamics (no free flight: at least one foot is
+// always in contact), lag buffers (the current action stands where the reference takes a randomly lagged one), pushes (`forces` are
+// never touched), control types "V" and "T", and the heading command's yaw law (legged_robot.py:537-539), which stays with the caller.
 //
 // One 64-lane wavefront per env, 4 envs per 256-thread workgroup (as csrc/envstep.hip).  Lanes 0..11 own the joints (leg l owns
 // 3l..3l+2) and lane 3l+i computes component i of foot l; the twelve foot components are then broadcast with v_readlane and every lane
@@ -37,6 +39,7 @@ struct SimK {
     float border, hscale, vscale;
     Span cmd_x, cmd_y, cmd_third;
     unsigned seed_lo, seed_hi, ctr_lo, ctr_hi;
+    float max_slope, min_det;                   // dtc_sim_step_tilt only
 };
 
 __device__ __forceinline__ float bcast(float v, int src_lane) {                    // src_lane is wave-uniform
@@ -56,6 +59,24 @@ __device__ __forceinline__ float terrain_height(const int16_t* __restrict__ hs, 
     return (float)h * k.vscale;
 }
 
+// The tilt rotation Rt, the minimal rotation that takes z to n = (nx, ny, nz): third column n, third row (-nx, -ny, nz), and the
+// three entries computed here (Rt[0][1] = Rt[1][0]).
+struct TiltR { float r00, r01, r11; };
+__device__ __forceinline__ TiltR tilt_entries(float nx, float ny, float nz) {
+    const float k1 = 1.0f + nz;
+    return TiltR{1.0f - (nx * nx) / k1, -((nx * ny) / k1), 1.0f - (ny * ny) / k1};
+}
+__device__ __forceinline__ void tilt_rotate(const TiltR& R, float nx, float ny, float nz, const float v[3], float out[3]) {       // Rt v
+    out[0] = (R.r00 * v[0] + R.r01 * v[1]) + nx * v[2];
+    out[1] = (R.r01 * v[0] + R.r11 * v[1]) + ny * v[2];
+    out[2] = (-(nx * v[0]) - ny * v[1]) + nz * v[2];
+}
+__device__ __forceinline__ void tilt_rotate_t(const TiltR& R, float nx, float ny, float nz, const float v[3], float out[3]) {     // Rt^T v
+    out[0] = (R.r00 * v[0] + R.r01 * v[1]) - nx * v[2];
+    out[1] = (R.r01 * v[0] + R.r11 * v[1]) - ny * v[2];
+    out[2] = (nx * v[0] + ny * v[1]) + nz * v[2];
+}
+
 // INVARIANTS of this kernel's signature and launch:
 //  * the descriptor `s` is the FIRST parameter, so it lies at offset 0 of the kernel-argument segment: the rows written after the
 //    loop take their pointers from there (see below).  A parameter put in front of it breaks that silently; keep the order.
@@ -63,6 +84,9 @@ __device__ __forceinline__ float terrain_height(const int16_t* __restrict__ hs, 
 //    wavefront's index): the ring-buffer shift below has lanes load slot t + 1 and store slot t of the same env, which is right
 //    only because a wavefront's loads issue ahead of its stores and nobody else writes those slots.
 static_assert(offsetof(DtcSimStep, actions_in) == 0 && sizeof(DtcSimStep) % 8 == 0, "descriptor layout the late loads rely on");
+// TILT = false is dtc_sim_step, the yaw-only base; TILT = true is dtc_sim_step_tilt: the body z-axis n (yaw frame) lives in the
+// quaternion between steps and in three registers through the loop, and r = Rt p, sv = Rt u stand where the yaw-only step has p, u.
+template <bool TILT>
 __global__ __launch_bounds__(256) void sim_step_kernel(const DtcSimStep s, const SimK k, int N) {
     const int lane = threadIdx.x & 63;
     const int n = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
@@ -92,6 +116,18 @@ __global__ __launch_bounds__(256) void sim_step_kernel(const DtcSimStep s, const
     const int leg0 = joint ? (lane / 3) * 3 : 0;                                   // first joint lane of this lane's leg
     const float* rs = s.root_states + e * 13;
     float x = rs[0], y = rs[1], z = rs[2], qz = rs[5], qw = rs[6];
+    float nx = 0.f, ny = 0.f, nz = 1.f, wx = 0.f, wy = 0.f;                        // TILT: body z-axis in the yaw frame, its rate
+    if constexpr (TILT) {                                                          // twist about z (the yaw pair) and swing (n)
+        const float qx = rs[3], qy = rs[4];
+        const float ry = sqrtf(qz * qz + qw * qw);
+        const float zy = qz / ry, wyw = qw / ry;
+        const float c = 1.0f - 2.0f * (zy * zy), sn = 2.0f * (zy * wyw);
+        const float ax = 2.0f * (qx * qz + qw * qy), ay = 2.0f * (qy * qz - qw * qx), az = 1.0f - 2.0f * (qx * qx + qy * qy);
+        const float mx = c * ax + sn * ay, my = c * ay - sn * ax;
+        const float rn = sqrtf((mx * mx + my * my) + az * az);
+        nx = mx / rn, ny = my / rn, nz = az / rn;
+        qz = zy, qw = wyw;
+    }
     float old_ang = 0.f;
     if (lane < 3) old_ang = s.base_ang_vel[e * 3 + lane];
     const long long elen = s.episode_length_buf[e] + 1;
@@ -126,41 +162,94 @@ __global__ __launch_bounds__(256) void sim_step_kernel(const DtcSimStep s, const
         for (int l = 0; l < 4; ++l)
 #pragma unroll
             for (int i = 0; i < 3; ++i) p[l][i] = bcast(pl, 3 * l + i), u[l][i] = bcast(ul, 3 * l + i);
-        // 4. yaw-only base, 5. terrain under each foot, 6. support and contact
+        // the feet in the yaw frame: r = Rt p, sv = Rt u (TILT), or p, u themselves
+        float r[4][3], sv[4][3];
+        if constexpr (TILT) {
+            const TiltR R = tilt_entries(nx, ny, nz);
+#pragma unroll
+            for (int l = 0; l < 4; ++l) tilt_rotate(R, nx, ny, nz, p[l], r[l]), tilt_rotate(R, nx, ny, nz, u[l], sv[l]);
+        } else {
+#pragma unroll
+            for (int l = 0; l < 4; ++l)
+#pragma unroll
+                for (int i = 0; i < 3; ++i) r[l][i] = p[l][i], sv[l][i] = u[l][i];
+        }
+        // 4. yaw, 5. terrain under each foot, 6. support and contact
         const float c = 1.0f - 2.0f * (qz * qz), sn = 2.0f * (qz * qw);
         float h[4];
 #pragma unroll
         for (int l = 0; l < 4; ++l) {
-            const float fx = x + (c * p[l][0] - sn * p[l][1]);
-            const float fy = y + (sn * p[l][0] + c * p[l][1]);
+            const float fx = x + (c * r[l][0] - sn * r[l][1]);
+            const float fy = y + (sn * r[l][0] + c * r[l][1]);
             h[l] = terrain_height(s.height_samples, k, fx, fy);
         }
-        float bz = h[0] - p[0][2];
+        float bz = h[0] - r[0][2];
 #pragma unroll
-        for (int l = 1; l < 4; ++l) bz = fmaxf(bz, h[l] - p[l][2]);
+        for (int l = 1; l < 4; ++l) bz = fmaxf(bz, h[l] - r[l][2]);
         nc = 0.f;
 #pragma unroll
         for (int l = 0; l < 4; ++l) {
-            ct[l] = ((bz + p[l][2]) - h[l]) <= k.eps;
+            ct[l] = ((bz + r[l][2]) - h[l]) <= k.eps;
             nc = nc + (ct[l] ? 1.0f : 0.0f);
         }
-        // 7. base twist: planar least squares of v_b + w z^ x p_l + u_l = 0 over the stance feet
+        // 7. base twist: planar least squares of v_b + w z^ x r_l + sv_l = 0 over the stance feet
         float spx = 0.f, spy = 0.f, sux = 0.f, suy = 0.f;
 #pragma unroll
         for (int l = 0; l < 4; ++l)
-            if (ct[l]) spx = spx + p[l][0], spy = spy + p[l][1], sux = sux + u[l][0], suy = suy + u[l][1];
+            if (ct[l]) spx = spx + r[l][0], spy = spy + r[l][1], sux = sux + sv[l][0], suy = suy + sv[l][1];
         const float pmx = spx / nc, pmy = spy / nc, umx = sux / nc, umy = suy / nc;
         float num = 0.f, den = 0.f;
 #pragma unroll
         for (int l = 0; l < 4; ++l)
             if (ct[l]) {
-                const float dpx = p[l][0] - pmx, dpy = p[l][1] - pmy, dux = u[l][0] - umx, duy = u[l][1] - umy;
+                const float dpx = r[l][0] - pmx, dpy = r[l][1] - pmy, dux = sv[l][0] - umx, duy = sv[l][1] - umy;
                 num = num + (dpx * duy - dpy * dux);
                 den = den + (dpx * dpx + dpy * dpy);
             }
         w = den > k.rmin2 ? -(num / den) : 0.0f;
         vbx = (-umx) + w * pmy;
         vby = (-umy) - w * pmx;
+        if constexpr (TILT) {
+            // the new tilt.  Stance legs: those extended to within eps of the most extended one (body frame: the legs the env stands
+            // on, whether or not the current plane has them on the ground).  Centred least squares of d_l = h_l - p_l.z =
+            // c0 + a p_l.x + b p_l.y over them, every d_l relative to the first stance leg's; then the tilt rate, the small-angle
+            // reading of dn/dt = omega x n
+            float zmin = p[0][2];
+#pragma unroll
+            for (int l = 1; l < 4; ++l) zmin = p[l][2] < zmin ? p[l][2] : zmin;
+            bool sl[4];
+            float ns = 0.f, d[4];
+#pragma unroll
+            for (int l = 0; l < 4; ++l) {
+                sl[l] = (p[l][2] - zmin) <= k.eps;
+                ns = ns + (sl[l] ? 1.0f : 0.0f);
+                d[l] = h[l] - p[l][2];
+            }
+            const float d0 = sl[0] ? d[0] : (sl[1] ? d[1] : (sl[2] ? d[2] : d[3]));
+            float tpx = 0.f, tpy = 0.f, te = 0.f;
+#pragma unroll
+            for (int l = 0; l < 4; ++l)
+                if (sl[l]) tpx = tpx + p[l][0], tpy = tpy + p[l][1], te = te + (d[l] - d0);
+            const float mx = tpx / ns, my = tpy / ns, me = te / ns;
+            float sxx = 0.f, sxy = 0.f, syy = 0.f, sxe = 0.f, sye = 0.f;
+#pragma unroll
+            for (int l = 0; l < 4; ++l)
+                if (sl[l]) {
+                    const float dx = p[l][0] - mx, dy = p[l][1] - my, de = (d[l] - d0) - me;
+                    sxx = sxx + dx * dx, sxy = sxy + dx * dy, syy = syy + dy * dy;
+                    sxe = sxe + dx * de, sye = sye + dy * de;
+                }
+            const float det = sxx * syy - sxy * sxy;
+            const float sa = (sxe * syy - sye * sxy) / det, sb = (sye * sxx - sxe * sxy) / det;
+            const float ca = sa < -k.max_slope ? -k.max_slope : (sa > k.max_slope ? k.max_slope : sa);
+            const float cb = sb < -k.max_slope ? -k.max_slope : (sb > k.max_slope ? k.max_slope : sb);
+            const float rr = sqrtf((ca * ca + cb * cb) + 1.0f);
+            const bool fit = ns >= 3.0f && det > k.min_det;
+            const float nnx = fit ? (-ca) / rr : nx, nny = fit ? (-cb) / rr : ny, nnz = fit ? 1.0f / rr : nz;
+            wx = -((nny - ny) / k.dt);
+            wy = (nnx - nx) / k.dt;
+            nx = nnx, ny = nny, nz = nnz;
+        }
         // 8. integrate the base
         x = x + (c * vbx - sn * vby) * k.dt;
         y = y + (sn * vbx + c * vby) * k.dt;
@@ -168,9 +257,9 @@ __global__ __launch_bounds__(256) void sim_step_kernel(const DtcSimStep s, const
         z = bz;
         const float ee = k.half_dt * w;
         const float zn = qz + ee * qw, wn = qw - ee * qz;
-        const float r = sqrtf(zn * zn + wn * wn);
-        qz = zn / r;
-        qw = wn / r;
+        const float rq = sqrtf(zn * zn + wn * wn);
+        qz = zn / rq;
+        qw = wn / rq;
     }
 
     // ---- the env's rows, once.  Every load of the bookkeeping below that another lane's store could change is issued first.
@@ -185,6 +274,21 @@ __global__ __launch_bounds__(256) void sim_step_kernel(const DtcSimStep s, const
     const float c = 1.0f - 2.0f * (qz * qz), sn = 2.0f * (qz * qw);
     const float Vx = c * vbx - sn * vby, Vy = sn * vbx + c * vby;
     const float fz = k.weight / nc;
+    // TILT: everything below takes the NEW tilt, as it takes the new yaw.  bl, ba: the base velocities in the body frame (Rt^T);
+    // oq: q_yaw (x) q_tilt, q_tilt = (-ny, nx, 0, 1 + nz) / sqrt(2 (1 + nz))
+    TiltR R{1.f, 0.f, 1.f};
+    float bl[3] = {vbx, vby, vz}, ba[3] = {0.0f, 0.0f, w}, Wx = 0.f, Wy = 0.f, oq[4] = {0.0f, 0.0f, qz, qw};
+    if constexpr (TILT) {
+        R = tilt_entries(nx, ny, nz);
+        const float vv[3] = {vbx, vby, vz}, wv[3] = {wx, wy, w};
+        tilt_rotate_t(R, nx, ny, nz, vv, bl);
+        tilt_rotate_t(R, nx, ny, nz, wv, ba);
+        Wx = c * wx - sn * wy, Wy = sn * wx + c * wy;
+        const float k1 = 1.0f + nz;
+        const float dn = sqrtf(2.0f * k1);
+        const float tx = (-ny) / dn, ty = nx / dn, tw = k1 / dn;
+        oq[0] = qw * tx - qz * ty, oq[1] = qw * ty + qz * tx, oq[2] = qz * tw, oq[3] = qw * tw;
+    }
 
     if (joint) {
         o->dof_pos[e * o->dof_pos_row_stride + lane * o->dof_pos_elem_stride] = q;
@@ -194,24 +298,29 @@ __global__ __launch_bounds__(256) void sim_step_kernel(const DtcSimStep s, const
     }
     if (lane < 13) {
         float v = 0.f;
-        v = lane == 0 ? x : v, v = lane == 1 ? y : v, v = lane == 2 ? z : v, v = lane == 5 ? qz : v, v = lane == 6 ? qw : v;
+        v = lane == 0 ? x : v, v = lane == 1 ? y : v, v = lane == 2 ? z : v, v = lane == 5 ? oq[2] : v, v = lane == 6 ? oq[3] : v;
         v = lane == 7 ? Vx : v, v = lane == 8 ? Vy : v, v = lane == 9 ? vz : v, v = lane == 12 ? w : v;
+        if constexpr (TILT) v = lane == 3 ? oq[0] : v, v = lane == 4 ? oq[1] : v, v = lane == 10 ? Wx : v, v = lane == 11 ? Wy : v;
         o->root_states[e * 13 + lane] = v;
     }
     if (lane < 3) {
-        o->base_lin_vel[e * 3 + lane] = lane == 0 ? vbx : (lane == 1 ? vby : vz);
+        o->base_lin_vel[e * 3 + lane] = lane == 0 ? bl[0] : (lane == 1 ? bl[1] : bl[2]);
         o->last_base_ang_vel[e * 3 + lane] = old_ang;
-        o->base_ang_vel[e * 3 + lane] = lane == 2 ? w : 0.0f;
-        o->projected_gravity[e * 3 + lane] = lane == 2 ? -1.0f : 0.0f;
+        o->base_ang_vel[e * 3 + lane] = lane == 0 ? ba[0] : (lane == 1 ? ba[1] : ba[2]);
+        if constexpr (TILT) o->projected_gravity[e * 3 + lane] = lane == 0 ? nx : (lane == 1 ? ny : -nz);
+        else o->projected_gravity[e * 3 + lane] = lane == 2 ? -1.0f : 0.0f;
         o->base_pos[e * 3 + lane] = lane == 0 ? x : (lane == 1 ? y : z);
     }
-    if (lane < 4) o->base_quat[e * 4 + lane] = lane == 2 ? qz : (lane == 3 ? qw : 0.0f);
+    if (lane < 4) o->base_quat[e * 4 + lane] = lane == 0 ? oq[0] : (lane == 1 ? oq[1] : (lane == 2 ? oq[2] : oq[3]));
     // foot rows (lanes 16 + 6 l + i: position i < 3, velocity i >= 3) and thigh rows (lanes 40 + 3 l + i) of rigid_body_state
 #pragma unroll
     for (int l = 0; l < 4; ++l) {
-        const float rx = u[l][0] - w * p[l][1], ry = u[l][1] + w * p[l][0];
-        const float f0 = x + (c * p[l][0] - sn * p[l][1]), f1 = y + (sn * p[l][0] + c * p[l][1]), f2 = z + p[l][2];
-        const float g0 = Vx + (c * rx - sn * ry), g1 = Vy + (sn * rx + c * ry), g2 = vz + u[l][2];
+        float r[3] = {p[l][0], p[l][1], p[l][2]}, sv[3] = {u[l][0], u[l][1], u[l][2]};
+        if constexpr (TILT) tilt_rotate(R, nx, ny, nz, p[l], r), tilt_rotate(R, nx, ny, nz, u[l], sv);
+        float rx = sv[0] - w * r[1], ry = sv[1] + w * r[0], rz = sv[2];
+        if constexpr (TILT) rx = rx + wy * r[2], ry = ry - wx * r[2], rz = rz + (wx * r[1] - wy * r[0]);      // the tilt rate's lever arm
+        const float f0 = x + (c * r[0] - sn * r[1]), f1 = y + (sn * r[0] + c * r[1]), f2 = z + r[2];
+        const float g0 = Vx + (c * rx - sn * ry), g1 = Vy + (sn * rx + c * ry), g2 = vz + rz;
         const int i = lane - (16 + 6 * l);
         if (i >= 0 && i < 6) {
             const float v = i == 0 ? f0 : (i == 1 ? f1 : (i == 2 ? f2 : (i == 3 ? g0 : (i == 4 ? g1 : g2))));
@@ -220,8 +329,12 @@ __global__ __launch_bounds__(256) void sim_step_kernel(const DtcSimStep s, const
     }
     if (lane >= 40 && lane < 52) {
         const int l = (lane - 40) / 3, m = lane - 40 - 3 * l;
-        const float hx = o->hip_offset[l * 3], hy = o->hip_offset[l * 3 + 1], hz = o->hip_offset[l * 3 + 2];
-        const float t0 = x + (c * hx - sn * hy), t1 = y + (sn * hx + c * hy), t2 = z + hz;
+        float hp[3] = {o->hip_offset[l * 3], o->hip_offset[l * 3 + 1], o->hip_offset[l * 3 + 2]};
+        if constexpr (TILT) {
+            const float hb[3] = {hp[0], hp[1], hp[2]};
+            tilt_rotate(R, nx, ny, nz, hb, hp);
+        }
+        const float t0 = x + (c * hp[0] - sn * hp[1]), t1 = y + (sn * hp[0] + c * hp[1]), t2 = z + hp[2];
         const float v = m == 0 ? t0 : (m == 1 ? t1 : t2);
 #pragma unroll
         for (int ll = 0; ll < 4; ++ll)                                             // constant index into the by-value struct
@@ -239,14 +352,14 @@ __global__ __launch_bounds__(256) void sim_step_kernel(const DtcSimStep s, const
     for (int i0 = 0; i0 < T * 2; i0 += 64) {
         const int i = i0 + lane, t = i >> 1, col = i & 1;
         if (i < T * 2) {
-            const float v = t + 1 < T ? o->lin_vel_buffer[((long long)(t + 1) * N + e) * 2 + col] : (col == 0 ? vbx : vby);
+            const float v = t + 1 < T ? o->lin_vel_buffer[((long long)(t + 1) * N + e) * 2 + col] : (col == 0 ? bl[0] : bl[1]);
             o->lin_vel_buffer[((long long)t * N + e) * 2 + col] = v;
         }
     }
     for (int i0 = 0; i0 < T; i0 += 64) {
         const int t = i0 + lane;
         if (t < T) {
-            const float v = t + 1 < T ? o->ang_vel_buffer[(long long)(t + 1) * N + e] : w;
+            const float v = t + 1 < T ? o->ang_vel_buffer[(long long)(t + 1) * N + e] : ba[2];
             o->ang_vel_buffer[(long long)t * N + e] = v;
         }
     }
@@ -291,13 +404,20 @@ Span span_of(const double r[2]) { return Span{(float)(r[1] - r[0]), (float)r[0]}
 
 }  // namespace
 
+extern "C" int dtc_sim_tilt_abi_sizes(int64_t* out, int cap) {
+    const int64_t sz[] = {sizeof(DtcSimTilt)};
+    if (cap > 0 && out) out[0] = sz[0];
+    return 1;
+}
+
 extern "C" int dtc_sim_abi_sizes(int64_t* out, int cap) {
     const int64_t sz[] = {sizeof(DtcSimCfg), sizeof(DtcSimStep)};
     for (int i = 0; i < 2 && i < cap && out; ++i) out[i] = sz[i];
     return 2;
 }
 
-extern "C" int dtc_sim_step(const DtcSimStep* st, const DtcSimCfg* cfg, int N, void* stream) {
+// dtc_sim_step (tilt == nullptr) and dtc_sim_step_tilt: one validation, one descriptor, the two instantiations of one kernel
+static int sim_step_launch(const DtcSimStep* st, const DtcSimCfg* cfg, const DtcSimTilt* tilt, int N, void* stream) {
     DTC_REQUIRE(st && cfg, "null descriptor");
     DTC_REQUIRE(N > 0 && N <= (1 << 24), "N %d outside 1..2^24", N);
     const DtcSimStep& s = *st;
@@ -336,7 +456,23 @@ extern "C" int dtc_sim_step(const DtcSimStep* st, const DtcSimCfg* cfg, int N, v
     k.seed_lo = (unsigned)c.seed, k.seed_hi = (unsigned)(c.seed >> 32), k.ctr_lo = (unsigned)c.counter, k.ctr_hi = (unsigned)(c.counter >> 32);
 
     hipStream_t hs = (hipStream_t)stream;
-    dtc::ProfScope prof("sim_step", (double)N * (2048.0 + 12.0 * c.num_bodies + 8.0 * c.buffer_len * (3 + c.num_commands)), hs);
-    hipLaunchKernelGGL(sim_step_kernel, dim3((unsigned)dtc::ceil_div(N, 4)), dim3(256), 0, hs, s, k, N);
+    dtc::ProfScope prof(tilt ? "sim_step_tilt" : "sim_step", (double)N * (2048.0 + 12.0 * c.num_bodies + 8.0 * c.buffer_len * (3 + c.num_commands)), hs);
+    if (tilt) {
+        DTC_REQUIRE(tilt->max_slope > 0.f && tilt->max_slope <= 1e3f && tilt->min_det >= 0.f, "max_slope %g outside (0, 1000] or min_det %g < 0",
+                    (double)tilt->max_slope, (double)tilt->min_det);
+        k.max_slope = tilt->max_slope, k.min_det = tilt->min_det;
+        hipLaunchKernelGGL(sim_step_kernel<true>, dim3((unsigned)dtc::ceil_div(N, 4)), dim3(256), 0, hs, s, k, N);
+        return dtc::check_launch("sim_step_tilt");
+    }
+    hipLaunchKernelGGL(sim_step_kernel<false>, dim3((unsigned)dtc::ceil_div(N, 4)), dim3(256), 0, hs, s, k, N);
     return dtc::check_launch("sim_step");
+}
+
+extern "C" int dtc_sim_step(const DtcSimStep* st, const DtcSimCfg* cfg, int N, void* stream) {
+    return sim_step_launch(st, cfg, nullptr, N, stream);
+}
+
+extern "C" int dtc_sim_step_tilt(const DtcSimStep* st, const DtcSimCfg* cfg, const DtcSimTilt* tilt, int N, void* stream) {
+    DTC_REQUIRE(tilt, "null DtcSimTilt");
+    return sim_step_launch(st, cfg, tilt, N, stream);
 }

@@ -197,6 +197,11 @@ class DtcSimStep(C.Structure):
                                            "base_quat", "contact_filt")])
 
 
+class DtcSimTilt(C.Structure):
+    """include/dtc_hip.h: the two constants dtc_sim_step_tilt adds to DtcSimCfg."""
+    _fields_ = [("max_slope", C.c_float), ("min_det", C.c_float)]
+
+
 class DtcRowCopy(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("src_stride_bytes", C.c_int64), ("width_bytes", C.c_int32)]
 
@@ -221,7 +226,7 @@ class DtcProfRec(C.Structure):
 ACT = {None: 0, "none": 0, "relu": 1, "crelu": 1, "elu": 2, "selu": 3, "lrelu": 4, "tanh": 5, "sigmoid": 6}
 MAX_OPERAND_ELEMS = (1 << 29) - 1
 
-ABI_VERSION = 22        # DTC_ABI_VERSION of include/dtc_hip.h this binding was written against
+ABI_VERSION = 23        # DTC_ABI_VERSION of include/dtc_hip.h this binding was written against
 
 _SIGS = {
     "dtc_version": (C.c_int, []),
@@ -248,6 +253,8 @@ _SIGS = {
     "dtc_env_reset": (C.c_int, [C.POINTER(DtcResetStep), C.POINTER(DtcResetCfg), C.c_int, c_stream]),
     "dtc_sim_abi_sizes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
     "dtc_sim_step": (C.c_int, [C.POINTER(DtcSimStep), C.POINTER(DtcSimCfg), C.c_int, c_stream]),
+    "dtc_sim_tilt_abi_sizes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
+    "dtc_sim_step_tilt": (C.c_int, [C.POINTER(DtcSimStep), C.POINTER(DtcSimCfg), C.POINTER(DtcSimTilt), C.c_int, c_stream]),
     "dtc_check_termination": (C.c_int, [c_f32p, C.c_int, c_i32p, C.c_int, c_i64p, C.c_int64, c_f32p, c_f32p, c_f32p,
                                         C.POINTER(DtcObsCfg), c_u8p, c_u8p, c_f32p, C.c_int, c_stream]),
     "dtc_store_transition": (C.c_int, [C.POINTER(DtcRowCopy), C.c_int, c_f32p, c_f32p, c_u8p, C.c_float, c_f32p,
@@ -460,6 +467,9 @@ def _check_abi(l):
     theirs += list(sizes[:n])
     mine += [DtcSimCfg, DtcSimStep]                                       # ... and by the surrogate env's
     n = l.dtc_sim_abi_sizes(sizes, 32)
+    theirs += list(sizes[:n])
+    mine += [DtcSimTilt]                                                  # ... and by its tilt entry point's
+    n = l.dtc_sim_tilt_abi_sizes(sizes, 32)
     theirs += list(sizes[:n])
     if l.dtc_version() != ABI_VERSION or theirs != [C.sizeof(t) for t in mine]:
         _lib = None

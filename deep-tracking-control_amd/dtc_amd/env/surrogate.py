@@ -6,7 +6,7 @@ observations), `EnvRewards`, `EnvReset` on `reset_buf`, `compute_observations(wh
 (legged_robot_dtc.py:215-223) and the observation clip (legged_robot.py:118-121).  Nothing in `step()` reads the device or calls
 `nonzero()`.  The env owns every tensor under the attribute name the reference env uses.
 
-It is a surrogate, not physics (include/dtc_hip.h lists what is absent): it gives the kernels a state that is consistent, evolves,
+It is a surrogate, not physics (include/dtc_hip.h lists what is absent; `SimConfig.tilt` opts into a kinematic roll and pitch): it gives the kernels a state that is consistent, evolves,
 responds to actions, terminates and resets, and a reward that depends on what the policy does.
 """
 from __future__ import annotations
@@ -171,8 +171,12 @@ class SurrogateLeggedEnv(VecEnv):
         c, s = self.config, self.config.sim
         # 1. the surrogate's physics and the bookkeeping up to the planner
         self.sim.step(self, actions.to(self.device, torch.float32).contiguous(), draws.get("u_cmd"))
-        if s.heading_command:                                                            # legged_robot.py:537-539, yaw-only base
-            heading = torch.atan2(2.0 * self.base_quat[:, 2] * self.base_quat[:, 3], 1.0 - 2.0 * self.base_quat[:, 2] * self.base_quat[:, 2])
+        if s.heading_command:                                                            # legged_robot.py:537-539
+            if s.tilt:                                                                   # forward = quat_apply(q, (1, 0, 0))
+                qx, qy, qz, qw = self.base_quat.unbind(dim=1)
+                heading = torch.atan2(2.0 * (qx * qy + qw * qz), 1.0 - 2.0 * (qy * qy + qz * qz))
+            else:                                                                        # the same, for a yaw-only base
+                heading = torch.atan2(2.0 * self.base_quat[:, 2] * self.base_quat[:, 3], 1.0 - 2.0 * self.base_quat[:, 2] * self.base_quat[:, 2])
             d = self.commands[:, 3] - heading
             d = torch.remainder(d + math.pi, 2 * math.pi) - math.pi                      # wrap_to_pi
             self.commands[:, 2] = torch.clip(0.5 * d, -1.5, 1.5)

@@ -1,8 +1,10 @@
-"""Host side of the surrogate legged env step (csrc/sim.hip, `dtc_sim_step`): the state the env kernels run on when no simulator
-stands behind them.  One launch per env step stands where the reference calls Isaac Gym: `decimation` substeps of the PD law of
-LeggedRobot._compute_torques (control type "P"), a kinematic quadruped that rides on its stance feet over the int16 terrain table,
-and the bookkeeping of post_physics_step up to the planner.  include/dtc_hip.h states every operation; it is a surrogate, not
-physics (no roll / pitch, no base dynamics, no lag buffers, no pushes, no "V" / "T" control, no heading yaw law).
+"""Host side of the surrogate legged env step (csrc/sim.hip, `dtc_sim_step` and `dtc_sim_step_tilt`): the state the env kernels run
+on when no simulator stands behind them.  One launch per env step stands where the reference calls Isaac Gym: `decimation` substeps
+of the PD law of LeggedRobot._compute_torques (control type "P"), a kinematic quadruped that rides on its stance feet over the int16
+terrain table, and the bookkeeping of post_physics_step up to the planner.  include/dtc_hip.h states every operation; it is a
+surrogate, not physics (no attitude or base dynamics, no free flight, no lag buffers, no pushes, no "V" / "T" control, no heading
+yaw law).  By default the base only yaws; `SimConfig.tilt` (opt-in) lets its roll and pitch follow the support points of the stance
+feet, still kinematically: after a reset the identity quaternion then gives one step with a tilt-rate spike.
 
 `SimConfig` holds the constants (Lite3 DTC values), `leg_tables(config)` the three small tables computed once in float64 from a
 two-link leg linearised at the default pose, and `SimStep` runs the launch on an env's own tensors (attribute names as in
@@ -63,6 +65,13 @@ class SimConfig:
     border_size: float = 20.0
     horizontal_scale: float = 0.05
     vertical_scale: float = 0.005
+    tilt: bool = False                       # roll and pitch from the stance feet (dtc_sim_step_tilt); off: dtc_sim_step, bit for bit
+    max_slope: float = 1.0                   # the fitted plane's slopes are clamped to +- max_slope (45 degrees)
+    # a stance keeps its tilt unless the determinant of its centred xy scatter exceeds min_det [m^4].  Three feet give
+    # det = (2 A)^2 / 3 (A: the triangle's area), so 1e-6 asks for 2 A > 1.7e-3 m^2: a triangle with a base of r_min = 0.05 m and a
+    # height of 0.035 m.  Any three feet of the default stance (0.34 m x 0.2 m) give 1.5e-3, fp32 rounding of a collinear stance
+    # of that size 1e-10.
+    min_det: float = 1e-6
 
     @property
     def dt(self) -> float:
@@ -112,7 +121,7 @@ def flat_table(rows: int = 1400, cols: int = 900, device="cpu") -> torch.Tensor:
 
 
 class SimStep:
-    """`dtc_sim_step` for `num_envs` envs over the terrain table `height_samples` [rows, cols] int16.  Owns the small device tables
+    """`dtc_sim_step` (`dtc_sim_step_tilt` with `config.tilt`) for `num_envs` envs over the terrain table `height_samples` [rows, cols] int16.  Owns the small device tables
     (`tables`: float32 copies of `leg_tables` / `joint_tables`).  `step(env, actions, u_cmd=None)` runs one env step in place on the
     tensors of `env`; with `u_cmd` left out the kernel draws the command resamples itself (Philox, keyed by `seed` and a call
     counter)."""
@@ -179,6 +188,10 @@ class SimStep:
         for name, t in self.tables.items():
             setattr(s, name, _ffi.ptr(t))
         c = self.cfg_struct()
-        _ffi.check(_ffi.lib().dtc_sim_step(s, c, N, _ffi.stream()), "dtc_sim_step")
+        if k.tilt:
+            tilt = _ffi.DtcSimTilt(float(k.max_slope), float(k.min_det))
+            _ffi.check(_ffi.lib().dtc_sim_step_tilt(s, c, tilt, N, _ffi.stream()), "dtc_sim_step_tilt")
+        else:
+            _ffi.check(_ffi.lib().dtc_sim_step(s, c, N, _ffi.stream()), "dtc_sim_step")
         if u_cmd is None:
             self.counter += 1

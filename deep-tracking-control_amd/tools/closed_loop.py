@@ -3,6 +3,8 @@
 
     python deep-tracking-control_amd/tools/closed_loop.py [--envs 4096] [--iters 10] [--out profiles/closed_loop.txt]
     python deep-tracking-control_amd/tools/closed_loop.py --signal        # + the learning-signal run: 256 envs, 30 iterations
+    python deep-tracking-control_amd/tools/closed_loop.py --tilt [--out profiles/closed_loop_tilt.txt]
+                                                                          # the yaw-only env beside the tilt env (SimConfig.tilt), timing only
 
 Per run and iteration: the mean step reward (mean of rew_buf over the iteration's 24 steps and all envs), the mean episode length
 (the runner's tracker: the last <= 100 finished episodes; "-" before the first one ends) and the mean length of the episodes in flight.
@@ -12,6 +14,8 @@ Timing, three interleaved rounds (default, one pass, default, ...), each figure 
     host-clock window that ends in a device synchronise (so the three do not overlap, and their sum exceeds the whole loop's time);
   * dtc_sim_step beside the torch restatement of the same step (below: the same arithmetic as torch ops on the same tensors, checked
     against the kernel to 1e-5 before it is timed), alternating, median of --calls windows each.
+With --tilt the two runs are the yaw-only env and the tilt env, both over the rough table `synthetic.reward_table()` (on the flat one
+the tilt stays level), default arithmetic: the same three interleaved rounds, and dtc_sim_step beside dtc_sim_step_tilt, alternating.
 """
 import argparse
 import os
@@ -24,6 +28,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 
+from dtc_amd import sim as SIM, synthetic  # noqa: E402
 from dtc_amd.env import SurrogateConfig, SurrogateLeggedEnv  # noqa: E402
 from dtc_amd.runners import OnPolicyRunner  # noqa: E402
 from dtc_amd.runners.on_policy_runner import _EpisodeTracker  # noqa: E402
@@ -33,9 +38,14 @@ STEPS = 24
 RUNS = (("default", {}), ("gemm_passes=1", dict(gemm_passes=1)))
 
 
-def make(num_envs, algo, seed=11):
+def rough_env(num_envs, tilt):
+    return SurrogateLeggedEnv(num_envs, DEV, SurrogateConfig(sim=SIM.SimConfig(tilt=tilt)), synthetic.reward_table(), seed=5)
+
+
+def make(num_envs, algo, seed=11, tilt=None):
+    """`tilt` None: the default env on the flat table; False / True: the yaw-only / the tilt env on the rough table."""
     torch.manual_seed(seed)
-    env = SurrogateLeggedEnv(num_envs, DEV, SurrogateConfig(), seed=5)
+    env = SurrogateLeggedEnv(num_envs, DEV, SurrogateConfig(), seed=5) if tilt is None else rough_env(num_envs, tilt)
     runner = dict(policy_class_name="ActorCriticDecoder", algorithm_class_name="PPO", num_steps_per_env=STEPS, save_interval=10 ** 9)
     return OnPolicyRunner(env, dict(runner=runner, algorithm=dict(algo), policy=dict()), log_dir=None, device=DEV), env
 
@@ -81,8 +91,8 @@ def timed(fn, acc):
     return f
 
 
-def timing_round(num_envs, iters, algo):
-    r, env = make(num_envs, algo)
+def timing_round(num_envs, iters, algo, tilt=None):
+    r, env = make(num_envs, algo, tilt=tilt)
     r.learn(2)                                                # warm-up: allocations, first launches
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -205,6 +215,48 @@ def sim_step_probe(num_envs, calls):
     return statistics.median(t_k), statistics.median(t_t), worst
 
 
+def tilt_probe(num_envs, calls):
+    """dtc_sim_step beside dtc_sim_step_tilt on the rough table, same actions, alternating: us per call (median)."""
+    envs = [rough_env(num_envs, tilt) for tilt in (False, True)]
+    g = torch.Generator(device=DEV).manual_seed(3)
+    for e in envs:
+        e.reset()
+    acc = ([], [])
+    for i in range(calls + 20):
+        a, u = torch.randn(num_envs, 12, generator=g, device=DEV), torch.rand(num_envs, 3, generator=g, device=DEV)
+        for t, e in zip(acc, envs):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            e.sim.step(e, a, u)
+            torch.cuda.synchronize()
+            if i >= 20:
+                t.append(1e6 * (time.perf_counter() - t0))
+    tilted = float((envs[1].projected_gravity[:, :2].abs().amax(dim=1) > 0.01).float().mean())
+    return statistics.median(acc[0]), statistics.median(acc[1]), tilted
+
+
+def tilt_report(args):
+    runs = (("yaw only", False), ("tilt", True))
+    rounds = {tag: [] for tag, _ in runs}
+    for _ in range(3):
+        for tag, tilt in runs:
+            rounds[tag].append(timing_round(args.envs, args.iters, {}, tilt=tilt))
+    lines = [f"closed loop on SurrogateLeggedEnv over the rough table, yaw-only base beside SimConfig(tilt=True): {args.envs} envs x {STEPS} steps "
+             f"per iteration, {args.iters} iterations, PPO, default arithmetic, fixed seeds",
+             "", "three interleaved rounds, median (min .. max):"]
+    for tag, _ in runs:
+        rs = rounds[tag]
+        lines.append(f"  {tag:9s} env-steps/s, whole loop {spread([r['steps_per_s'] for r in rs], '{:.0f}')}")
+        lines.append(f"  {'':9s} ms per iteration, each call closed by a synchronise: env.step x{STEPS} {spread([r['env_ms'] for r in rs], '{:.2f}')}"
+                     f" | act() x{STEPS} {spread([r['act_ms'] for r in rs], '{:.2f}')} | update() {spread([r['update_ms'] for r in rs], '{:.2f}')}")
+    probes = [tilt_probe(args.envs, args.calls) for _ in range(3)]
+    lines += ["", f"one surrogate step at {args.envs} envs, us per call (host clock, closed by a synchronise), alternating, three rounds:",
+              f"  dtc_sim_step (yaw only)  {spread([p[0] for p in probes])}",
+              f"  dtc_sim_step_tilt        {spread([p[1] for p in probes])}   (envs tilted by more than 0.01 at the end: "
+              f"{100 * statistics.mean(p[2] for p in probes):.0f} %)"]
+    return lines
+
+
 def spread(vals, fmt="{:.1f}"):
     return f"{fmt.format(statistics.median(vals))} ({fmt.format(min(vals))} .. {fmt.format(max(vals))})"
 
@@ -215,8 +267,16 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--signal", action="store_true")
+    ap.add_argument("--tilt", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.tilt:
+        text = "\n".join(tilt_report(args)) + "\n"
+        print(text)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text)
+        return
     lines = [f"closed loop on SurrogateLeggedEnv: {args.envs} envs x {STEPS} steps per iteration, {args.iters} iterations, PPO, fixed seeds",
              "", "iteration: mean step reward | mean episode length (finished, last <= 100) | mean length in flight"]
     for tag, algo in RUNS:

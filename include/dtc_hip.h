@@ -42,7 +42,7 @@ extern "C" {
 #define DTC_ACT_SIGMOID 6
 
 /* library / device info ------------------------------------------------------------------ */
-#define DTC_ABI_VERSION 22                  /* bumped whenever a signature or a by-value struct layout changes       */
+#define DTC_ABI_VERSION 23                  /* bumped whenever a signature or a by-value struct layout changes       */
 int dtc_version(void);                       /* == DTC_ABI_VERSION of the build; the host binding refuses a mismatch   */
 /* sizeof() of the structs that cross the boundary, in the order DtcGridCfg, DtcObsCfg, DtcRowCopy, DtcSeg, DtcSegMat,
    DtcFwdLayer, DtcWgradJob, DtcPpoCfg, DtcProfRec, DtcWimgJob, DtcH2iWJob, DtcH2iOperand, DtcWgradH2iJob, DtcEnvStep, DtcH2iFwdLayer, DtcH2iDgradLayer, DtcGruFwdItem, DtcGruBwdItem: the binding compares them with its own layouts at load time (a library
@@ -385,8 +385,9 @@ int dtc_env_reset(const DtcResetStep* st, const DtcResetCfg* cfg, int N, void* s
  * (legged_robot.py:610-630, the current action where the reference takes a randomly lagged one), a kinematic quadruped, and the
  * bookkeeping of post_physics_step up to the planner (legged_robot_dtc.py:66-91, legged_robot.py:534-535, :562-564), as ONE launch,
  * one wavefront per env, each env row loaded once and stored once.  It is a surrogate, not physics: state that is consistent,
- * evolves, responds to actions and can terminate.  Absent on purpose: roll and pitch (the quaternion keeps x = y = 0,
- * projected_gravity is (0, 0, -1)), base dynamics (the base rides on its stance feet), lag buffers, pushes (`forces` are not
+ * evolves, responds to actions and can terminate.  In dtc_sim_step the base only yaws (the quaternion keeps x = y = 0,
+ * projected_gravity is (0, 0, -1)); dtc_sim_step_tilt, below, adds a kinematic roll and pitch.  Absent on purpose from both:
+ * attitude and base dynamics (no free flight: the base rides on its stance feet), lag buffers, pushes (`forces` are not
  * touched), control types "V" and "T", and the heading command's yaw law (legged_robot.py:537-539 stays with the caller).
  *
  * Every value is a single-rounded fp32 operation in the order below (-ffp-contract=off; tests/sim_oracle.py restates it in numpy
@@ -468,6 +469,61 @@ typedef struct DtcSimStep {
    time.  Returns the number of entries (written up to `cap`). */
 int dtc_sim_abi_sizes(int64_t* out, int cap);
 int dtc_sim_step(const DtcSimStep* st, const DtcSimCfg* cfg, int N, void* stream);
+
+/* ---- surrogate legged env with roll and pitch (opt-in) ------------------------------------
+ * dtc_sim_step_tilt is dtc_sim_step with a body plane that follows the support points of the stance feet over the terrain table.
+ * Still kinematic, still ONE launch (the other instantiation of the same kernel), still not physics: there are no attitude dynamics,
+ * the tilt is a least-squares plane through where the terrain asks the stance feet to be.  No new tensor: the tilt lives in the
+ * quaternion of root_states[:, 3:7] between steps.  Absent as before: base dynamics and free flight, lag buffers, pushes, control
+ * types "V" and "T", the heading command's yaw law.  After a reset the quaternion is the identity, so the first fit on sloped ground
+ * is one step whose tilt rate (w.x, w.y below) is the whole tilt divided by sim_dt: a spike by construction.
+ *
+ * Only + - * /, sqrt and comparisons, each a single-rounded fp32 operation in the order below (tests/sim_tilt_oracle.py restates it
+ * in numpy float32, bit for bit, and is the specification).  Rt(n), for a unit vector n, is the minimal rotation that takes z to n:
+ *   k1 = 1 + n.z;   Rt = [[1 - (n.x * n.x) / k1,  -((n.x * n.y) / k1),  n.x],
+ *                         [-((n.x * n.y) / k1),   1 - (n.y * n.y) / k1, n.y],
+ *                         [-n.x,                  -n.y,                 n.z]]
+ *   Rt v   = ((R00 * v.x + R01 * v.y) + n.x * v.z,  (R01 * v.x + R11 * v.y) + n.y * v.z,  (-(n.x * v.x) - n.y * v.y) + n.z * v.z)
+ *   Rt^T v = ((R00 * v.x + R01 * v.y) - n.x * v.z,  (R01 * v.x + R11 * v.y) - n.y * v.z,  (n.x * v.x + n.y * v.y) + n.z * v.z)
+ * At load, q = (qx, qy, qz, qw) = root_states[3:7] is split into its twist about z and the remaining swing:
+ *   ry = sqrt(qz * qz + qw * qw);  the yaw pair (zy, wy) = (qz / ry, qw / ry) stands where dtc_sim_step has (qz, qw);
+ *   c = 1 - 2 * (zy * zy);  s = 2 * (zy * wy);
+ *   the body z-axis in the world: A = (2 * (qx * qz + qw * qy),  2 * (qy * qz - qw * qx),  1 - 2 * (qx * qx + qy * qy));
+ *   in the yaw frame: m = (c * A.x + s * A.y,  c * A.y - s * A.x,  A.z);  n = m / sqrt((m.x * m.x + m.y * m.y) + m.z * m.z)
+ *   (the identity quaternion, and every quaternion with qx = qy = 0, gives n = (0, 0, 1) exactly).
+ * One substep: steps 1..3 of dtc_sim_step give p_l, u_l (body frame); then
+ *   T1. r_l = Rt(n) p_l;  sv_l = Rt(n) u_l.  Steps 4..8 run as stated above with r_l, sv_l in place of p_l, u_l: the terrain lookup
+ *       under each foot, base_z = max_l(h_l - r_l.z), contact_l = ((base_z + r_l.z) - h_l) <= contact_eps, the no-slip twist fit.
+ *   T2. the new tilt, after step 7.  The stance legs of the fit are those extended to within contact_eps of the most extended leg, in the
+ *       body frame: zmin = min_l p_l.z (by comparisons);  stance_l = (p_l.z - zmin) <= contact_eps;  n_s = their number.  (The contact
+ *       test of step 6 cannot choose them: it is taken under the CURRENT tilt, so a level base on a slope has only its uphill feet
+ *       in contact and its plane would never move.  Legs the policy lifts leave the fit; the contacts of step 6 stay what they are.)
+ *       d_l = h_l - p_l.z;  d0 = d of the first stance leg;  over the stance legs, from 0.0f in leg order:
+ *       tp = sum p_l.xy;  te = sum (d_l - d0);  m = tp / n_s;  me = te / n_s;  dx = p_l.x - m.x;  dy = p_l.y - m.y;  de = (d_l - d0) - me;
+ *       Sxx = sum dx * dx;  Sxy = sum dx * dy;  Syy = sum dy * dy;  Sxe = sum dx * de;  Sye = sum dy * de;
+ *       det = Sxx * Syy - Sxy * Sxy;  a = (Sxe * Syy - Sye * Sxy) / det;  b = (Sye * Sxx - Sxe * Sxy) / det
+ *       (the centred least-squares fit d = c0 + a p.x + b p.y; equal d_l give a = b = 0 exactly);
+ *       a, b clamped by comparisons to [-max_slope, max_slope];  rr = sqrt((a * a + b * b) + 1);
+ *       n_new = n_s >= 3 and det > min_det ? ((-a) / rr, (-b) / rr, 1 / rr) : n
+ *   T3. the tilt rate in the yaw frame: w.x = -((n_new.y - n.y) / dt);  w.y = (n_new.x - n.x) / dt: the small-angle reading of
+ *       dn/dt = omega x n (at n = z it is exact; the error grows with the square of the tilt).  Then n = n_new, then step 8.
+ * After the last substep, with c, s of the NEW yaw pair, Rt of the NEW n, r_l = Rt p_l, sv_l = Rt u_l, V as in dtc_sim_step:
+ *   k1 = 1 + n.z;  dn = sqrt(2 * k1);  q_tilt = (tx, ty, 0, tw) = ((-n.y) / dn, n.x / dn, 0, k1 / dn);
+ *   q = q_yaw (x) q_tilt = (wy * tx - zy * ty,  wy * ty + zy * tx,  zy * tw,  wy * tw)         -> root_states[3:7], base_quat;
+ *   root_states[7:13] = (V.x, V.y, vz, c * w.x - s * w.y, s * w.x + c * w.y, w)  (both velocities in the world frame);
+ *   base_lin_vel = Rt^T (vb.x, vb.y, vz);  base_ang_vel = Rt^T (w.x, w.y, w);  projected_gravity = (n.x, n.y, -n.z);
+ *   rigid_body_state[foot_l]: columns 0..2 = (x + (c r.x - s r.y), y + (s r.x + c r.y), z + r.z), columns 7..9 = (V.x + (c g.x - s g.y),
+ *   V.y + (s g.x + c g.y), vz + g.z) with g = ((sv.x - w * r.y) + w.y * r.z, (sv.y + w * r.x) - w.x * r.z, sv.z + (w.x * r.y - w.y * r.x));
+ *   rigid_body_state[thigh_l]: columns 0..2 = base + Rz (Rt hip_offset_l);
+ *   lin_vel_buffer takes base_lin_vel[0:2] and ang_vel_buffer base_ang_vel[2] (legged_robot_dtc.py:76-79).
+ * Everything else is exactly as in dtc_sim_step. */
+typedef struct DtcSimTilt {
+    float max_slope;                 /* bound of the fitted slopes a, b (> 0)                                             */
+    float min_det;                   /* m^4: a stance whose centred xy scatter has det <= min_det keeps the tilt (>= 0)   */
+} DtcSimTilt;
+/* sizeof() of DtcSimTilt, in a table of its own (dtc_sim_abi_sizes keeps its 2 entries). */
+int dtc_sim_tilt_abi_sizes(int64_t* out, int cap);
+int dtc_sim_step_tilt(const DtcSimStep* st, const DtcSimCfg* cfg, const DtcSimTilt* tilt, int N, void* stream);
 
 /* ---- rollout-side store (row f2) ---------------------------------------------------------
  * RolloutStorage.add_transitions, rsl_rl/rsl_rl/storage/rollout_storage.py:99-116: the 13 `copy_` of one env step as
