@@ -202,6 +202,13 @@ class DtcSimTilt(C.Structure):
     _fields_ = [("max_slope", C.c_float), ("min_det", C.c_float)]
 
 
+class DtcTerrainCfg(C.Structure):
+    """include/dtc_hip.h: the configuration of dtc_terrain_generate; field order as there."""
+    _fields_ = ([(k, C.c_double) for k in ("horizontal_scale", "vertical_scale", "border_size", "terrain_length", "terrain_width")] +
+                [("proportions", C.c_double * 9)] +
+                [(k, C.c_int32) for k in ("num_rows", "num_cols", "curriculum", "tot_rows", "tot_cols", "reserved")] + [("seed", C.c_uint64)])
+
+
 class DtcRowCopy(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("src_stride_bytes", C.c_int64), ("width_bytes", C.c_int32)]
 
@@ -226,7 +233,7 @@ class DtcProfRec(C.Structure):
 ACT = {None: 0, "none": 0, "relu": 1, "crelu": 1, "elu": 2, "selu": 3, "lrelu": 4, "tanh": 5, "sigmoid": 6}
 MAX_OPERAND_ELEMS = (1 << 29) - 1
 
-ABI_VERSION = 23        # DTC_ABI_VERSION of include/dtc_hip.h this binding was written against
+ABI_VERSION = 24        # DTC_ABI_VERSION of include/dtc_hip.h this binding was written against
 
 _SIGS = {
     "dtc_version": (C.c_int, []),
@@ -255,6 +262,8 @@ _SIGS = {
     "dtc_sim_step": (C.c_int, [C.POINTER(DtcSimStep), C.POINTER(DtcSimCfg), C.c_int, c_stream]),
     "dtc_sim_tilt_abi_sizes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
     "dtc_sim_step_tilt": (C.c_int, [C.POINTER(DtcSimStep), C.POINTER(DtcSimCfg), C.POINTER(DtcSimTilt), C.c_int, c_stream]),
+    "dtc_terrain_abi_sizes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
+    "dtc_terrain_generate": (C.c_int, [C.POINTER(DtcTerrainCfg), C.c_void_p, C.c_void_p, c_stream]),
     "dtc_check_termination": (C.c_int, [c_f32p, C.c_int, c_i32p, C.c_int, c_i64p, C.c_int64, c_f32p, c_f32p, c_f32p,
                                         C.POINTER(DtcObsCfg), c_u8p, c_u8p, c_f32p, C.c_int, c_stream]),
     "dtc_store_transition": (C.c_int, [C.POINTER(DtcRowCopy), C.c_int, c_f32p, c_f32p, c_u8p, C.c_float, c_f32p,
@@ -470,6 +479,9 @@ def _check_abi(l):
     theirs += list(sizes[:n])
     mine += [DtcSimTilt]                                                  # ... and by its tilt entry point's
     n = l.dtc_sim_tilt_abi_sizes(sizes, 32)
+    theirs += list(sizes[:n])
+    mine += [DtcTerrainCfg]                                               # ... and by the terrain generator's
+    n = l.dtc_terrain_abi_sizes(sizes, 32)
     theirs += list(sizes[:n])
     if l.dtc_version() != ABI_VERSION or theirs != [C.sizeof(t) for t in mine]:
         _lib = None

@@ -8,6 +8,14 @@ observations), `EnvRewards`, `EnvReset` on `reset_buf`, `compute_observations(wh
 
 It is a surrogate, not physics (include/dtc_hip.h lists what is absent; `SimConfig.tilt` opts into a kinematic roll and pitch): it gives the kernels a state that is consistent, evolves,
 responds to actions, terminates and resets, and a reward that depends on what the policy does.
+
+`SurrogateConfig.terrain` (opt-in, a `terrain.TerrainConfig`; None: the env above, bit for bit) puts the env on the DTC curriculum
+terrain generated on the device (`dtc_amd.terrain`): stairs, stepping stones, gaps, pits.  The env origins are then the sub-terrain
+origins, `terrain_levels` / `terrain_types` are set as LeggedRobot._get_env_origins does (legged_robot.py:1205-1215) and the terrain
+curriculum of reset_idx runs on state that evolves.  What this is NOT: the surrogate rides on its highest support, so a foot over a
+hole is simply out of contact, and an env whose four feet are all over a gap drops to the gap floor kinematically and climbs the far
+wall in one step -- there is no falling, no collision with a wall and no getting stuck; the terrain shapes the footholds, the height
+scan, the rewards and the curriculum, not a contact dynamics.
 """
 from __future__ import annotations
 
@@ -18,6 +26,7 @@ import numpy as np
 import torch
 
 from .. import foothold, reset, rewards, sim
+from ..terrain import Terrain, TerrainConfig
 from .vec_env import VecEnv
 
 # raw reward scales (multiplied by dt, as the reference does): a Lite3-style set in which every term reads surrogate state
@@ -40,6 +49,7 @@ class SurrogateConfig:
     noise_scales: dict = field(default_factory=lambda: dict(ang_vel=0.2, gravity=0.05, dof_pos=0.01, dof_vel=1.5))
     contain_nonfinite: bool = True           # an env whose dofs or root state are not finite after the surrogate step is reset at once
     env_spacing: float = 1.0                 # env origins: rows of 32 envs, this far apart, inside the terrain table
+    terrain: TerrainConfig | None = None     # opt-in: the DTC curriculum terrain, generated on the device (None: the tables above)
 
     @property
     def max_episode_length(self) -> int:
@@ -55,6 +65,13 @@ class SurrogateConfig:
     def reset_config(self) -> reset.ResetConfig:
         s = self.sim
         init = (0.0, 0.0, s.nominal_height, 0.0, 0.0, 0.0, 1.0) + (0.0,) * 6
+        t = self.terrain
+        if t is not None:
+            return reset.ResetConfig(terrain_curriculum=bool(t.curriculum), custom_origins=True, max_terrain_level=int(t.num_rows),
+                                     env_length=float(t.terrain_length), heading_command=s.heading_command,
+                                     randomize_motor_strength=self.randomize_motor_strength, max_episode_length_s=self.episode_length_s,
+                                     lin_vel_x=s.lin_vel_x, lin_vel_y=s.lin_vel_y, ang_vel_yaw=s.ang_vel_yaw, heading=s.heading,
+                                     base_init_state=init)
         return reset.ResetConfig(terrain_curriculum=False, custom_origins=False, heading_command=s.heading_command,
                                  randomize_motor_strength=self.randomize_motor_strength, max_episode_length_s=self.episode_length_s,
                                  lin_vel_x=s.lin_vel_x, lin_vel_y=s.lin_vel_y, ang_vel_yaw=s.ang_vel_yaw, heading=s.heading,
@@ -74,11 +91,30 @@ class SurrogateLeggedEnv(VecEnv):
     the rough one).  `step(actions, draws=None)`: `draws` is the parity mode -- a dict with any of u_cmd [N,3], u_reset [N,26],
     u_obs [N,53], u_heights [N,693] (uniform [0,1)) and height_noise (float); what it leaves out is drawn on the device from `seed`
     (command and reset draws by the kernels' Philox streams, the two observation noises by a seeded device generator); the reset's
-    height_noise is the reference's host draw, np.random.normal(0, 0.02), from a seeded RandomState."""
+    height_noise is the reference's host draw, np.random.normal(0, 0.02), from a seeded RandomState.
+
+    With `config.terrain` set the table is the generated DTC terrain (`self.terrain`, a `dtc_amd.terrain.Terrain`; passing
+    `height_samples` as well is an error), `terrain_levels` is drawn in [0, max_init_terrain_level] from the env's seeded device
+    generator unless given, the first `reset()` leaves the levels alone (init_done, legged_robot.py:693-695), later resets move
+    them, `draws` may carry level_draw [N] int64 next to u_reset, and `extras["episode"]["terrain_level"]` is the mean level
+    (a device scalar).  `regenerate_terrain(seed)` lays the terrain out anew in place."""
 
     def __init__(self, num_envs: int, device="cuda", config: SurrogateConfig | None = None, height_samples: torch.Tensor | None = None,
-                 seed: int = 0):
+                 seed: int = 0, terrain_levels: torch.Tensor | None = None):
         c = self.config = config or SurrogateConfig()
+        tc = c.terrain
+        if tc is not None:
+            if height_samples is not None:
+                raise ValueError("SurrogateLeggedEnv: config.terrain generates the table; height_samples cannot be given as well")
+            tc.validate()
+            for name in ("horizontal_scale", "vertical_scale", "border_size"):
+                if float(getattr(tc, name)) != float(getattr(c.sim, name)):
+                    raise ValueError(f"SurrogateLeggedEnv: terrain.{name} {getattr(tc, name)} != sim.{name} {getattr(c.sim, name)}")
+            max_init = int(tc.max_init_terrain_level) if tc.curriculum else tc.num_rows - 1          # legged_robot.py:1209-1210
+            if not 0 <= max_init < tc.num_rows:
+                raise ValueError(f"SurrogateLeggedEnv: max_init_terrain_level {max_init} outside 0..{tc.num_rows - 1}")
+        elif terrain_levels is not None:
+            raise ValueError("SurrogateLeggedEnv: terrain_levels needs config.terrain")
         dev = torch.device(device)
         if dev.type == "cuda" and dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())
@@ -88,7 +124,11 @@ class SurrogateLeggedEnv(VecEnv):
         self.num_obs, self.num_privileged_obs = 9 + 3 * D + c.obs.num_foothold_obs, 2 * P + 3
         self.num_obs_history = c.num_observation_history * self.num_obs
         self.max_episode_length, self.dt = c.max_episode_length, s.dt
-        self.height_samples = (sim.flat_table() if height_samples is None else height_samples).to(dev).contiguous()
+        self.terrain = Terrain(tc, dev) if tc is not None else None
+        if self.terrain is not None:
+            self.height_samples = self.terrain.height_field_raw
+        else:
+            self.height_samples = (sim.flat_table() if height_samples is None else height_samples).to(dev).contiguous()
         self.sim = sim.SimStep(N, dev, s, self.height_samples, seed=seed)
         f = dict(dtype=torch.float32, device=dev)
         z = lambda *shape: torch.zeros(*shape, **f)                                      # noqa: E731
@@ -140,6 +180,19 @@ class SurrogateLeggedEnv(VecEnv):
         self._out = self.env_step.out
         self.reset_buf, self.time_out_buf = self._out["reset_buf"], self._out["time_out_buf"]
         self.obs_buf, self.privileged_obs_buf = self._out["obs_buf"], self._out["privileged_obs_buf"]
+        self.custom_origins, self.init_done = self.terrain is not None, self.terrain is None
+        if self.terrain is not None:                                                     # _get_env_origins, legged_robot.py:1205-1215
+            if terrain_levels is None:
+                terrain_levels = torch.randint(0, max_init + 1, (N,), generator=self._gen, device=dev)
+            elif tuple(terrain_levels.shape) != (N,) or terrain_levels.dtype != torch.int64:
+                raise ValueError(f"SurrogateLeggedEnv: terrain_levels must be an int64 tensor of shape {(N,)}")
+            self.terrain_levels = terrain_levels.to(dev).clone().contiguous()
+            self.terrain_types = torch.div(torch.arange(N, device=dev), N / tc.num_cols, rounding_mode="floor").to(torch.long)
+            self.max_terrain_level = tc.num_rows
+            self.terrain_origins = self.terrain.env_origins
+            self.env_origins = self.terrain_origins[self.terrain_levels, self.terrain_types].contiguous()
+            if tc.curriculum:
+                self._episode["terrain_level"] = self.env_reset.terrain_level_mean[0]   # legged_robot.py:257-259
 
     # ------------------------------------------------------------------ one env step
     def _observation_inputs(self, draws):
@@ -155,7 +208,11 @@ class SurrogateLeggedEnv(VecEnv):
     def _reset_envs(self, draws):
         """reset_idx for the envs named in reset_buf (legged_robot.py:200-272), one dtc_env_reset call."""
         hn = draws.get("height_noise")
-        self.env_reset(reset_buf=self.reset_buf, root_states=self.root_states, env_origins=self.env_origins, commands=self.commands,
+        on_terrain = {}
+        if self.terrain is not None:
+            on_terrain = dict(terrain_levels=self.terrain_levels, terrain_types=self.terrain_types, terrain_origins=self.terrain_origins,
+                              level_draw=draws.get("level_draw"), init_done=self.init_done)
+        self.env_reset(**on_terrain, reset_buf=self.reset_buf, root_states=self.root_states, env_origins=self.env_origins, commands=self.commands,
                        dof_pos=self.dof_pos, dof_vel=self.dof_vel, default_dof_pos=self.default_dof_pos.reshape(-1), forces=self.forces,
                        motor_strengths=self.motor_strengths, Kp_factors=self.Kp_factors, Kd_factors=self.Kd_factors,
                        height_noise_offset=self.height_noise_offset, episode_sums=self.env_rewards.episode_sums, stumble=self.env_rewards.stumble,
@@ -241,8 +298,17 @@ class SurrogateLeggedEnv(VecEnv):
         """Reset every env, then one step with zero actions (base_task.py:115-119)."""
         self.reset_buf.fill_(1)
         self._reset_envs(draws or {})
+        self.init_done = True                                                            # the initial reset moved no level; later ones do
         obs, _, _, _, _ = self.step(torch.zeros(self.num_envs, self.num_actions, device=self.device), draws)
         return obs
+
+    def regenerate_terrain(self, seed: int):
+        """A new layout from `seed`, in place: the table every kernel holds is refilled, and the env origins follow the new
+        sub-terrain origins at the unchanged levels.  Robots stay where they are until their next reset."""
+        if self.terrain is None:
+            raise ValueError("SurrogateLeggedEnv.regenerate_terrain: the env has no config.terrain")
+        self.terrain.generate(seed)
+        self.env_origins.copy_(self.terrain_origins[self.terrain_levels, self.terrain_types])
 
     def get_observations(self):
         return self.obs_buf

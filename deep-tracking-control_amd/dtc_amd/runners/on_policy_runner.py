@@ -119,7 +119,11 @@ class OnPolicyRunner:
                 if tracker is not None:
                     tracker.step(rewards, dones)
                     if 'episode' in infos:
-                        ep_infos.append(infos['episode'])
+                        # an env may hand out views of device scalars it rewrites at every reset (the surrogate env does): keep the
+                        # values, as one stacked tensor per step (one launch when every entry is a device scalar)
+                        ep = infos['episode']
+                        vals = [torch.as_tensor(v, dtype=torch.float32, device=self.device) for v in ep.values()]
+                        ep_infos.append((tuple(ep), torch.stack([v if v.dim() == 0 else v.mean() for v in vals])))
             if self._plain:
                 self.alg.compute_returns(priv)
             else:
@@ -161,7 +165,7 @@ class OnPolicyRunner:
             if dpj and tracking:
                 losses, finished = self._job_means(losses, tracker)
             if logging:
-                self.log(it, last, losses, collection_time=t1 - t0, learn_time=t2 - t1, tracker=tracker, finished=finished)
+                self.log(it, last, losses, collection_time=t1 - t0, learn_time=t2 - t1, tracker=tracker, finished=finished, ep_infos=ep_infos)
                 if it % self.save_interval == 0:
                     self.save(os.path.join(self.log_dir, f'model_{it}.pt'))
             ep_infos.clear()
@@ -203,9 +207,11 @@ class OnPolicyRunner:
     def _contains_act(self):
         return bool(getattr(self.alg, "contain_nonfinite_act", False))
 
-    def log(self, it, last, losses, collection_time, learn_time, tracker, width=80, pad=35, finished=_LOCAL):
+    def log(self, it, last, losses, collection_time, learn_time, tracker, width=80, pad=35, finished=_LOCAL, ep_infos=None):
         """Writes and prints the scalars of iteration `it` and returns them.  `finished`: the (mean reward, mean episode length) to log
-        instead of the tracker's own (data parallel: the job's, _job_means); throughput counts the envs of every rank."""
+        instead of the tracker's own (data parallel: the job's, _job_means); throughput counts the envs of every rank.  `ep_infos`: one
+        (keys, stacked values) pair per step of the rollout, from extras["episode"]; the mean of every entry over the steps is logged as
+        'Episode/<key>', as the reference's runner does (on_policy_runner.py:171-182), with one host read for all of them."""
         value_loss, surrogate_loss, _adaptation, _decoder, recons_loss, vel_loss, kld_loss = tuple(losses) + (0.0,) * (7 - len(losses))
         steps = self.num_steps_per_env * self.env.num_envs * dp.world_size()
         self.tot_timesteps += steps
@@ -232,6 +238,10 @@ class OnPolicyRunner:
             # (step, env) pairs of the last rollout that act() repaired: zero actions, cleared live state (data parallel: the job's sum)
             job = getattr(self, "_job_nonfinite_act", None)
             scalars['Train/nonfinite_act'] = self.alg.last_nonfinite_act if job is None else job
+        if ep_infos:
+            keys = ep_infos[0][0]
+            for k, v in zip(keys, torch.stack([row for names, row in ep_infos if names == keys]).mean(dim=0).tolist()):
+                scalars['Episode/' + k] = v
         if self.writer is not None:
             for k, v in scalars.items():
                 self.writer.add_scalar(k, v, it)

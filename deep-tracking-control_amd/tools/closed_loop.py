@@ -5,6 +5,8 @@
     python deep-tracking-control_amd/tools/closed_loop.py --signal        # + the learning-signal run: 256 envs, 30 iterations
     python deep-tracking-control_amd/tools/closed_loop.py --tilt [--out profiles/closed_loop_tilt.txt]
                                                                           # the yaw-only env beside the tilt env (SimConfig.tilt), timing only
+    python deep-tracking-control_amd/tools/closed_loop.py --terrain [--out profiles/closed_loop_terrain.txt]
+                                                                          # the rough table beside the generated DTC terrain
 
 Per run and iteration: the mean step reward (mean of rew_buf over the iteration's 24 steps and all envs), the mean episode length
 (the runner's tracker: the last <= 100 finished episodes; "-" before the first one ends) and the mean length of the episodes in flight.
@@ -16,6 +18,10 @@ Timing, three interleaved rounds (default, one pass, default, ...), each figure 
     against the kernel to 1e-5 before it is timed), alternating, median of --calls windows each.
 With --tilt the two runs are the yaw-only env and the tilt env, both over the rough table `synthetic.reward_table()` (on the flat one
 the tilt stays level), default arithmetic: the same three interleaved rounds, and dtc_sim_step beside dtc_sim_step_tilt, alternating.
+With --terrain the two runs are the env over the rough table and the env on the generated DTC terrain (`SurrogateConfig.terrain`, the
+Lite3 grid), default arithmetic, the same three interleaved rounds; then dtc_terrain_generate at the Lite3 grid (6 x 2, 1760 x 1120
+cells) and at 10 x 20 beside the numpy restatement tests/terrain_oracle.py on the host, and, on a 6 x 9 grid that holds every family
+as one column, the mean terrain level and the share of envs reset per step per family over 200 steps of an untrained policy.
 """
 import argparse
 import os
@@ -32,6 +38,7 @@ from dtc_amd import sim as SIM, synthetic  # noqa: E402
 from dtc_amd.env import SurrogateConfig, SurrogateLeggedEnv  # noqa: E402
 from dtc_amd.runners import OnPolicyRunner  # noqa: E402
 from dtc_amd.runners.on_policy_runner import _EpisodeTracker  # noqa: E402
+from dtc_amd.terrain import FAMILIES, Terrain, TerrainConfig  # noqa: E402
 
 DEV = "cuda"
 STEPS = 24
@@ -42,11 +49,15 @@ def rough_env(num_envs, tilt):
     return SurrogateLeggedEnv(num_envs, DEV, SurrogateConfig(sim=SIM.SimConfig(tilt=tilt)), synthetic.reward_table(), seed=5)
 
 
-def make(num_envs, algo, seed=11, tilt=None):
-    """`tilt` None: the default env on the flat table; False / True: the yaw-only / the tilt env on the rough table."""
+def make(num_envs, algo, seed=11, tilt=None, terrain=None, steps=STEPS):
+    """`tilt` None: the default env on the flat table; False / True: the yaw-only / the tilt env on the rough table; `terrain`, a
+    TerrainConfig: the env on the generated terrain."""
     torch.manual_seed(seed)
-    env = SurrogateLeggedEnv(num_envs, DEV, SurrogateConfig(), seed=5) if tilt is None else rough_env(num_envs, tilt)
-    runner = dict(policy_class_name="ActorCriticDecoder", algorithm_class_name="PPO", num_steps_per_env=STEPS, save_interval=10 ** 9)
+    if terrain is not None:
+        env = SurrogateLeggedEnv(num_envs, DEV, SurrogateConfig(terrain=terrain), seed=5)
+    else:
+        env = SurrogateLeggedEnv(num_envs, DEV, SurrogateConfig(), seed=5) if tilt is None else rough_env(num_envs, tilt)
+    runner = dict(policy_class_name="ActorCriticDecoder", algorithm_class_name="PPO", num_steps_per_env=steps, save_interval=10 ** 9)
     return OnPolicyRunner(env, dict(runner=runner, algorithm=dict(algo), policy=dict()), log_dir=None, device=DEV), env
 
 
@@ -91,8 +102,8 @@ def timed(fn, acc):
     return f
 
 
-def timing_round(num_envs, iters, algo, tilt=None):
-    r, env = make(num_envs, algo, tilt=tilt)
+def timing_round(num_envs, iters, algo, tilt=None, terrain=None):
+    r, env = make(num_envs, algo, tilt=tilt, terrain=terrain)
     r.learn(2)                                                # warm-up: allocations, first launches
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -257,6 +268,86 @@ def tilt_report(args):
     return lines
 
 
+ALL_FAMILIES = (0.1, 0.1, 0.1, 0.1, 0.15, 0.15, 0.1, 0.1, 0.1)
+
+
+def generation_probe(cfg, calls):
+    """dtc_terrain_generate in place, us per call (host clock, closed by a synchronise; median), and the numpy restatement's seconds for one table."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(HERE)), "tests"))
+    import terrain_oracle as O
+    t = Terrain(cfg, DEV)
+    acc = []
+    for i in range(calls + 5):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        t.generate(seed=i)
+        torch.cuda.synchronize()
+        if i >= 5:
+            acc.append(1e6 * (time.perf_counter() - t0))
+    k = O.config(horizontal_scale=cfg.horizontal_scale, vertical_scale=cfg.vertical_scale, border_size=cfg.border_size,
+                 curriculum=cfg.curriculum, terrain_length=cfg.terrain_length, terrain_width=cfg.terrain_width, num_rows=cfg.num_rows,
+                 num_cols=cfg.num_cols, terrain_proportions=cfg.terrain_proportions, seed=calls + 4)
+    t0 = time.perf_counter()
+    want = O.generate(k)
+    host = time.perf_counter() - t0
+    same = bool((t.height_field_raw.cpu().numpy() == want["table"]).all())
+    return statistics.median(acc), host, same, (t.tot_rows, t.tot_cols)
+
+
+def family_probe(num_envs, steps=200, rollout=25):
+    """An untrained policy on a 6 x 9 grid whose column j is family j: per family the mean terrain level at the start and at the end
+    and the share of its envs reset per step.  Rollouts without updates; everything is summed on the device and read once."""
+    cfg = TerrainConfig(num_rows=6, num_cols=9, terrain_proportions=tuple([1 / 9] * 9), seed=1)
+    r, env = make(num_envs, {}, terrain=cfg, steps=rollout)
+    types = env.terrain_types
+    count = torch.bincount(types, minlength=9).double()
+    level0 = torch.zeros(9, dtype=torch.float64, device=DEV).index_add_(0, types, env.terrain_levels.double()) / count
+    resets = torch.zeros(9, dtype=torch.float64, device=DEV)
+    inner = r.env.step
+
+    def step(actions):
+        out = inner(actions)
+        resets.index_add_(0, types, out[2].double())
+        return out
+    object.__setattr__(r.env, "step", step)
+    state = dict(obs_dict=r.env.get_observations(), rew_buf=r.env.get_reward_buf())
+    for _ in range(steps // rollout):
+        r._collect(state, None, [])
+        r.alg.storage.clear()
+    level1 = torch.zeros(9, dtype=torch.float64, device=DEV).index_add_(0, types, env.terrain_levels.double()) / count
+    return level0.tolist(), level1.tolist(), (resets / count / (steps // rollout * rollout)).tolist(), count.tolist()
+
+
+def terrain_report(args):
+    lite3 = TerrainConfig(seed=1)
+    runs = (("rough table", dict(tilt=False)), ("terrain", dict(terrain=lite3)))
+    rounds = {tag: [] for tag, _ in runs}
+    for _ in range(3):
+        for tag, kw in runs:
+            rounds[tag].append(timing_round(args.envs, args.iters, {}, **kw))
+    lines = [f"closed loop on SurrogateLeggedEnv over the rough table beside SurrogateConfig(terrain=TerrainConfig()), the Lite3 grid: "
+             f"{args.envs} envs x {STEPS} steps per iteration, {args.iters} iterations, PPO, default arithmetic, fixed seeds",
+             "", "three interleaved rounds, median (min .. max):"]
+    for tag, _ in runs:
+        rs = rounds[tag]
+        lines.append(f"  {tag:11s} env-steps/s, whole loop {spread([r['steps_per_s'] for r in rs], '{:.0f}')}")
+        lines.append(f"  {'':11s} ms per iteration, each call closed by a synchronise: env.step x{STEPS} {spread([r['env_ms'] for r in rs], '{:.2f}')}"
+                     f" | act() x{STEPS} {spread([r['act_ms'] for r in rs], '{:.2f}')} | update() {spread([r['update_ms'] for r in rs], '{:.2f}')}")
+    lines += ["", "dtc_terrain_generate in place, us per call (host clock, closed by a synchronise), three rounds; the numpy restatement "
+              "(tests/terrain_oracle.py) on the host, ms:"]
+    for tag, cfg in (("Lite3 6 x 2", lite3), ("10 x 20", TerrainConfig(num_rows=10, num_cols=20, terrain_proportions=ALL_FAMILIES, seed=1))):
+        probes = [generation_probe(cfg, args.calls) for _ in range(3)]
+        rows, cols = probes[0][3]
+        lines.append(f"  {tag:11s} {rows} x {cols} cells: kernel {spread([p[0] for p in probes])} us | numpy {spread([1e3 * p[1] for p in probes])} ms"
+                     f" | tables equal: {all(p[2] for p in probes)}")
+    level0, level1, share, count = family_probe(args.envs)
+    lines += ["", f"an untrained policy, {args.envs} envs on a 6 x 9 grid (column j = family j, max_init_terrain_level 5), 200 steps, no update:",
+              "  family              envs   mean terrain_level start -> end   envs reset per step"]
+    for j, name in enumerate(FAMILIES):
+        lines.append(f"  {name:19s} {int(count[j]):5d}   {level0[j]:.3f} -> {level1[j]:.3f}                     {100 * share[j]:.2f} %")
+    return lines
+
+
 def spread(vals, fmt="{:.1f}"):
     return f"{fmt.format(statistics.median(vals))} ({fmt.format(min(vals))} .. {fmt.format(max(vals))})"
 
@@ -268,10 +359,11 @@ def main():
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--signal", action="store_true")
     ap.add_argument("--tilt", action="store_true")
+    ap.add_argument("--terrain", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if args.tilt:
-        text = "\n".join(tilt_report(args)) + "\n"
+    if args.tilt or args.terrain:
+        text = "\n".join((tilt_report if args.tilt else terrain_report)(args)) + "\n"
         print(text)
         if args.out:
             with open(args.out, "w") as f:

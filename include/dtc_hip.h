@@ -42,7 +42,7 @@ extern "C" {
 #define DTC_ACT_SIGMOID 6
 
 /* library / device info ------------------------------------------------------------------ */
-#define DTC_ABI_VERSION 23                  /* bumped whenever a signature or a by-value struct layout changes       */
+#define DTC_ABI_VERSION 24                  /* bumped whenever a signature or a by-value struct layout changes       */
 int dtc_version(void);                       /* == DTC_ABI_VERSION of the build; the host binding refuses a mismatch   */
 /* sizeof() of the structs that cross the boundary, in the order DtcGridCfg, DtcObsCfg, DtcRowCopy, DtcSeg, DtcSegMat,
    DtcFwdLayer, DtcWgradJob, DtcPpoCfg, DtcProfRec, DtcWimgJob, DtcH2iWJob, DtcH2iOperand, DtcWgradH2iJob, DtcEnvStep, DtcH2iFwdLayer, DtcH2iDgradLayer, DtcGruFwdItem, DtcGruBwdItem: the binding compares them with its own layouts at load time (a library
@@ -524,6 +524,75 @@ typedef struct DtcSimTilt {
 /* sizeof() of DtcSimTilt, in a table of its own (dtc_sim_abi_sizes keeps its 2 entries). */
 int dtc_sim_tilt_abi_sizes(int64_t* out, int cap);
 int dtc_sim_step_tilt(const DtcSimStep* st, const DtcSimCfg* cfg, const DtcSimTilt* tilt, int N, void* stream);
+
+/* ---- DTC curriculum terrain, generated on the device (opt-in) ------------------------------
+ * dtc_terrain_generate (csrc/terrain.hip) fills the int16 height table [tot_rows, tot_cols] (border included: zeros) and
+ * terrain_origins [R, C, 3] fp32 from one seed, as ONE launch: the first blocks write the table, the last R * C blocks the origins
+ * (each recomputes its sub-terrain's central window; the table is not read back).  No second launch, no atomics, nothing outside the
+ * two outputs is written.  tests/terrain_oracle.py restates everything below in numpy and is the specification; the kernel equals it
+ * bit for bit.
+ *
+ * The reference's (legged_gym/utils/terrain.py): the layout, the choice of a family, the parameters, the origins, and families 6 (gap)
+ * and 7 (pit) cell for cell.  This project's: the cells of families 0..5 and 8.  The reference takes those from isaacgym.terrain_utils
+ * and from Python loops over numpy's random stream; here they are pure functions of (cfg, seed, i, j, cell) with the reference's
+ * parameters -- not its random sequence, and not isaacgym's code.
+ *
+ * Arithmetic: parameters are IEEE doubles in the order written (-ffp-contract=off), as the reference's Python floats, so every
+ * int(x / scale) below is the reference's (int() truncates toward zero); cells are integers; `//` is Python's floor division.
+ * Geometry (terrain.py:20-30), hs = horizontal_scale, vs = vertical_scale, R = num_rows, C = num_cols:
+ *   S = int(terrain_length / hs) cells per sub-terrain side (terrain_length == terrain_width, else DTC_ERR_ARG; at least 2 m);
+ *   border = int(border_size / hs);  tot_rows = R * S + 2 * border;  tot_cols = C * S + 2 * border (< 2^31 cells, else DTC_ERR_ARG);
+ *   sub-terrain (i, j) occupies rows border + i * S .., columns border + j * S ..; (a, b) is a cell inside it.
+ * Origins (terrain.py:143-160): x = (i + 0.5) * terrain_length;  y = (j + 0.5) * terrain_width;  z = the maximum of the cells
+ *   [x1, x2) x [x1, x2), x1 = int((terrain_length / 2 - 1) / hs), x2 = min(int((terrain_length / 2 + 1) / hs), S), times vs; each a
+ *   double rounded once to fp32.
+ * Draws: Philox4x32-10, key = (seed low, seed high), counter = (item, sub-terrain index i * C + j, purpose, 0x74657272), so no two
+ *   draws share a counter; words x, y, z, w;  below(word, n) = (word * n) >> 32 in 64 bits.  Purposes: 0 layout (item 0), 1 noise node
+ *   (item na * W + nb), 2 rectangle (item r), 3 stepping-stone row shift (item b // p), 4 stones-everywhere row shift (item b // p),
+ *   5 stones-everywhere stone (item (b // p) * 65536 + (a + shift) // p).
+ * Family and difficulty (terrain.py:45-62): curriculum: difficulty = i / R, choice = j / C + 0.001; else choice = x * 2^-32 and
+ *   difficulty = {0.25, 0.5, 0.75, 0.9}[y >> 30] of the layout draw.  `proportions` are the CUMULATIVE sums of terrain_proportions as
+ *   Terrain.__init__ takes them, padded to nine entries with 2.0.  make_terrain (terrain.py:79-141, the "lite3" values):
+ *   slope = difficulty * 0.4;  stepping_stones_size = 1.05 - difficulty;  step_height = 0.05 + 0.13 * difficulty;
+ *   discrete_obstacles_height = 0.05 + difficulty * 0.15;  stone_distance = difficulty == 0 ? 0.03 : 0.06;
+ *   max_height = 0.02 + 0.03 * difficulty;  stone_size = -0.1 * difficulty + 0.3;  gap_size = pit_depth = 0.8 * difficulty;
+ *   choice < p[0]: family 0 (slope negated when choice < p[0] / 2);  < p[1]: 1;  < p[3]: stairs, 2 (step_height negated) when
+ *   choice < p[2], else 3;  < p[4]: 4;  < p[5]: 5;  < p[6]: 6;  < p[7]: 7;  else 8.
+ * Cells, in units of vs (clamped to int16 at the end).  e = min(a, S - 1 - a, b, S - 1 - b);  e_max = max((S - int(3 / hs)) // 2, 0);
+ * platform(size): P = int(size / hs);  the square [(S - P) // 2, (S + P) // 2) in a and b (P >= S: the whole sub-terrain).
+ *   0 smooth slope:  rint(((slope * hs) * min(e, e_max)) / vs)                      (a pyramid; its flat top is the 3 m platform)
+ *   1 rough slope:   family 0 plus lattice noise: g = max(int(0.2 / hs), 1), W = S // g + 2, node (na, nb) carries
+ *                    n = ((below(x, 21) - 10) * 0.005) / vs;  with na = a // g, nb = b // g, fa = a % g, fb = b % g:
+ *                    t = (((g - fa) * (g - fb)) * n[na][nb] + (fa * (g - fb)) * n[na + 1][nb]) +
+ *                        (((g - fa) * fb) * n[na][nb + 1] + (fa * fb) * n[na + 1][nb + 1]);   noise = rint(t / (g * g))
+ *   2 / 3 stairs:    (min(e, e_max) // max(int(0.31 / hs), 1)) * int(step_height / vs)
+ *   4 discrete:      20 rectangles r: la = min(int(1 / hs) + below(x, int(2 / hs) - int(1 / hs) + 1), S), lb likewise from y,
+ *                    pa = below(z, S - la + 1), pb = below(w, S - lb + 1);  full = int(discrete_obstacles_height / vs);
+ *                    mag = y & 1 ? full : full // 2;  value = x & 1 ? -mag : mag;  the highest r whose rectangle
+ *                    [pa, pa + la) x [pb, pb + lb) holds the cell gives its value, no rectangle: 0;  platform(3): 0
+ *   5 stepping:      s = int(stepping_stones_size / hs);  p = max(s + int(stone_distance / hs), 1);  shift = below(x, p) of row b // p;
+ *                    stone when s >= S, or s >= 1 and b % p < s and (a + shift) % p < s: 0;  else int(-2 / vs);  platform(1): 0
+ *   6 gap:           gap_terrain (terrain.py:162-173), its two slice assignments with Python's slice rules (a negative start counts
+ *                    from the end): -1000 in the outer square, 0 in the inner
+ *   7 pit:           pit_terrain (terrain.py:175-182): -int(pit_depth / vs) in the square S // 2 -+ int(1 / hs / 2)
+ *   8 stones:        m = int(stone_size / hs);  p = max(m + int(stone_distance / hs), 1);  shift as in 5 (purpose 4);  t = a + shift;
+ *                    the stone (b // p, t // p) has sa = m - 1 + below(x, 2), sb = m - 1 + below(y, 2) and height
+ *                    1 + below(z, 2 * int(max_height / vs)) (0 when int(max_height / vs) < 1);  b % p < sb and t % p < sa: that height;
+ *                    else int(-2 / vs);  platform(1.3): 0
+ * `cfg` is a HOST pointer; height_samples (2-byte aligned) and terrain_origins are DEVICE pointers of tot_rows * tot_cols int16 and
+ * R * C * 3 floats.  A bad argument returns DTC_ERR_ARG before any launch. */
+typedef struct DtcTerrainCfg {
+    double horizontal_scale, vertical_scale, border_size, terrain_length, terrain_width;      /* [m]                     */
+    double proportions[9];           /* cumulative terrain_proportions, padded with 2.0                                   */
+    int32_t num_rows, num_cols;      /* R (levels), C (types)                                                             */
+    int32_t curriculum;              /* 1: curiculum(), 0: randomized_terrain()                                           */
+    int32_t tot_rows, tot_cols;      /* the table as the caller allocated it: must equal the geometry above               */
+    int32_t reserved;                /* 0                                                                                 */
+    uint64_t seed;
+} DtcTerrainCfg;
+/* sizeof() of DtcTerrainCfg, in a table of its own (the other tables keep their lengths). */
+int dtc_terrain_abi_sizes(int64_t* out, int cap);
+int dtc_terrain_generate(const DtcTerrainCfg* cfg, int16_t* height_samples, float* terrain_origins, void* stream);
 
 /* ---- rollout-side store (row f2) ---------------------------------------------------------
  * RolloutStorage.add_transitions, rsl_rl/rsl_rl/storage/rollout_storage.py:99-116: the 13 `copy_` of one env step as
