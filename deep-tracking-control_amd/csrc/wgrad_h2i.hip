@@ -25,13 +25,14 @@
 // This is the price of one fp16 multiply per fragment; a wider range for f is a performance trade left open.
 // Per wave and stage: 4 LDS-DMA pieces, 16 transpose reads, 2 table reads, 16 v_pk_mul_f16, 12 MFMAs.
 // The stage loop is unrolled over three 128-row blocks (24 stages: the period of (position in the block, stage buffer)).
-// Partial slabs [batch slice][tile][128][128]; wgrad_h2i_reduce_kernel sums the slices in a fixed order.
+// Partial slabs [batch slice][tile][128][128]; wgrad_h2i_reduce_kernel sums the slices in a fixed order.  The slice rule, the index
+// maps, the slab sum and the host plan are shared with the other weight-gradient families: csrc/wgrad_plan.hpp.
 #include "h2i_core.hpp"
+#include "wgrad_plan.hpp"
 
 namespace {
 
 constexpr int TILE = 128;
-constexpr int MAX_JOBS_H = 12;
 // How far a block may raise the accumulators' scale above the smallest scale a block of the same batch slice has had.  A row of block
 // b adds at most three products |hi hi'| <= 2^30 f, f <= 1, to accumulators held at scale T_b; at a later scale T_c they are therefore
 // below rows x 2^30.01 x 2^(T_c - min_b T_b).  A slice holds at most 2^22 rows: an image is below 2 GiB and a row takes at least 64
@@ -68,7 +69,7 @@ struct HJob {
 };
 struct HGroup {
     int count, M, mtiles, rows_per_split, splits, tiles_total;
-    HJob job[MAX_JOBS_H];
+    HJob job[WGRAD_MAX_JOBS];
 };
 
 // PASSES = 3: lo hi' + hi lo' + hi hi' per product (the default); PASSES = 1 (opt-in, dtc_set_h2i_passes): plane 0 of both operands alone
@@ -91,15 +92,12 @@ __device__ __forceinline__ void wgrad_h2i_group_body(const HGroup& G) {
     __shared__ int Tred[4][2];
 #define AS(b) ((b) == 0 ? A0 : (b) == 1 ? A1 : A2)
 #define BS(b) ((b) == 0 ? B0 : (b) == 1 ? B1 : B2)
-    const int xcd = blockIdx.x & 7, jb = blockIdx.x >> 3;
-    const int split = xcd + 8 * (jb / G.tiles_total);
-    if (split >= G.splits) return;
-    int t = jb % G.tiles_total;
-    int j = 0;
-    while (j < G.count - 1 && t >= G.job[j].tile_end) ++j;
-    const int tiles_j = G.job[j].tile_end - (j > 0 ? G.job[j - 1].tile_end : 0);
-    if (j > 0) t -= G.job[j - 1].tile_end;
-    const HJob& J = G.job[j];
+    int split, t;
+    if (!slice_tile(G.tiles_total, G.splits, split, t)) return;
+    const JobPos jp = tile_job(G, t);
+    const int tiles_j = job_tiles(G, jp.j);
+    t = jp.t;
+    const HJob& J = G.job[jp.j];
     const int tr = t / J.col_tiles, tc = t - tr * J.col_tiles;
     const int m_begin = split * G.rows_per_split;                    // multiples of 128: a slice is a whole number of exponent blocks
     const int m_end = min(G.mtiles * 128, m_begin + G.rows_per_split);
@@ -116,12 +114,9 @@ __device__ __forceinline__ void wgrad_h2i_group_body(const HGroup& G) {
     const u32 aoff = sa < J.st_n ? (u32)sa * (u32)HI_CHUNK + slot : INVALID;  // columns behind the matrix: zeros land
     const u32 boff = sb < J.st_k ? (u32)sb * (u32)HI_CHUNK + slot : INVALID;
     const rsrc_t ares = make_rsrc_bytes(J.dZ, J.dz_bytes), bres = make_rsrc_bytes(J.X, J.x_bytes);
-    auto load_stage = [&](auto nbc, int mb) {
+    // one stage of both operands -> stage buffer nbc: ua / ub = byte offset of its 16 batch rows in the two images, dead = INVALID: zeros land
+    auto load_at = [&](auto nbc, u32 ua, u32 ub, u32 dead) {
         constexpr int nbuf = decltype(nbc)::value;
-        // batch rows mb .. mb + 15 sit in row tile mb >> 7 at local rows (mb & 127) ..; rows >= m_end: nothing valid -> zeros
-        const u32 ua = (u32)((mb >> 7) * J.st_n) * (u32)HI_CHUNK + (u32)(mb & 127) * 32u;
-        const u32 ub = (u32)((mb >> 7) * J.st_k) * (u32)HI_CHUNK + (u32)(mb & 127) * 32u;
-        const u32 dead = oob_mask(mb + mrow, m_live - 1);
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
             __builtin_amdgcn_raw_ptr_buffer_load_lds(ares, (lds_void*)&AS(nbuf)[p][wave * 1024], 16, aoff | dead, ua + p * HI_PLANE, 0, 0);
@@ -208,8 +203,10 @@ __device__ __forceinline__ void wgrad_h2i_group_body(const HGroup& G) {
     int t_cur = 0, tz_cur = 0;                                     // scale of the accumulators (T, Tz of the block in flight)
     if (KT > 0) {
         table_request(m_begin);
-        load_stage(S0{}, m_begin);
-        load_stage(S1{}, m_begin + BK);
+        // batch rows mb .. mb + 15 sit in row tile mb >> 7 at local rows (mb & 127) ..; rows >= m_live: nothing valid -> zeros
+        const u32 ua = (u32)((m_begin >> 7) * J.st_n) * (u32)HI_CHUNK, ub = (u32)((m_begin >> 7) * J.st_k) * (u32)HI_CHUNK;
+        load_at(S0{}, ua, ub, oob_mask(m_begin + mrow, m_live - 1));
+        load_at(S1{}, ua + BK * 32u, ub + BK * 32u, oob_mask(m_begin + BK + mrow, m_live - 1));
         table_minima();
         __syncthreads();
         table_finish(0, 0, 0);
@@ -229,14 +226,6 @@ __device__ __forceinline__ void wgrad_h2i_group_body(const HGroup& G) {
     // wave's transfers reach LDS in the order they were issued; the stage waits count them in that order, so a stage with twice the
     // transfers only waits longer).  A whole block's stage is the stage it was plus one scalar test and one branch that is not taken.
     auto tail_dead = [&](int row, int lim) { return oob_mask(mrow + row, lim - 1); };
-    auto load_at = [&](auto nbc, u32 ua, u32 ub, u32 dead) {
-        constexpr int nbuf = decltype(nbc)::value;
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(ares, (lds_void*)&AS(nbuf)[p][wave * 1024], 16, aoff | dead, ua + p * HI_PLANE, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(bres, (lds_void*)&BS(nbuf)[p][wave * 1024], 16, boff | dead, ub + p * HI_PLANE, 0, 0);
-        }
-    };
     struct Blk {
         int kt0, which;
         bool more;
@@ -434,80 +423,27 @@ __global__ __launch_bounds__(256) void wgrad_h2i_reduce_kernel(const HGroup G) {
         }
         return;
     }
-    int t = b >> 4;
-    const int rg = b & 15;
-    int j = 0;
-    while (j < G.count - 1 && t >= G.job[j].tile_end) ++j;
-    const int tiles_j = G.job[j].tile_end - (j > 0 ? G.job[j - 1].tile_end : 0);
-    if (j > 0) t -= G.job[j - 1].tile_end;
-    const HJob& J = G.job[j];
-    const int tr = t / J.col_tiles, tc = t - tr * J.col_tiles;
-    const int rl = rg * 8 + (threadIdx.x >> 5), c4 = threadIdx.x & 31;
-    const int n = tr * TILE + rl;
-    if (n >= J.N) return;
-    const f32x4* p = reinterpret_cast<const f32x4*>(J.part + (long long)t * (TILE * TILE) + (long long)rl * TILE) + c4;
-    const long long step = (long long)tiles_j * (TILE * TILE / 4);
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    int sp = 0;
-    for (; sp + 7 < G.splits; sp += 8) {               // eight slabs in flight per thread; the order of the additions is fixed
-        f32x4 v[8];
+    // eight slabs in flight per thread
+    reduce_slab_rows<8>(G, b, [](int r) { return r; }, [](const HJob& J, int n, int tc, int c4, const f32x4& sum) {
+        const int k = tc * TILE + 4 * c4;
+        float* dst = J.dW + (long long)n * J.ldw + k;
+        if (k + 4 <= J.K && (reinterpret_cast<unsigned long long>(dst) & 15ull) == 0) {
+            *reinterpret_cast<f32x4*>(dst) = sum;
+        } else {
 #pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = p[(long long)(sp + u) * step];
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[e] += v[u][e];
-    }
-    for (; sp < G.splits; ++sp) {
-        const f32x4 v0 = p[(long long)sp * step];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] += v0[e];
-    }
-    const int k = tc * TILE + 4 * c4;
-    float* dst = J.dW + (long long)n * J.ldw + k;
-    if (k + 4 <= J.K && (reinterpret_cast<unsigned long long>(dst) & 15ull) == 0) {
-        *reinterpret_cast<f32x4*>(dst) = acc;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (k + e < J.K) dst[e] = acc[e];
-    }
+            for (int e = 0; e < 4; ++e)
+                if (k + e < J.K) dst[e] = sum[e];
+        }
+    });
 }
 
-struct HPlan {
-    HGroup dev;
-    long long bytes;
-    int red_blocks;
-    double flop, algo_bytes;
-};
-
-int h2i_splits(int M, int tiles_total) {
-    // 768 (round 5; 8 batch slices for the 61..70-tile buckets of the bench step): with both operands arriving by LDS-DMA the slices need
-    // not be short to hide their loads -- 1024 / 1536 / 2048 workgroups: 50.3 / 50.1 / 50.2 ms per step on one box, 512 / 768 / 1024: 46.67 /
-    // 46.70 / 46.94 on another (interleaved pairs; round 4's converting kernel wanted 1536) -- and a third of the partial slabs is a third
-    // of the reduce traffic (again on round 6's kernel: 8 / 16 / 24 slices 46.3 / 46.8 / 47.2 ms per step, three interleaved rounds)
-    constexpr int target = 768, cap = 24;
-    int s = target / (tiles_total > 0 ? tiles_total : 1) / 8 * 8;
-    if (s < 8) s = 8;
-    if (s > cap) s = cap;
-    const int max_s = (int)dtc::ceil_div(dtc::ceil_div(M, 128), 8) * 8;     // a slice holds at least one 128-row block
-    if (s > max_s) s = max_s;
-    return s;
-}
+using HPlan = WgradPlan<HGroup>;
 
 int plan_h2i(const DtcWgradH2iJob* jobs, int count, int M, void* workspace, HPlan& P) {
-    DTC_REQUIRE(jobs != nullptr && count >= 1 && count <= MAX_JOBS_H, "job count %d outside 1..%d", count, MAX_JOBS_H);
-    DTC_REQUIRE(M > 0, "bad M=%d", M);
-    HGroup& G = P.dev;
-    G.count = count;
-    G.M = M;
-    G.mtiles = (int)hi_rtiles(M);
-    int tiles = 0, row_tiles = 0;
-    for (int j = 0; j < count; ++j) {
-        const DtcWgradH2iJob& h = jobs[j];
+    int row_tiles = 0;
+    int rc = plan_jobs(P.dev, jobs, count, M, SLICES_H2I, 128, [&](int j, const DtcWgradH2iJob& h, HJob& d, int& tiles) -> int {
         DTC_REQUIRE(h.N > 0 && h.K > 0 && h.dZimg && h.Ximg && h.dW && dtc::aligned16(h.dZimg) && dtc::aligned16(h.Ximg), "job %d: bad shape / null or unaligned pointer", j);
         DTC_REQUIRE(h.ldw >= h.K + h.wcol0 && h.wcol0 >= 0, "job %d: columns [%d, %d) outside the %lld-wide gradient", j, h.wcol0, h.wcol0 + h.K, (long long)h.ldw);
-        HJob& d = G.job[j];
         d.dZ = (const u32x4*)h.dZimg;
         d.X = (const u32x4*)h.Ximg;
         d.st_n = (int)hi_stages(h.N);
@@ -526,27 +462,18 @@ int plan_h2i(const DtcWgradH2iJob* jobs, int count, int M, void* workspace, HPla
         d.K = h.K;
         d.col_tiles = (int)dtc::ceil_div(h.K, TILE);
         d.row_tiles = (int)dtc::ceil_div(h.N, TILE);
-        tiles += d.row_tiles * d.col_tiles;
+        tiles = d.row_tiles * d.col_tiles;
         row_tiles += d.row_tiles;
-        d.tile_end = tiles;
-    }
-    G.tiles_total = tiles;
-    G.splits = h2i_splits(M, tiles);
-    G.rows_per_split = (int)dtc::ceil_div(dtc::ceil_div(M, G.splits), 128) * 128;
-    long long off = 0;
-    P.flop = P.algo_bytes = 0.0;
-    for (int j = 0; j < count; ++j) {
-        HJob& d = G.job[j];
-        const long long tiles_j = d.tile_end - (j > 0 ? G.job[j - 1].tile_end : 0);
-        d.part = workspace ? (float*)((char*)workspace + off) : nullptr;
-        off += (long long)G.splits * tiles_j * TILE * TILE * (long long)sizeof(float);
-        d.bpart = workspace ? (float*)((char*)workspace + off) : nullptr;
-        off += (long long)G.splits * d.col_tiles * d.row_tiles * TILE * (long long)sizeof(float);
-        P.flop += 2.0 * M * (double)d.N * d.K;
-        P.algo_bytes += 4.0 * ((double)M * d.N + (double)M * d.K) + 4.0 * (double)d.N * (d.K + 1);
-    }
-    P.bytes = off;
-    P.red_blocks = tiles * 16 + 4 * row_tiles;
+        return DTC_OK;
+    });
+    if (rc != DTC_OK) return rc;
+    P.dev.mtiles = (int)hi_rtiles(M);
+    const long long splits = P.dev.splits;
+    P.bytes = plan_slabs(P, workspace, [&](HJob& d, int tiles_j, auto take) {
+        d.part = take(splits * tiles_j * TILE * TILE * (long long)sizeof(float));
+        d.bpart = take(splits * d.col_tiles * d.row_tiles * TILE * (long long)sizeof(float));
+    });
+    P.red_blocks = P.dev.tiles_total * 16 + 4 * row_tiles;
     return DTC_OK;
 }
 
@@ -565,15 +492,10 @@ extern "C" int dtc_wgrad_group_h2i(const DtcWgradH2iJob* jobs, int count, int M,
     if (rc != DTC_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const HGroup& G = P.dev;
-    {
-        dtc::ProfScope prof(dtc::prof_shape_name("linear_wgrad", M, G.tiles_total, count), P.flop, s, P.algo_bytes);
-        const dim3 grid(G.tiles_total * 8 * (int)dtc::ceil_div(G.splits, 8));
-        if (dtc_get_h2i_passes() == 1) hipLaunchKernelGGL(wgrad_h2i_onepass_group_kernel, grid, dim3(256), 0, s, G);
-        else hipLaunchKernelGGL(wgrad_h2i_group_kernel, grid, dim3(256), 0, s, G);
-    }
-    {
-        dtc::ProfScope prof(dtc::prof_shape_name("wgrad_reduce", G.splits, G.tiles_total, count), (double)P.bytes + P.bytes / (double)G.splits, s);
-        hipLaunchKernelGGL(wgrad_h2i_reduce_kernel, dim3(P.red_blocks), dim3(256), 0, s, G);
-    }
-    return dtc::check_launch("wgrad_group_h2i");
+    return wgrad_launch_pair(P, s, "wgrad_group_h2i",
+        [&](int grid) {
+            if (dtc_get_h2i_passes() == 1) hipLaunchKernelGGL(wgrad_h2i_onepass_group_kernel, dim3(grid), dim3(256), 0, s, G);
+            else hipLaunchKernelGGL(wgrad_h2i_group_kernel, dim3(grid), dim3(256), 0, s, G);
+        },
+        [&] { hipLaunchKernelGGL(wgrad_h2i_reduce_kernel, dim3(P.red_blocks), dim3(256), 0, s, G); });
 }

@@ -13,15 +13,15 @@
 //     to is only a matter of addressing: the partial slabs are written in physical order (coalesced float4 rows) and the
 //     reduce kernel maps them back while it sums the batch slices in a fixed order (deterministic, no atomics).
 // Tiles: 128 (n) x 128 (c, inside ONE segment of X), 2 x 2 waves of 64 x 64, stage = 16 batch rows, double-buffered LDS
-// (48 KiB); grouped launch over all layers of a gradient bucket and 8 k batch slices (slice s runs on XCD s % 8), as
-// csrc/wgrad.hip does for the single-pass kernels.
+// (48 KiB); grouped launch over all layers of a gradient bucket and 8 k batch slices (slice s runs on XCD s % 8).  The slice rule, the
+// index maps, the slab sum and the host plan are shared with the other weight-gradient families: csrc/wgrad_plan.hpp.
 #include <type_traits>
 
 #include "s3_core.hpp"
+#include "wgrad_plan.hpp"
 
 namespace {
 
-constexpr int MAX_JOBS_S3 = 12;
 constexpr int TILE = 128;
 
 struct S3Job {
@@ -40,8 +40,7 @@ struct S3Job {
 };
 struct S3Group {
     int count, M, rows_per_split, splits, tiles_total;
-    int per_xcd;            // > 0: balanced map -- the (slice, tile) items in slice-major order, cut into 8 equal runs, one per XCD
-    S3Job job[MAX_JOBS_S3];
+    S3Job job[WGRAD_MAX_JOBS];
 };
 
 __device__ __forceinline__ int phys(int x) { return (x & 3) * 32 + (x >> 2); }          // logical -> physical (0..127)
@@ -53,38 +52,19 @@ __device__ __forceinline__ int logical(int p) { return 4 * (p & 31) + (p >> 5); 
 // bench step's grouped launches ran 318 instead of 270 us).  The row-map variant keeps 180 registers (budget 3 would spill one)
 // H2 (round 4): operands as two fp16 terms, three MFMA passes per 16 batch rows (s3_core.hpp) instead of three bf16 terms and six
 template <bool GATHER_A, bool H2 = false>
-#ifndef DTC_WGRAD_H2_WG
-#define DTC_WGRAD_H2_WG 2
-#endif
-__global__ __launch_bounds__(256, H2 ? DTC_WGRAD_H2_WG : 2) void wgrad_s3_group_kernel(const S3Group G) {
+__global__ __launch_bounds__(256, 2) void wgrad_s3_group_kernel(const S3Group G) {
     using P = Prec<H2>;
     constexpr int NP = P::NP, NT = P::NT;
     __shared__ __attribute__((aligned(16))) u32x2 As[2][3][TILE * 4];          // (three planes either way: the epilogue's patches need the 48 KiB)
     __shared__ __attribute__((aligned(16))) u32x2 Bs[2][3][TILE * 4];
-    const int xcd = blockIdx.x & 7, jb = blockIdx.x >> 3;
     int split, t;
-    if (G.per_xcd > 0) {                               // any slice count: every XCD gets the same number of workgroups
-        const int q = xcd * G.per_xcd + jb;
-        if (q >= G.splits * G.tiles_total) return;
-        split = q / G.tiles_total;
-        t = q - split * G.tiles_total;
-    } else {
-        split = xcd + 8 * (jb / G.tiles_total);
-        if (split >= G.splits) return;
-        t = jb % G.tiles_total;
-    }
-    int j = 0;
-    while (j < G.count - 1 && t >= G.job[j].tile_end) ++j;
-    if (j > 0) t -= G.job[j - 1].tile_end;
-    const S3Job& J = G.job[j];
+    if (!slice_tile(G.tiles_total, G.splits, split, t)) return;
+    const JobPos jp = tile_job(G, t);
+    t = jp.t;
+    const S3Job& J = G.job[jp.j];
     const int tr = t / J.col_tiles;
-    int tc = t - tr * J.col_tiles;
-    int seg = 0;
-    for (; seg < J.X.nseg - 1; ++seg) {
-        const int nt = (J.X.s[seg].width + TILE - 1) / TILE;
-        if (tc < nt) break;
-        tc -= nt;
-    }
+    const SegTile st = seg_tile(J.X, t - tr * J.col_tiles, TILE);
+    const int seg = st.seg, tc = st.tc;
     const SegDev sd = J.X.s[seg];
     const int N = J.N, M = G.M;
     const int n0 = tr * TILE, lc0 = tc * TILE;
@@ -125,14 +105,7 @@ __global__ __launch_bounds__(256, H2 ? DTC_WGRAD_H2_WG : 2) void wgrad_s3_group_
     }
     const int e_mine = is_a ? ez : exx;
 
-    // AHW (fp16 kernels, round 4; -DDTC_H2_WGRAD_AHEAD2=1, OFF): the operand loads TWO stages ahead of the MFMAs (two register sets, set =
-    // parity of the stage), as linear_s3_kernel<.., H2> has them.  Here both operands travel through registers: 180 instead of 152
-    // registers = two instead of three workgroups per CU, 59.4 vs 54.5 ms per step; squeezed into three (-DDTC_WGRAD_H2_WG=3): 58.8 vs 57.3.
-#ifndef DTC_H2_WGRAD_AHEAD2
-#define DTC_H2_WGRAD_AHEAD2 0
-#endif
-    constexpr bool AHW = H2 && !GATHER_A && (DTC_H2_WGRAD_AHEAD2 != 0);
-    f32x4 vs[AHW ? 2 : 1][4];
+    f32x4 v[4];
     float bsum[4] = {0.f, 0.f, 0.f, 0.f};
     u32 rnext[4];
     auto rows_of = [&](int mb) {                       // source rows of X for the stage starting at batch row mb
@@ -144,8 +117,7 @@ __global__ __launch_bounds__(256, H2 ? DTC_WGRAD_H2_WG : 2) void wgrad_s3_group_
         }
     };
     if (GATHER_A || !is_a) rows_of(m_begin);
-    auto load_stage = [&](int mb, auto setc) {
-        f32x4(&v)[4] = vs[AHW ? decltype(setc)::value : 0];
+    auto load_stage = [&](int mb) {
         if (is_a) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -163,8 +135,7 @@ __global__ __launch_bounds__(256, H2 ? DTC_WGRAD_H2_WG : 2) void wgrad_s3_group_
     };
     // BIAS (workgroup-uniform): the first column tile of a layer also sums dZ's columns (12 of the ~100 VALU of a stage that the
     // other tiles, and the X side everywhere, do not need to issue)
-    auto store_stage = [&](int buf, auto bias, auto setc) {
-        f32x4(&v)[4] = vs[AHW ? decltype(setc)::value : 0];
+    auto store_stage = [&](int buf, auto bias) {
         u32x2(*dst)[TILE * 4] = is_a ? As[buf] : Bs[buf];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -206,8 +177,7 @@ __global__ __launch_bounds__(256, H2 ? DTC_WGRAD_H2_WG : 2) void wgrad_s3_group_
 
     // fused stage: the MFMAs of LDS[buf] with the conversion + LDS store of the loaded block (-> LDS[buf ^ 1]) placed between the
     // MFMAs of the second column tile, one column of the block per three MFMAs (see linear_s3_kernel)
-    auto stage_ilv = [&](int buf, auto bias, auto setc) {        // setc: the register set that is converted (-> LDS[buf ^ 1])
-        f32x4(&v)[4] = vs[AHW ? decltype(setc)::value : 0];
+    auto stage_ilv = [&](int buf, auto bias) {
         u32x4 a[2][NP], b[NP];
 #pragma unroll
         for (int p = 0; p < NP; ++p)
@@ -242,43 +212,13 @@ __global__ __launch_bounds__(256, H2 ? DTC_WGRAD_H2_WG : 2) void wgrad_s3_group_
 
     const int KT = (m_end - m_begin + BK - 1) / BK;
     auto k_loop = [&](auto bias) {
-        if constexpr (AHW) {
-            // stage kt lives in register set kt & 1 and goes to LDS[kt & 1]; half step HS<P>(kt), P = kt & 1: the loads of stage kt + 1
-            // are issued (into the set stage kt - 1 was converted from), LDS[P ^ 1] (stage kt - 1) feeds the MFMAs, set P (stage kt,
-            // loaded one half step earlier) is converted into LDS[P].  Loads past the slice read masked rows: zeros, never stored.
-            load_stage(m_begin, S0{});
-            store_stage(0, bias, S0{});
-            load_stage(m_begin + BK, S1{});
-            __syncthreads();
-            int kt = 1;
-            for (; kt + 1 < KT; kt += 2) {                   // kt is odd here
-                load_stage(m_begin + (kt + 1) * BK, S0{});
-                stage_ilv(0, bias, S1{});
-                __syncthreads();
-                load_stage(m_begin + (kt + 2) * BK, S1{});
-                stage_ilv(1, bias, S0{});
-                __syncthreads();
-            }
-            if (kt < KT) {
-                load_stage(m_begin + (kt + 1) * BK, S0{});
-                stage_ilv(0, bias, S1{});
-                __syncthreads();
-            }
-            mfma_stage((KT - 1) & 1);
-            return;
-        }
         int buf = 0;
-        load_stage(m_begin, S0{});
-        store_stage(0, bias, S0{});
+        load_stage(m_begin);
+        store_stage(0, bias);
         __syncthreads();
         for (int kt = 1; kt < KT; ++kt) {
-            load_stage(m_begin + kt * BK, S0{});
-#ifndef DTC_S3_NO_ILV
-            stage_ilv(buf, bias, S0{});
-#else
-            mfma_stage(buf);
-            store_stage(buf ^ 1, bias, S0{});
-#endif
+            load_stage(m_begin + kt * BK);
+            stage_ilv(buf, bias);
             __syncthreads();
             buf ^= 1;
         }
@@ -300,7 +240,7 @@ __global__ __launch_bounds__(256, H2 ? DTC_WGRAD_H2_WG : 2) void wgrad_s3_group_
                 for (int r = 0; r < 16; ++r) acc[i][jj][r] = poison ? __builtin_nanf("") : __builtin_ldexpf(acc[i][jj][r], -(ez + exx));
     }
     __syncthreads();
-    float* slab = J.part + ((long long)split * (J.tile_end - (j > 0 ? G.job[j - 1].tile_end : 0)) + t) * (TILE * TILE);
+    float* slab = J.part + ((long long)split * job_tiles(G, jp.j) + t) * (TILE * TILE);
     float* patch = reinterpret_cast<float*>(&As[0][0][0]) + wave * (32 * LDW);
     const int prow = lane >> 3, pc4 = lane & 7;
 #pragma unroll
@@ -342,139 +282,48 @@ __global__ __launch_bounds__(256) void wgrad_s3_reduce_kernel(const S3Group G) {
         J.db[n] = s;
         return;
     }
-    int t = b >> 4;
-    const int rg = b & 15;
-    int j = 0;
-    while (j < G.count - 1 && t >= G.job[j].tile_end) ++j;
-    const int tiles_j = G.job[j].tile_end - (j > 0 ? G.job[j - 1].tile_end : 0);
-    if (j > 0) t -= G.job[j - 1].tile_end;
-    const S3Job& J = G.job[j];
-    const int tr = t / J.col_tiles;
-    int tc = t - tr * J.col_tiles;
-    int seg = 0;
-    for (; seg < J.X.nseg - 1; ++seg) {
-        const int nt = (J.X.s[seg].width + TILE - 1) / TILE;
-        if (tc < nt) break;
-        tc -= nt;
-    }
-    const SegDev& sd = J.X.s[seg];
-    const int pn = rg * 8 + (threadIdx.x >> 5), pc4 = threadIdx.x & 31;
-    const int n = tr * TILE + logical(pn);
-    if (n >= J.N) return;
-    const f32x4* p = reinterpret_cast<const f32x4*>(J.part + (long long)t * (TILE * TILE) + (long long)pn * TILE) + pc4;
-    const long long step = (long long)tiles_j * (TILE * TILE / 4);
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    int sp = 0;
-    for (; sp + 3 < G.splits; sp += 4) {
-        const f32x4 v0 = p[(long long)sp * step], v1 = p[(long long)(sp + 1) * step], v2 = p[(long long)(sp + 2) * step], v3 = p[(long long)(sp + 3) * step];
+    reduce_slab_rows<4>(G, b, [](int p) { return logical(p); }, [](const S3Job& J, int n, int tc, int pc4, const f32x4& sum) {
+        const SegTile st = seg_tile(J.X, tc, TILE);
+        const SegDev& sd = J.X.s[st.seg];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] = (((acc[e] + v0[e]) + v1[e]) + v2[e]) + v3[e];
-    }
-    for (; sp < G.splits; ++sp) {
-        const f32x4 v0 = p[(long long)sp * step];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] += v0[e];
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int lc = tc * TILE + logical(4 * pc4 + e);
-        if (lc < sd.width) J.dW[(long long)n * J.K + sd.start + lc] = acc[e];
-    }
+        for (int e = 0; e < 4; ++e) {
+            const int lc = st.tc * TILE + logical(4 * pc4 + e);
+            if (lc < sd.width) J.dW[(long long)n * J.K + sd.start + lc] = sum[e];
+        }
+    });
 }
 
-// DTC_WGRAD_S3_FILL=1: as many batch slices as fill the chip's 768 workgroup slots ONCE (61 tiles: 12 slices = 732 workgroups
-// instead of 8 = 488 on 768 slots), with the balanced (slice, tile) -> XCD map
-bool fill_slots() {
-    static const bool on = [] {
-        return false;                                // (measured no faster; kept as code for the balanced map below)
-    }();
-    return on;
-}
-
-int split_cap() {
-    static const int cap = [] {
-        return 24;
-    }();
-    return cap;
-}
-
-int group_splits_s3(int M, int tiles_total) {
-    // 768: eight batch slices for the 61..70-tile groups of the bench step.  Measured (tools/jobs/r3_sweep2.sh): 512..1536 within
-    // 0.5 % of each other in step time, 2048 (32 slices) no faster; the partial slabs are HBM traffic written and read once
-    // per slice, so the smallest count that still fills the chip wins (family traffic 1.30 -> 1.15 x the algorithmic bytes)
-    // (round 4, two-term fp16 kernels -- half the matrix work per workgroup: 1536 = 24 slices for the 61..64-tile groups, 16 for the
-    // 70-tile one: 57.4 vs 60.2 ms per step; 2048 / 3072 with a higher cap: 59.7 / 61.0 vs 59.1 on another box)
-    constexpr int target = 1536;
-    int s = target / (tiles_total > 0 ? tiles_total : 1);
-    if (!fill_slots()) s = s / 8 * 8;                 // the slice -> XCD map needs whole groups of eight
-    if (s < 8) s = 8;
-    if (s > split_cap()) s = split_cap();               // small groups: bounded slab traffic (64 KiB per tile and slice, written and re-read)
-    const int max_s = (int)dtc::ceil_div(dtc::ceil_div(M, BK * 8), 8) * 8;
-    if (s > max_s) s = max_s;
-    return s;
-}
-
-constexpr int SLOT_BYTES = MAX_JOBS_S3 * 5 * AMAX_RECORD_BYTES;      // 12 jobs x (dZ + 4 segments of X) records
-struct S3Plan {
-    S3Group dev;
+constexpr int SLOT_BYTES = WGRAD_MAX_JOBS * 5 * AMAX_RECORD_BYTES;      // 12 jobs x (dZ + 4 segments of X) records
+struct S3Plan : WgradPlan<S3Group> {
     u32* slots;
-    long long bytes;
-    int red_blocks;
-    double flop, algo_bytes;
 };
 
 int plan_s3(const DtcWgradJob* jobs, int count, int M, void* workspace, S3Plan& P) {
-    DTC_REQUIRE(jobs != nullptr && count >= 1 && count <= MAX_JOBS_S3, "job count %d outside 1..%d", count, MAX_JOBS_S3);
-    DTC_REQUIRE(M > 0, "bad M=%d", M);
-    S3Group& G = P.dev;
-    G.count = count;
-    G.M = M;
-    int tiles = 0, row_tiles = 0;
-    for (int j = 0; j < count; ++j) {
-        const DtcWgradJob& h = jobs[j];
-        DTC_REQUIRE(h.N > 0 && h.K > 0 && h.lddz >= h.N, "job %d: bad shape N=%d K=%d lddz=%lld", j, h.N, h.K, (long long)h.lddz);
-        DTC_REQUIRE(h.dZ && h.dW, "job %d: null pointer", j);
+    int row_tiles = 0;
+    int rc = plan_jobs(P.dev, jobs, count, M, SLICES_S3, BK, [&](int j, const DtcWgradJob& h, S3Job& d, int& tiles) -> int {
+        int bad = check_job(h, j);
+        if (bad != DTC_OK) return bad;
         DTC_REQUIRE((h.dz_rows > 0 ? h.dz_rows : (long long)M) * h.lddz <= MAX_ELEMS, "job %d: matrix too large", j);
         DTC_REQUIRE(h.dz_rows >= 0 && (h.dz_rows == 0 || h.X.idx != nullptr), "job %d: dz_rows needs the row map X.idx", j);
-        S3Job& d = G.job[j];
-        int rc = to_dev(&h.X, d.X, h.K, false, M, "dtc_linear_wgrad_group_s3 / _h2");
-        if (rc != DTC_OK) return rc;
-        d.dZ = h.dZ;
-        d.lddz = h.lddz;
+        bad = describe_job(h, d, M, TILE, "dtc_linear_wgrad_group_s3 / _h2");
+        if (bad != DTC_OK) return bad;
         d.dz_rows = h.dz_rows;
-        d.dW = h.dW;
-        d.db = h.db;
         d.za = h.dz_amax;
         for (int i = 0; i < 4; ++i) d.xa[i] = i < h.X.nseg ? h.X.seg[i].amax : nullptr;
-        d.N = h.N;
-        d.K = h.K;
-        d.col_tiles = 0;
-        for (int i = 0; i < d.X.nseg; ++i) d.col_tiles += (int)dtc::ceil_div(d.X.s[i].width, TILE);
         d.row_tiles = (int)dtc::ceil_div(h.N, TILE);
-        tiles += d.row_tiles * d.col_tiles;
+        tiles = d.row_tiles * d.col_tiles;
         row_tiles += d.row_tiles;
-        d.tile_end = tiles;
-    }
-    G.tiles_total = tiles;
-    G.splits = group_splits_s3(M, tiles);
-    G.rows_per_split = (int)dtc::ceil_div(dtc::ceil_div(M, G.splits), BK) * BK;
-    G.per_xcd = (G.splits % 8) ? (int)dtc::ceil_div((long long)G.splits * tiles, 8) : 0;
-    long long off = 0;
-    P.flop = P.algo_bytes = 0.0;
-    for (int j = 0; j < count; ++j) {
-        S3Job& d = G.job[j];
-        const long long tiles_j = d.tile_end - (j > 0 ? G.job[j - 1].tile_end : 0);
-        d.part = workspace ? (float*)((char*)workspace + off) : nullptr;
-        off += (long long)G.splits * tiles_j * TILE * TILE * (long long)sizeof(float);
-        d.bpart = workspace ? (float*)((char*)workspace + off) : nullptr;
-        off += (long long)G.splits * d.row_tiles * TILE * (long long)sizeof(float);
-        P.flop += 2.0 * M * (double)d.N * d.K;
-        P.algo_bytes += 4.0 * ((double)M * d.N + (double)M * d.K + (double)d.N * (d.K + 1));
-    }
+        return DTC_OK;
+    });
+    if (rc != DTC_OK) return rc;
+    const long long splits = P.dev.splits;
+    long long off = plan_slabs(P, workspace, [&](S3Job& d, int tiles_j, auto take) {
+        d.part = take(splits * tiles_j * TILE * TILE * (long long)sizeof(float));
+        d.bpart = take(splits * d.row_tiles * TILE * (long long)sizeof(float));
+    });
     P.slots = workspace ? (u32*)((char*)workspace + off) : nullptr;      // fp16 launches: amax slots of operands that came without one
-    off += SLOT_BYTES;
-    P.bytes = off;
-    P.red_blocks = tiles * 16 + row_tiles;
+    P.bytes = off + SLOT_BYTES;
+    P.red_blocks = P.dev.tiles_total * 16 + row_tiles;
     return DTC_OK;
 }
 
@@ -516,22 +365,17 @@ int wgrad_group_s3(const DtcWgradJob* jobs, int count, int M, void* workspace, v
         DTC_REQUIRE(amax_group_run(A, P.slots, SLOT_BYTES, s), "hipMemsetAsync failed");
     }
     const S3Group& G = P.dev;
-    {
-        dtc::ProfScope prof(dtc::prof_shape_name("linear_wgrad", M, G.tiles_total, count), P.flop, s, P.algo_bytes);
-        const int grid = G.per_xcd > 0 ? 8 * G.per_xcd : G.tiles_total * 8 * (int)dtc::ceil_div(G.splits, 8);
-        bool any_rows = false;
-        for (int j = 0; j < G.count; ++j) any_rows = any_rows || G.job[j].dz_rows > 0;
-        if (h2) {
-            if (any_rows) hipLaunchKernelGGL((wgrad_s3_group_kernel<true, true>), dim3(grid), dim3(256), 0, s, G);
-            else hipLaunchKernelGGL((wgrad_s3_group_kernel<false, true>), dim3(grid), dim3(256), 0, s, G);
-        } else if (any_rows) hipLaunchKernelGGL((wgrad_s3_group_kernel<true>), dim3(grid), dim3(256), 0, s, G);
-        else hipLaunchKernelGGL((wgrad_s3_group_kernel<false>), dim3(grid), dim3(256), 0, s, G);
-    }
-    {
-        dtc::ProfScope prof(dtc::prof_shape_name("wgrad_reduce", G.splits, G.tiles_total, count), (double)P.bytes + P.bytes / (double)G.splits, s);
-        hipLaunchKernelGGL(wgrad_s3_reduce_kernel, dim3(P.red_blocks), dim3(256), 0, s, G);
-    }
-    return dtc::check_launch("wgrad_group_s3");
+    bool any_rows = false;
+    for (int j = 0; j < G.count; ++j) any_rows = any_rows || G.job[j].dz_rows > 0;
+    return wgrad_launch_pair(P, s, "wgrad_group_s3",
+        [&](int grid) {
+            if (h2) {
+                if (any_rows) hipLaunchKernelGGL((wgrad_s3_group_kernel<true, true>), dim3(grid), dim3(256), 0, s, G);
+                else hipLaunchKernelGGL((wgrad_s3_group_kernel<false, true>), dim3(grid), dim3(256), 0, s, G);
+            } else if (any_rows) hipLaunchKernelGGL((wgrad_s3_group_kernel<true>), dim3(grid), dim3(256), 0, s, G);
+            else hipLaunchKernelGGL((wgrad_s3_group_kernel<false>), dim3(grid), dim3(256), 0, s, G);
+        },
+        [&] { hipLaunchKernelGGL(wgrad_s3_reduce_kernel, dim3(P.red_blocks), dim3(256), 0, s, G); });
 }
 }  // namespace
 

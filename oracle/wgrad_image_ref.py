@@ -1,6 +1,6 @@
 """Numpy restatement of the image weight gradient's scaling scheme (TEST INFRASTRUCTURE: only tests/ import this; numpy only).
 
-Restates csrc/wgrad_h2i.hip (wgrad_h2i_group_kernel, wgrad_h2i_reduce_kernel, h2i_splits): dW [N, K] = dZ^T X and db = colsum(dZ)
+Restates csrc/wgrad_h2i.hip (wgrad_h2i_group_kernel, wgrad_h2i_reduce_kernel; slice rule SLICES_H2I of csrc/wgrad_plan.hpp): dW [N, K] = dZ^T X and db = colsum(dZ)
 from two operand images (format: oracle/h2image.py), with exact (float64) accumulation in place of the matrix pipe's fp32 one.
 
 The scheme.  Row m of the images holds (hi, lo) = split(dZ[m] 2^eZ[m]) and split(X[m] 2^eX[m]), one exponent per row and block of
@@ -58,7 +58,7 @@ def bits_kept(k):
 
 
 def slices(M, tiles_total):
-    """(batch slices, rows per slice) of a launch over M rows and `tiles_total` 128 x 128 tiles of all its jobs (h2i_splits)"""
+    """(batch slices, rows per slice) of a launch over M rows and `tiles_total` 128 x 128 tiles of all its jobs (wgrad_slices with SLICES_H2I, csrc/wgrad_plan.hpp)"""
     s = max(8, min(24, 768 // max(tiles_total, 1) // 8 * 8))
     s = min(s, -(-(-(-M // 128)) // 8) * 8)
     return s, -(-(-(-M // s)) // 128) * 128

@@ -171,7 +171,7 @@ def part_ld(K):                                         # gemm_core.hpp:23
     return (K + 4) & ~3
 
 
-def wgrad_variant(M, N, widths):                        # wgrad.hip:350-364 (pick_bn, wgrad_splits), 485-508
+def wgrad_variant(M, N, widths):                        # wgrad.hip (pick_bn, dtc_linear_wgrad), wgrad_plan.hpp (wgrad_slices, SLICES_LAYER)
     """-> (partial kernel, reduce kernel, splits, rows per split); widths: the segments of X"""
     K = sum(widths)
     bn = 32 if K <= 32 else 64

@@ -194,3 +194,41 @@ def test_both_representations_stay_selectable_at_run_time():
         out[h2] = Y
         assert float((Y.double() - ref).abs().max() / ref.abs().max()) < 1.5e-6
     assert not torch.equal(out[True], out[False])                                         # different sums, same error level
+
+
+def test_grouped_weight_gradients_with_a_row_map_for_dz():
+    """dtc_wgrad_group_h2 with a job whose dZ goes through X.idx (DtcWgradJob.dz_rows): the row-map instance of the two-term kernel.  The
+    smallest group that still walks every index map of the launch: M = 1100 rows (ragged last slice, eight slices' worth of padding
+    workgroups), jobs 140 x 70 (X = gathered segments of 53 and 17 columns, dZ through the same map), 1 x 128 and 130 x 130 -- nine tiles,
+    partial row and column tiles, jobs that start at a non-zero tile sum.  Against fp64; a second call gives the same bits."""
+    from dtc_amd import _ffi, ops
+    g = torch.Generator().manual_seed(31)
+    M, R = 1100, 1500
+    d = lambda t: t.to(DEV)
+    idx = torch.randperm(R, generator=g)[:M]
+    dZ0, Xa, Xb = torch.randn(R, 140, generator=g), torch.randn(R, 53, generator=g), torch.randn(R, 40, generator=g)
+    dZ1, X1 = torch.randn(M, 1, generator=g) + 1.0, torch.randn(M, 128, generator=g)       # (a column sum far from zero)
+    dZ2, X2 = torch.randn(M, 130, generator=g), torch.randn(M, 130, generator=g)
+    idx_d, keep = d(idx), [d(t) for t in (dZ0, Xa, Xb, dZ1, X1, dZ2, X2)]
+    mats = [(keep[0], _ffi.segmat([_ffi.seg(keep[1], 0, 53, gather=True), _ffi.seg(keep[2], 9, 17, gather=True)], idx_d)),
+            (keep[3], ops.as_segmat(keep[4])), (keep[5], ops.as_segmat(keep[6]))]
+    refs = [(dZ0[idx], torch.cat([Xa[idx], Xb[idx, 9:26]], dim=1)), (dZ1, X1), (dZ2, X2)]
+    jobs = (_ffi.DtcWgradJob * 3)()
+    outs = []
+    for j, ((dz, xs), (rz, rx)) in enumerate(zip(mats, refs)):
+        N, K = rz.shape[1], rx.shape[1]
+        dW, db = torch.full((N, K), float("nan"), device=DEV), torch.full((N,), float("nan"), device=DEV)
+        jobs[j].dZ, jobs[j].lddz, jobs[j].X, jobs[j].dW, jobs[j].db, jobs[j].N, jobs[j].K = dz.data_ptr(), dz.stride(0), xs, dW.data_ptr(), db.data_ptr(), N, K
+        outs.append((dW, db))
+    jobs[0].dz_rows = R
+    ws = ops.workspace(int(_ffi.lib().dtc_wgrad_group_s3_workspace(jobs, 3, M)), DEV)
+    run = lambda: _ffi.check(_ffi.lib().dtc_wgrad_group_h2(jobs, 3, M, ws.data_ptr(), _ffi.stream()), "dtc_wgrad_group_h2")
+    run()
+    first = [(w.clone(), b.clone()) for w, b in outs]
+    for (dW, db), (rz, rx) in zip(outs, refs):
+        rw, rb = rz.double().T @ rx.double(), rz.double().sum(0)
+        assert float((dW.double().cpu() - rw).abs().max() / rw.abs().max()) < 2e-6
+        assert float((db.double().cpu() - rb).abs().max() / rb.abs().max()) < 2e-6
+    run()
+    for (dW, db), (w0, b0) in zip(outs, first):
+        assert torch.equal(dW, w0) and torch.equal(db, b0)
