@@ -9,18 +9,23 @@
 // It is a surrogate, not physics.  dtc_sim_step keeps the base level (quaternion x = y = 0, projected gravity (0, 0, -1));
 // dtc_sim_step_tilt, the other instantiation of the same kernel, lets roll and pitch follow the least-squares plane through the
 // support points the terrain asks of the stance feet -- kinematically: after a reset (identity quaternion) the first fit is one
-// substep with a tilt-rate spike.  Deliberately absent from both: attitude and base dynamics (no free flight: at least one foot is
-// always in contact), lag buffers (the current action stands where the reference takes a randomly lagged one), pushes (`forces` are
-// never touched), control types "V" and "T", and the heading command's yaw law (legged_robot.py:537-539), which stays with the caller.
+// substep with a tilt-rate spike.  dtc_sim_step_act, two further instantiations (either base), adds the reference's two training
+// disturbances: the PD goal comes from a six-slot lag buffer of scaled actions, shifted at every substep, at a slot the host draws per
+// substep for all envs (legged_robot.py:608-618), and a random planar velocity (:546-553, :673-678) that rides on the base twist as a
+// slip velocity with a chosen exponential decay -- kinematic, not a contact dynamics; its decay and floor are free constants fitted
+// to nothing.  Deliberately absent from all: attitude and base dynamics (no free flight: at least one foot is always in contact),
+// `forces` (never touched), control types "V" and "T", and the heading command's yaw law (legged_robot.py:537-539), which stays with
+// the caller.
 //
 // One 64-lane wavefront per env, 4 envs per 256-thread workgroup (as csrc/envstep.hip).  Lanes 0..11 own the joints (leg l owns
 // 3l..3l+2) and lane 3l+i computes component i of foot l; the twelve foot components are then broadcast with v_readlane and every lane
 // carries the same base state
 // through the substep, so the whole decimation loop runs in registers: each env row is loaded once, ahead of the loop, and stored once,
 // after it.  Only the terrain table is read inside the loop.  No atomics, no LDS, no scratch (every register array is indexed by
-// unrolled constants).  Latency bound: ~0.8 KB read and ~1.2 KB written per env.  -ffp-contract=off (build.py): every value is one
-// single-rounded fp32 operation in the stated order, sums over legs run in leg order from 0.0f, and tests/sim_oracle.py restates the
-// step in numpy float32 bit for bit.
+// unrolled constants).  Latency bound: ~0.8 KB read and ~1.2 KB written per env (dtc_sim_step_act: ~0.3 KB more each way).
+// -ffp-contract=off (build.py): every value is one single-rounded fp32 operation in the stated order, sums over legs run in leg order
+// from 0.0f, and tests/sim_oracle.py restates the step in numpy float32 bit for bit (tests/sim_tilt_oracle.py and
+// tests/sim_actuator_oracle.py: the other instantiations).
 #include <cstddef>
 
 #include "common.hpp"
@@ -78,16 +83,27 @@ __device__ __forceinline__ void tilt_rotate_t(const TiltR& R, float nx, float ny
 }
 
 // INVARIANTS of this kernel's signature and launch:
-//  * the descriptor `s` is the FIRST parameter, so it lies at offset 0 of the kernel-argument segment: the rows written after the
-//    loop take their pointers from there (see below).  A parameter put in front of it breaks that silently; keep the order.
+//  * the descriptor is the FIRST parameter (`d`, whose first member is the DtcSimStep `s`), so it lies at offset 0 of the
+//    kernel-argument segment: the rows written after the loop take their pointers from there (see below).  A parameter put in front
+//    of it breaks that silently; keep the order.  (ACT: lag_state and push_vel are needed ahead of the loop and come from `d`
+//    itself; after the loop they, u_push and the push constants come from the segment like the rest.)
 //  * one wavefront owns one env row and no other wavefront touches it (grid = ceil(N / 4) workgroups of 4 wavefronts, n from the
 //    wavefront's index): the ring-buffer shift below has lanes load slot t + 1 and store slot t of the same env, which is right
 //    only because a wavefront's loads issue ahead of its stores and nobody else writes those slots.
 static_assert(offsetof(DtcSimStep, actions_in) == 0 && sizeof(DtcSimStep) % 8 == 0, "descriptor layout the late loads rely on");
+// The first parameter: the descriptor alone, or (ACT) the descriptor with the actuator's by-value struct behind it, so that the late
+// loads find both at offsets the language fixes (0 and offsetof(SimDesc<true>, a)) whatever follows in the argument list.
+template <bool ACT> struct SimDesc { DtcSimStep s; };
+template <> struct SimDesc<true> { DtcSimStep s; DtcSimActuator a; };
+static_assert(offsetof(SimDesc<true>, s) == 0 && offsetof(SimDesc<true>, a) % 8 == 0 && sizeof(SimDesc<false>) == sizeof(DtcSimStep),
+              "descriptor layout the late loads rely on");
 // TILT = false is dtc_sim_step, the yaw-only base; TILT = true is dtc_sim_step_tilt: the body z-axis n (yaw frame) lives in the
 // quaternion between steps and in three registers through the loop, and r = Rt p, sv = Rt u stand where the yaw-only step has p, u.
-template <bool TILT>
-__global__ __launch_bounds__(256) void sim_step_kernel(const DtcSimStep s, const SimK k, int N) {
+// ACT = true is dtc_sim_step_act (either base): the PD goal comes from the six-slot lag buffer of scaled actions, which lanes 0..11
+// hold in registers through the loop, and a pending push (two wave-uniform registers) rides on the base twist and decays.
+template <bool TILT, bool ACT>
+__global__ __launch_bounds__(256) void sim_step_kernel(const SimDesc<ACT> d, const SimK k, int N) {
+    const DtcSimStep& s = d.s;
     const int lane = threadIdx.x & 63;
     const int n = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
     if (n >= N) return;
@@ -136,6 +152,14 @@ __global__ __launch_bounds__(256) void sim_step_kernel(const DtcSimStep s, const
 
     const float a = fminf(fmaxf(act, -k.clip), k.clip);
     const float goal = fminf(fmaxf(a * k.action_scale + dflt, lo), hi);
+    float lg[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, px = 0.f, py = 0.f;              // ACT: the joint's lag slots, the pending push (world)
+    if constexpr (ACT) {
+        if (joint) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) lg[i] = d.a.lag_state[(e * 6 + i) * D + lane];
+        }
+        if (d.a.push) px = d.a.push_vel[e * 2], py = d.a.push_vel[e * 2 + 1];
+    }
 
     float tau = 0.f, p[4][3], u[4][3], w = 0.f, vbx = 0.f, vby = 0.f, vz = 0.f, nc = 0.f;
     bool ct[4];
@@ -146,8 +170,21 @@ __global__ __launch_bounds__(256) void sim_step_kernel(const DtcSimStep s, const
         for (int i = 0; i < 3; ++i) p[l][i] = 0.f, u[l][i] = 0.f;
     }
     for (int it = 0; it < k.dec; ++it) {
+        // 0. (ACT) the lag buffer shifts, takes the scaled action, and slot choice[it] (wave-uniform) is the PD goal
+        float g = goal;
+        if constexpr (ACT) {
+#pragma unroll
+            for (int i = 0; i < 5; ++i) lg[i] = lg[i + 1];
+            lg[5] = a * k.action_scale;
+            const int ch = d.a.lag_choice[it];
+            float sel = lg[5];
+#pragma unroll
+            for (int i = 0; i < 5; ++i) sel = ch == i ? lg[i] : sel;
+            const float gl = fminf(fmaxf(sel + dflt, lo), hi);
+            g = d.a.lag ? gl : goal;
+        }
         // 1. PD law, 2. joint integration with hard limits (joint lanes)
-        tau = fminf(fmaxf(((kp * ((goal - q) + off)) - kd * qd) * strength, -limit), limit);
+        tau = fminf(fmaxf(((kp * ((g - q) + off)) - kd * qd) * strength, -limit), limit);
         qd = qd + (tau / k.inertia) * k.dt;
         q = q + qd * k.dt;
         if (q < lo) q = lo, qd = 0.f;
@@ -250,6 +287,14 @@ __global__ __launch_bounds__(256) void sim_step_kernel(const DtcSimStep s, const
             wy = (nnx - nx) / k.dt;
             nx = nnx, ny = nny, nz = nnz;
         }
+        // 7p. (ACT) a pending push rides on the twist: a select, so that an env without one keeps the bits above (the sign of a
+        // zero included)
+        if constexpr (ACT) {
+            const bool pushed = px != 0.0f || py != 0.0f;
+            const float ax = vbx + (c * px + sn * py), ay = vby + (c * py - sn * px);
+            vbx = pushed ? ax : vbx;
+            vby = pushed ? ay : vby;
+        }
         // 8. integrate the base
         x = x + (c * vbx - sn * vby) * k.dt;
         y = y + (sn * vbx + c * vby) * k.dt;
@@ -260,6 +305,10 @@ __global__ __launch_bounds__(256) void sim_step_kernel(const DtcSimStep s, const
         const float rq = sqrtf(zn * zn + wn * wn);
         qz = zn / rq;
         qw = wn / rq;
+        if constexpr (ACT) {                                                       // 8p. the push decays, and ends below the floor
+            px = px * d.a.keep, py = py * d.a.keep;
+            if (px * px + py * py < d.a.floor2) px = 0.0f, py = 0.0f;
+        }
     }
 
     // ---- the env's rows, once.  Every load of the bookkeeping below that another lane's store could change is issued first.
@@ -274,6 +323,31 @@ __global__ __launch_bounds__(256) void sim_step_kernel(const DtcSimStep s, const
     const float c = 1.0f - 2.0f * (qz * qz), sn = 2.0f * (qz * qw);
     const float Vx = c * vbx - sn * vby, Vy = sn * vbx + c * vby;
     const float fz = k.weight / nc;
+    // ACT: a new push (the host's flag, legged_robot.py:546-553, :673-678) is the pending push of the next step and overwrites the
+    // root's planar velocity, after base_lin_vel and the foot velocities took the old one.  Every lane draws the same two values.
+    float rvx = Vx, rvy = Vy;
+    if constexpr (ACT) {
+        const __attribute__((address_space(4))) DtcSimActuator* oa =
+            (const __attribute__((address_space(4))) DtcSimActuator*)(args + offsetof(SimDesc<true>, a));
+        if (oa->push && oa->push_now) {
+            float u0, u1;
+            if (oa->u_push) {
+                u0 = oa->u_push[e * 2], u1 = oa->u_push[e * 2 + 1];
+            } else {
+                const U4 r = philox4x32_10(U4{(unsigned)n, 1u, k.ctr_lo, k.ctr_hi}, k.seed_lo, k.seed_hi);
+                u0 = (float)(r.x >> 8) * 5.9604644775390625e-08f;
+                u1 = (float)(r.y >> 8) * 5.9604644775390625e-08f;
+            }
+            px = oa->push_span * u0 + oa->push_lo;
+            py = oa->push_span * u1 + oa->push_lo;
+            rvx = px, rvy = py;
+        }
+        if (joint) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) oa->lag_state[(e * 6 + i) * D + lane] = lg[i];
+        }
+        if (oa->push && lane < 2) oa->push_vel[e * 2 + lane] = lane == 0 ? px : py;
+    }
     // TILT: everything below takes the NEW tilt, as it takes the new yaw.  bl, ba: the base velocities in the body frame (Rt^T);
     // oq: q_yaw (x) q_tilt, q_tilt = (-ny, nx, 0, 1 + nz) / sqrt(2 (1 + nz))
     TiltR R{1.f, 0.f, 1.f};
@@ -299,7 +373,7 @@ __global__ __launch_bounds__(256) void sim_step_kernel(const DtcSimStep s, const
     if (lane < 13) {
         float v = 0.f;
         v = lane == 0 ? x : v, v = lane == 1 ? y : v, v = lane == 2 ? z : v, v = lane == 5 ? oq[2] : v, v = lane == 6 ? oq[3] : v;
-        v = lane == 7 ? Vx : v, v = lane == 8 ? Vy : v, v = lane == 9 ? vz : v, v = lane == 12 ? w : v;
+        v = lane == 7 ? rvx : v, v = lane == 8 ? rvy : v, v = lane == 9 ? vz : v, v = lane == 12 ? w : v;
         if constexpr (TILT) v = lane == 3 ? oq[0] : v, v = lane == 4 ? oq[1] : v, v = lane == 10 ? Wx : v, v = lane == 11 ? Wy : v;
         o->root_states[e * 13 + lane] = v;
     }
@@ -416,8 +490,15 @@ extern "C" int dtc_sim_abi_sizes(int64_t* out, int cap) {
     return 2;
 }
 
-// dtc_sim_step (tilt == nullptr) and dtc_sim_step_tilt: one validation, one descriptor, the two instantiations of one kernel
-static int sim_step_launch(const DtcSimStep* st, const DtcSimCfg* cfg, const DtcSimTilt* tilt, int N, void* stream) {
+extern "C" int dtc_sim_act_abi_sizes(int64_t* out, int cap) {
+    const int64_t sz[] = {sizeof(DtcSimActuator)};
+    if (cap > 0 && out) out[0] = sz[0];
+    return 1;
+}
+
+// dtc_sim_step (tilt == nullptr), dtc_sim_step_tilt and dtc_sim_step_act (act != nullptr, either base): one validation, one
+// descriptor, the four instantiations of one kernel
+static int sim_step_launch(const DtcSimStep* st, const DtcSimCfg* cfg, const DtcSimTilt* tilt, const DtcSimActuator* act, int N, void* stream) {
     DTC_REQUIRE(st && cfg, "null descriptor");
     DTC_REQUIRE(N > 0 && N <= (1 << 24), "N %d outside 1..2^24", N);
     const DtcSimStep& s = *st;
@@ -455,24 +536,46 @@ static int sim_step_launch(const DtcSimStep* st, const DtcSimCfg* cfg, const Dtc
     k.cmd_x = span_of(c.lin_vel_x), k.cmd_y = span_of(c.lin_vel_y), k.cmd_third = span_of(c.heading_command ? c.heading : c.ang_vel_yaw);
     k.seed_lo = (unsigned)c.seed, k.seed_hi = (unsigned)(c.seed >> 32), k.ctr_lo = (unsigned)c.counter, k.ctr_hi = (unsigned)(c.counter >> 32);
 
-    hipStream_t hs = (hipStream_t)stream;
-    dtc::ProfScope prof(tilt ? "sim_step_tilt" : "sim_step", (double)N * (2048.0 + 12.0 * c.num_bodies + 8.0 * c.buffer_len * (3 + c.num_commands)), hs);
     if (tilt) {
         DTC_REQUIRE(tilt->max_slope > 0.f && tilt->max_slope <= 1e3f && tilt->min_det >= 0.f, "max_slope %g outside (0, 1000] or min_det %g < 0",
                     (double)tilt->max_slope, (double)tilt->min_det);
         k.max_slope = tilt->max_slope, k.min_det = tilt->min_det;
-        hipLaunchKernelGGL(sim_step_kernel<true>, dim3((unsigned)dtc::ceil_div(N, 4)), dim3(256), 0, hs, s, k, N);
-        return dtc::check_launch("sim_step_tilt");
     }
-    hipLaunchKernelGGL(sim_step_kernel<false>, dim3((unsigned)dtc::ceil_div(N, 4)), dim3(256), 0, hs, s, k, N);
-    return dtc::check_launch("sim_step");
+    if (act) {                                                                     // comparisons written so that a NaN is refused
+        DTC_REQUIRE(act->lag_state, "null lag_state");
+        DTC_REQUIRE(!act->push || act->push_vel, "null push_vel with pushes configured");
+        for (int it = 0; it < c.decimation; ++it)
+            DTC_REQUIRE(act->lag_choice[it] <= 5, "lag_choice[%d] = %d outside 0..5", it, (int)act->lag_choice[it]);
+        DTC_REQUIRE(act->keep > 0.f && act->keep <= 1.f, "keep %g outside (0, 1]", (double)act->keep);
+        DTC_REQUIRE(act->floor2 >= 0.f && act->push_span >= 0.f, "negative push floor %g or span %g", (double)act->floor2, (double)act->push_span);
+    }
+
+    hipStream_t hs = (hipStream_t)stream;
+    const dim3 grid((unsigned)dtc::ceil_div(N, 4)), block(256);
+    const char* name = act ? (tilt ? "sim_step_tilt_act" : "sim_step_act") : (tilt ? "sim_step_tilt" : "sim_step");
+    dtc::ProfScope prof(name, (double)N * (2048.0 + 12.0 * c.num_bodies + 8.0 * c.buffer_len * (3 + c.num_commands) + (act ? 592.0 : 0.0)), hs);
+    if (act) {
+        const SimDesc<true> d{s, *act};
+        if (tilt) hipLaunchKernelGGL((sim_step_kernel<true, true>), grid, block, 0, hs, d, k, N);
+        else hipLaunchKernelGGL((sim_step_kernel<false, true>), grid, block, 0, hs, d, k, N);
+    } else {
+        const SimDesc<false> d{s};
+        if (tilt) hipLaunchKernelGGL((sim_step_kernel<true, false>), grid, block, 0, hs, d, k, N);
+        else hipLaunchKernelGGL((sim_step_kernel<false, false>), grid, block, 0, hs, d, k, N);
+    }
+    return dtc::check_launch(name);
 }
 
 extern "C" int dtc_sim_step(const DtcSimStep* st, const DtcSimCfg* cfg, int N, void* stream) {
-    return sim_step_launch(st, cfg, nullptr, N, stream);
+    return sim_step_launch(st, cfg, nullptr, nullptr, N, stream);
 }
 
 extern "C" int dtc_sim_step_tilt(const DtcSimStep* st, const DtcSimCfg* cfg, const DtcSimTilt* tilt, int N, void* stream) {
     DTC_REQUIRE(tilt, "null DtcSimTilt");
-    return sim_step_launch(st, cfg, tilt, N, stream);
+    return sim_step_launch(st, cfg, tilt, nullptr, N, stream);
+}
+
+extern "C" int dtc_sim_step_act(const DtcSimStep* st, const DtcSimCfg* cfg, const DtcSimTilt* tilt, const DtcSimActuator* act, int N, void* stream) {
+    DTC_REQUIRE(act, "null DtcSimActuator");
+    return sim_step_launch(st, cfg, tilt, act, N, stream);
 }

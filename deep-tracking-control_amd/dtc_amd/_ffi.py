@@ -202,6 +202,13 @@ class DtcSimTilt(C.Structure):
     _fields_ = [("max_slope", C.c_float), ("min_det", C.c_float)]
 
 
+class DtcSimActuator(C.Structure):
+    """include/dtc_hip.h: what dtc_sim_step_act adds to a surrogate step (lag buffer, pending push); field order as there."""
+    _fields_ = ([(k, C.c_void_p) for k in ("lag_state", "push_vel", "u_push")] + [("lag_choice", C.c_uint8 * 64)] +
+                [(k, C.c_int32) for k in ("lag", "push", "push_now")] +
+                [(k, C.c_float) for k in ("keep", "floor2", "push_span", "push_lo")] + [("reserved", C.c_int32)])
+
+
 class DtcTerrainCfg(C.Structure):
     """include/dtc_hip.h: the configuration of dtc_terrain_generate; field order as there."""
     _fields_ = ([(k, C.c_double) for k in ("horizontal_scale", "vertical_scale", "border_size", "terrain_length", "terrain_width")] +
@@ -233,7 +240,7 @@ class DtcProfRec(C.Structure):
 ACT = {None: 0, "none": 0, "relu": 1, "crelu": 1, "elu": 2, "selu": 3, "lrelu": 4, "tanh": 5, "sigmoid": 6}
 MAX_OPERAND_ELEMS = (1 << 29) - 1
 
-ABI_VERSION = 24        # DTC_ABI_VERSION of include/dtc_hip.h this binding was written against
+ABI_VERSION = 25        # DTC_ABI_VERSION of include/dtc_hip.h this binding was written against
 
 _SIGS = {
     "dtc_version": (C.c_int, []),
@@ -262,6 +269,9 @@ _SIGS = {
     "dtc_sim_step": (C.c_int, [C.POINTER(DtcSimStep), C.POINTER(DtcSimCfg), C.c_int, c_stream]),
     "dtc_sim_tilt_abi_sizes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
     "dtc_sim_step_tilt": (C.c_int, [C.POINTER(DtcSimStep), C.POINTER(DtcSimCfg), C.POINTER(DtcSimTilt), C.c_int, c_stream]),
+    "dtc_sim_act_abi_sizes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
+    "dtc_sim_step_act": (C.c_int, [C.POINTER(DtcSimStep), C.POINTER(DtcSimCfg), C.POINTER(DtcSimTilt), C.POINTER(DtcSimActuator), C.c_int,
+                                   c_stream]),
     "dtc_terrain_abi_sizes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
     "dtc_terrain_generate": (C.c_int, [C.POINTER(DtcTerrainCfg), C.c_void_p, C.c_void_p, c_stream]),
     "dtc_check_termination": (C.c_int, [c_f32p, C.c_int, c_i32p, C.c_int, c_i64p, C.c_int64, c_f32p, c_f32p, c_f32p,
@@ -479,6 +489,9 @@ def _check_abi(l):
     theirs += list(sizes[:n])
     mine += [DtcSimTilt]                                                  # ... and by its tilt entry point's
     n = l.dtc_sim_tilt_abi_sizes(sizes, 32)
+    theirs += list(sizes[:n])
+    mine += [DtcSimActuator]                                              # ... and by its actuator entry point's
+    n = l.dtc_sim_act_abi_sizes(sizes, 32)
     theirs += list(sizes[:n])
     mine += [DtcTerrainCfg]                                               # ... and by the terrain generator's
     n = l.dtc_terrain_abi_sizes(sizes, 32)

@@ -9,6 +9,12 @@ observations), `EnvRewards`, `EnvReset` on `reset_buf`, `compute_observations(wh
 It is a surrogate, not physics (include/dtc_hip.h lists what is absent; `SimConfig.tilt` opts into a kinematic roll and pitch): it gives the kernels a state that is consistent, evolves,
 responds to actions, terminates and resets, and a reward that depends on what the policy does.
 
+`SimConfig.actuator` (opt-in, a `sim.ActuatorConfig`; None: the env above, bit for bit) adds the reference's two training
+disturbances to the same launch: the PD goal lags behind the action by a host-drawn number of substeps (`lag_state`, and
+`lag_buffer`, its six slots under the reference's name), and every `push_interval` steps, on two consecutive steps, a random planar
+velocity is given to the base (`push_vel`; `common_step_counter` is a host integer).  The push is a kinematic slip velocity with a
+chosen decay, not a contact dynamics.
+
 `SurrogateConfig.terrain` (opt-in, a `terrain.TerrainConfig`; None: the env above, bit for bit) puts the env on the DTC curriculum
 terrain generated on the device (`dtc_amd.terrain`): stairs, stepping stones, gaps, pits.  The env origins are then the sub-terrain
 origins, `terrain_levels` / `terrain_types` are set as LeggedRobot._get_env_origins does (legged_robot.py:1205-1215) and the terrain
@@ -89,7 +95,8 @@ class _Cfg:
 class SurrogateLeggedEnv(VecEnv):
     """`num_envs` kinematic quadrupeds over the int16 terrain table `height_samples` (default: flat; `synthetic.reward_table()` is
     the rough one).  `step(actions, draws=None)`: `draws` is the parity mode -- a dict with any of u_cmd [N,3], u_reset [N,26],
-    u_obs [N,53], u_heights [N,693] (uniform [0,1)) and height_noise (float); what it leaves out is drawn on the device from `seed`
+    u_obs [N,53], u_heights [N,693] (uniform [0,1)), height_noise (float) and, with `config.sim.actuator`, lag_choice (`decimation`
+    slots in 0..5, a host sequence) and u_push [N,2]; what it leaves out is drawn on the device from `seed`
     (command and reset draws by the kernels' Philox streams, the two observation noises by a seeded device generator); the reset's
     height_noise is the reference's host draw, np.random.normal(0, 0.02), from a seeded RandomState.
 
@@ -153,6 +160,11 @@ class SurrogateLeggedEnv(VecEnv):
         self.lin_vel_buffer, self.ang_vel_buffer, self.cmd_buffer = z(T, N, 2), z(T, N, 1), z(T, N, C)
         self.Kp_factors, self.Kd_factors, self.motor_strengths, self.motor_offsets = 1 + z(N, D), 1 + z(N, D), 1 + z(N, D), z(N, D)
         self.episode_length_buf = torch.zeros(N, dtype=torch.int64, device=dev)
+        self._actuator_rows = ()
+        if s.actuator is not None:                                                       # legged_robot.py:827, :546-553
+            self.lag_state, self.push_vel, self.common_step_counter = z(N, 6, D), z(N, 2), 0
+            self.lag_buffer = [self.lag_state[:, i] for i in range(6)]
+            self._actuator_rows = (self.lag_state, self.push_vel)
         self.last_contacts = torch.zeros(N, 4, dtype=torch.bool, device=dev)
         self.contact_filt = torch.zeros(N, 4, dtype=torch.bool, device=dev)
         self.robot_mass = torch.full((N,), float(s.mass), **f)
@@ -221,13 +233,20 @@ class SurrogateLeggedEnv(VecEnv):
                        base_lin_vel_last=self.base_lin_vel_last, episode_length_buf=self.episode_length_buf, contact_filt=self.contact_filt,
                        last_contacts=self.last_contacts, lin_vel_buffer=self.lin_vel_buffer, ang_vel_buffer=self.ang_vel_buffer,
                        cmd_buffer=self.cmd_buffer, u=draws.get("u_reset"), command_ranges=self.command_ranges,
+                       extra_rows=self._actuator_rows,
                        height_noise=float(self._height_noise.normal(0, 0.02)) if hn is None else float(hn))
 
     def step(self, actions: torch.Tensor, draws: dict | None = None):
         draws = draws or {}
         c, s = self.config, self.config.sim
         # 1. the surrogate's physics and the bookkeeping up to the planner
-        self.sim.step(self, actions.to(self.device, torch.float32).contiguous(), draws.get("u_cmd"))
+        if s.actuator is None:
+            self.sim.step(self, actions.to(self.device, torch.float32).contiguous(), draws.get("u_cmd"))
+        else:                                                                            # legged_robot.py:67, :673
+            self.common_step_counter += 1
+            push = s.actuator.push and self.common_step_counter % s.push_interval in (0, 1)
+            self.sim.step(self, actions.to(self.device, torch.float32).contiguous(), draws.get("u_cmd"), lag_choice=draws.get("lag_choice"),
+                          u_push=draws.get("u_push"), push=push)
         if s.heading_command:                                                            # legged_robot.py:537-539
             if s.tilt:                                                                   # forward = quat_apply(q, (1, 0, 0))
                 qx, qy, qz, qw = self.base_quat.unbind(dim=1)
@@ -243,7 +262,7 @@ class SurrogateLeggedEnv(VecEnv):
             # sums and every later step: its rows are zeroed here, ahead of every consumer, and it is reset in this step
             bad = ~(torch.isfinite(self.dof_state).flatten(1).all(dim=1) & torch.isfinite(self.root_states).all(dim=1))
             for t in (self.dof_state, self.root_states, self.rigid_body_state, self.contact_forces, self.torques, self.base_lin_vel,
-                      self.base_ang_vel, self.last_base_ang_vel, self.base_pos, self.base_quat):
+                      self.base_ang_vel, self.last_base_ang_vel, self.base_pos, self.base_quat) + self._actuator_rows:
                 t.masked_fill_(bad.view(-1, *([1] * (t.dim() - 1))), 0.0)
             for t in (self.lin_vel_buffer, self.ang_vel_buffer, self.cmd_buffer):
                 t.masked_fill_(bad.view(1, -1, 1), 0.0)

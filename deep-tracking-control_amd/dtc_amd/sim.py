@@ -1,10 +1,13 @@
-"""Host side of the surrogate legged env step (csrc/sim.hip, `dtc_sim_step` and `dtc_sim_step_tilt`): the state the env kernels run
+"""Host side of the surrogate legged env step (csrc/sim.hip, `dtc_sim_step`, `dtc_sim_step_tilt`, `dtc_sim_step_act`): the state the env kernels run
 on when no simulator stands behind them.  One launch per env step stands where the reference calls Isaac Gym: `decimation` substeps
 of the PD law of LeggedRobot._compute_torques (control type "P"), a kinematic quadruped that rides on its stance feet over the int16
 terrain table, and the bookkeeping of post_physics_step up to the planner.  include/dtc_hip.h states every operation; it is a
-surrogate, not physics (no attitude or base dynamics, no free flight, no lag buffers, no pushes, no "V" / "T" control, no heading
-yaw law).  By default the base only yaws; `SimConfig.tilt` (opt-in) lets its roll and pitch follow the support points of the stance
-feet, still kinematically: after a reset the identity quaternion then gives one step with a tilt-rate spike.
+surrogate, not physics (no attitude or base dynamics, no free flight, no "V" / "T" control, no heading yaw law).  By default the
+base only yaws; `SimConfig.tilt` (opt-in) lets its roll and pitch follow the support points of the stance feet, still kinematically:
+after a reset the identity quaternion then gives one step with a tilt-rate spike.  `SimConfig.actuator` (opt-in, an
+`ActuatorConfig`) adds the two disturbances the reference trains under: the PD goal taken from a six-slot lag buffer of scaled
+actions at a slot the host draws per substep, and random pushes -- here a kinematic slip velocity of the base with a chosen decay,
+not a contact dynamics.
 
 `SimConfig` holds the constants (Lite3 DTC values), `leg_tables(config)` the three small tables computed once in float64 from a
 two-link leg linearised at the default pose, and `SimStep` runs the launch on an env's own tensors (attribute names as in
@@ -30,6 +33,31 @@ _ENV_TENSORS = dict(Kp_factors=("D", torch.float32), Kd_factors=("D", torch.floa
                     projected_gravity=(3, torch.float32), base_pos=(3, torch.float32), base_quat=(4, torch.float32),
                     contact_filt=(4, torch.bool))
 _RING_BUFFERS = dict(lin_vel_buffer=2, ang_vel_buffer=1, cmd_buffer="C")
+
+
+@dataclass
+class ActuatorConfig:
+    """Actuator lag and random pushes of `dtc_sim_step_act` (include/dtc_hip.h states the operations).  `lag`: the PD goal of substep
+    `it` is the lag buffer's slot `choice[it]`, one host draw per substep for all envs from the inclusive range `lag_slots` (the
+    reference: np.random.randint(1, 5), legged_robot.py:614); slot 5 is the current action.  `push`: every `push_interval_s`, on two
+    consecutive env steps, the base's planar velocity is overwritten by a uniform draw in +- `max_push_vel_xy`
+    (legged_robot.py:546-553, :673-678).  The surrogate has no momentum to carry that velocity, so the draw rides on the base twist
+    as a slip velocity that decays with the time constant `push_decay_s` and is dropped below `push_floor` [m/s]: both are free
+    constants of the surrogate, chosen, not fitted to anything."""
+    lag: bool = True
+    lag_slots: tuple = (1, 4)
+    push: bool = True
+    push_interval_s: float = 15.0
+    max_push_vel_xy: float = 1.0
+    push_decay_s: float = 0.2
+    push_floor: float = 1e-6
+
+    def validate(self):
+        lo, hi = self.lag_slots
+        if not (0 <= int(lo) <= int(hi) <= 5):
+            raise ValueError(f"ActuatorConfig: lag_slots {self.lag_slots} outside 0..5")
+        if not (self.push_interval_s > 0 and self.push_decay_s > 0 and self.max_push_vel_xy >= 0 and self.push_floor >= 0):
+            raise ValueError("ActuatorConfig: push_interval_s and push_decay_s must be positive, max_push_vel_xy and push_floor not negative")
 
 
 @dataclass
@@ -72,6 +100,7 @@ class SimConfig:
     # height of 0.035 m.  Any three feet of the default stance (0.34 m x 0.2 m) give 1.5e-3, fp32 rounding of a collinear stance
     # of that size 1e-10.
     min_det: float = 1e-6
+    actuator: ActuatorConfig | None = None   # lag buffer and pushes (dtc_sim_step_act); None: the entry points above, bit for bit
 
     @property
     def dt(self) -> float:
@@ -80,6 +109,10 @@ class SimConfig:
     @property
     def resampling_steps(self) -> int:
         return int(self.resampling_time / self.dt)                      # legged_robot.py:534
+
+    @property
+    def push_interval(self) -> int:
+        return int(math.ceil(self.actuator.push_interval_s / self.dt))  # legged_robot.py:1240
 
     @property
     def nominal_height(self) -> float:
@@ -124,7 +157,9 @@ class SimStep:
     """`dtc_sim_step` (`dtc_sim_step_tilt` with `config.tilt`) for `num_envs` envs over the terrain table `height_samples` [rows, cols] int16.  Owns the small device tables
     (`tables`: float32 copies of `leg_tables` / `joint_tables`).  `step(env, actions, u_cmd=None)` runs one env step in place on the
     tensors of `env`; with `u_cmd` left out the kernel draws the command resamples itself (Philox, keyed by `seed` and a call
-    counter)."""
+    counter).  With `config.actuator` the launch is `dtc_sim_step_act` on the env's `lag_state` [N,6,12] and `push_vel` [N,2] as
+    well: `lag_choice` (`decimation` slots; left out: drawn from a RandomState(seed) this object owns, as the reference draws on
+    the host), `push` (the env's flag: this step draws a new push) and `u_push` [N,2] (left out: the kernel's Philox)."""
 
     def __init__(self, num_envs: int, device, config: SimConfig, height_samples: torch.Tensor, *, seed: int = 0, tables: dict | None = None):
         dev = torch.device(device)
@@ -138,6 +173,9 @@ class SimStep:
         self.height_samples = height_samples.to(dev).contiguous()
         t = dict(leg_tables(config), **joint_tables(config)) if tables is None else tables
         self.tables = {k: torch.as_tensor(np.asarray(v), dtype=torch.float32).to(dev).contiguous() for k, v in t.items()}
+        if config.actuator is not None:
+            config.actuator.validate()
+            self._lag_rng = np.random.RandomState(self.seed)
 
     def cfg_struct(self) -> "_ffi.DtcSimCfg":
         k, c = self.cfg, _ffi.DtcSimCfg()
@@ -159,8 +197,27 @@ class SimStep:
         if not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != dtype or tuple(t.shape) != tail or not t.is_contiguous():
             raise _ffi.DtcError(f"SimStep: {name} must be a contiguous {dtype} tensor of shape {tail} on {self.device}")
 
-    def step(self, env, actions: torch.Tensor, u_cmd: torch.Tensor | None = None):
+    def act_struct(self, lag_choice=None, push: bool = False) -> "_ffi.DtcSimActuator":
+        """The by-value constants of dtc_sim_step_act (the three pointers are left NULL)."""
+        k, a, act = self.cfg, self.cfg.actuator, _ffi.DtcSimActuator()
+        if lag_choice is None:
+            lag_choice = self._lag_rng.randint(int(a.lag_slots[0]), int(a.lag_slots[1]) + 1, size=int(k.decimation))
+        lag_choice = [int(v) for v in lag_choice]
+        if len(lag_choice) != int(k.decimation) or not all(0 <= v <= 5 for v in lag_choice):
+            raise _ffi.DtcError(f"SimStep: lag_choice must be {int(k.decimation)} slots in 0..5, got {lag_choice}")
+        for it, v in enumerate(lag_choice):
+            act.lag_choice[it] = v
+        act.lag, act.push, act.push_now = int(bool(a.lag)), int(bool(a.push)), int(bool(a.push) and bool(push))
+        act.keep = float(np.float32(math.exp(-k.sim_dt / a.push_decay_s)))
+        act.floor2 = float(np.float32(a.push_floor * a.push_floor))
+        act.push_span, act.push_lo = float(np.float32(2.0 * a.max_push_vel_xy)), float(np.float32(-a.max_push_vel_xy))
+        return act
+
+    def step(self, env, actions: torch.Tensor, u_cmd: torch.Tensor | None = None, *, lag_choice=None, u_push: torch.Tensor | None = None,
+             push: bool = False):
         k, N = self.cfg, self.N
+        if k.actuator is None and (lag_choice is not None or u_push is not None or push):
+            raise _ffi.DtcError("SimStep: lag_choice / u_push / push need config.actuator")
         dims = dict(D=12, B=int(k.num_bodies), C=int(k.num_commands))
         s = _ffi.DtcSimStep()
         self._check("actions", actions, (N, 12), torch.float32)
@@ -188,10 +245,23 @@ class SimStep:
         for name, t in self.tables.items():
             setattr(s, name, _ffi.ptr(t))
         c = self.cfg_struct()
-        if k.tilt:
-            tilt = _ffi.DtcSimTilt(float(k.max_slope), float(k.min_det))
+        tilt = _ffi.DtcSimTilt(float(k.max_slope), float(k.min_det)) if k.tilt else None
+        drew_push = False
+        if k.actuator is not None:
+            act = self.act_struct(lag_choice, push)
+            self._check("lag_state", env.lag_state, (N, 6, 12), torch.float32)
+            act.lag_state = _ffi.ptr(env.lag_state)
+            if k.actuator.push:
+                self._check("push_vel", env.push_vel, (N, 2), torch.float32)
+                act.push_vel = _ffi.ptr(env.push_vel)
+                if u_push is not None:
+                    self._check("u_push", u_push, (N, 2), torch.float32)
+                    act.u_push = _ffi.ptr(u_push)
+                drew_push = bool(act.push_now) and u_push is None
+            _ffi.check(_ffi.lib().dtc_sim_step_act(s, c, tilt, act, N, _ffi.stream()), "dtc_sim_step_act")
+        elif k.tilt:
             _ffi.check(_ffi.lib().dtc_sim_step_tilt(s, c, tilt, N, _ffi.stream()), "dtc_sim_step_tilt")
         else:
             _ffi.check(_ffi.lib().dtc_sim_step(s, c, N, _ffi.stream()), "dtc_sim_step")
-        if u_cmd is None:
+        if u_cmd is None or drew_push:
             self.counter += 1

@@ -7,6 +7,8 @@
                                                                           # the yaw-only env beside the tilt env (SimConfig.tilt), timing only
     python deep-tracking-control_amd/tools/closed_loop.py --terrain [--out profiles/closed_loop_terrain.txt]
                                                                           # the rough table beside the generated DTC terrain
+    python deep-tracking-control_amd/tools/closed_loop.py --actuator [--out profiles/closed_loop_actuator.txt]
+                                                                          # the env beside the env with actuator lag and pushes
 
 Per run and iteration: the mean step reward (mean of rew_buf over the iteration's 24 steps and all envs), the mean episode length
 (the runner's tracker: the last <= 100 finished episodes; "-" before the first one ends) and the mean length of the episodes in flight.
@@ -22,6 +24,9 @@ With --terrain the two runs are the env over the rough table and the env on the 
 Lite3 grid), default arithmetic, the same three interleaved rounds; then dtc_terrain_generate at the Lite3 grid (6 x 2, 1760 x 1120
 cells) and at 10 x 20 beside the numpy restatement tests/terrain_oracle.py on the host, and, on a 6 x 9 grid that holds every family
 as one column, the mean terrain level and the share of envs reset per step per family over 200 steps of an untrained policy.
+With --actuator the two runs are the yaw-only env over the rough table without and with `SimConfig(actuator=ActuatorConfig())` (the
+reference's lag range and push schedule), default arithmetic, the same three interleaved rounds; dtc_sim_step beside
+dtc_sim_step_act, alternating; and the mean step reward per iteration of both, for which nothing was tuned.
 """
 import argparse
 import os
@@ -45,18 +50,18 @@ STEPS = 24
 RUNS = (("default", {}), ("gemm_passes=1", dict(gemm_passes=1)))
 
 
-def rough_env(num_envs, tilt):
-    return SurrogateLeggedEnv(num_envs, DEV, SurrogateConfig(sim=SIM.SimConfig(tilt=tilt)), synthetic.reward_table(), seed=5)
+def rough_env(num_envs, tilt, actuator=None):
+    return SurrogateLeggedEnv(num_envs, DEV, SurrogateConfig(sim=SIM.SimConfig(tilt=tilt, actuator=actuator)), synthetic.reward_table(), seed=5)
 
 
-def make(num_envs, algo, seed=11, tilt=None, terrain=None, steps=STEPS):
-    """`tilt` None: the default env on the flat table; False / True: the yaw-only / the tilt env on the rough table; `terrain`, a
-    TerrainConfig: the env on the generated terrain."""
+def make(num_envs, algo, seed=11, tilt=None, terrain=None, steps=STEPS, actuator=None):
+    """`tilt` None: the default env on the flat table; False / True: the yaw-only / the tilt env on the rough table (`actuator`, an
+    ActuatorConfig: with lag and pushes); `terrain`, a TerrainConfig: the env on the generated terrain."""
     torch.manual_seed(seed)
     if terrain is not None:
         env = SurrogateLeggedEnv(num_envs, DEV, SurrogateConfig(terrain=terrain), seed=5)
     else:
-        env = SurrogateLeggedEnv(num_envs, DEV, SurrogateConfig(), seed=5) if tilt is None else rough_env(num_envs, tilt)
+        env = SurrogateLeggedEnv(num_envs, DEV, SurrogateConfig(), seed=5) if tilt is None else rough_env(num_envs, tilt, actuator)
     runner = dict(policy_class_name="ActorCriticDecoder", algorithm_class_name="PPO", num_steps_per_env=steps, save_interval=10 ** 9)
     return OnPolicyRunner(env, dict(runner=runner, algorithm=dict(algo), policy=dict()), log_dir=None, device=DEV), env
 
@@ -82,8 +87,8 @@ class Watch:
         self.sum.zero_()
 
 
-def learning_curve(num_envs, iters, algo):
-    r, env = make(num_envs, algo)
+def learning_curve(num_envs, iters, algo, **kw):
+    r, env = make(num_envs, algo, **kw)
     w = Watch(r, env)
     for _ in range(iters):
         r.learn(1)
@@ -102,8 +107,8 @@ def timed(fn, acc):
     return f
 
 
-def timing_round(num_envs, iters, algo, tilt=None, terrain=None):
-    r, env = make(num_envs, algo, tilt=tilt, terrain=terrain)
+def timing_round(num_envs, iters, algo, tilt=None, terrain=None, actuator=None):
+    r, env = make(num_envs, algo, tilt=tilt, terrain=terrain, actuator=actuator)
     r.learn(2)                                                # warm-up: allocations, first launches
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -268,6 +273,55 @@ def tilt_report(args):
     return lines
 
 
+def actuator_probe(num_envs, calls):
+    """dtc_sim_step beside dtc_sim_step_act on the rough table, same actions, alternating: us per call (median).  The lag slots are
+    drawn on the host as in production; a push is drawn on two of every three calls (far more often than the reference's schedule),
+    so that a push is pending in every call."""
+    envs = [rough_env(num_envs, False, act) for act in (None, SIM.ActuatorConfig())]
+    g = torch.Generator(device=DEV).manual_seed(3)
+    for e in envs:
+        e.reset()
+    acc = ([], [])
+    for i in range(calls + 20):
+        a, u = torch.randn(num_envs, 12, generator=g, device=DEV), torch.rand(num_envs, 3, generator=g, device=DEV)
+        for t, e, kw in zip(acc, envs, ({}, dict(push=i % 3 in (0, 1)))):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            e.sim.step(e, a, u, **kw)
+            torch.cuda.synchronize()
+            if i >= 20:
+                t.append(1e6 * (time.perf_counter() - t0))
+    return statistics.median(acc[0]), statistics.median(acc[1])
+
+
+def actuator_report(args):
+    runs = (("no actuator", None), ("actuator", SIM.ActuatorConfig()))
+    rounds = {tag: [] for tag, _ in runs}
+    for _ in range(3):
+        for tag, act in runs:
+            rounds[tag].append(timing_round(args.envs, args.iters, {}, tilt=False, actuator=act))
+    lines = [f"closed loop on SurrogateLeggedEnv over the rough table, without and with SimConfig(actuator=ActuatorConfig()) (lag slots 1..4, a "
+             f"push of up to 1 m/s every 15 s on two consecutive steps, decay 0.2 s): {args.envs} envs x {STEPS} steps per iteration, "
+             f"{args.iters} iterations, PPO, default arithmetic, fixed seeds",
+             "", "three interleaved rounds, median (min .. max):"]
+    for tag, _ in runs:
+        rs = rounds[tag]
+        lines.append(f"  {tag:11s} env-steps/s, whole loop {spread([r['steps_per_s'] for r in rs], '{:.0f}')}")
+        lines.append(f"  {'':11s} ms per iteration, each call closed by a synchronise: env.step x{STEPS} {spread([r['env_ms'] for r in rs], '{:.2f}')}"
+                     f" | act() x{STEPS} {spread([r['act_ms'] for r in rs], '{:.2f}')} | update() {spread([r['update_ms'] for r in rs], '{:.2f}')}")
+    probes = [actuator_probe(args.envs, args.calls) for _ in range(3)]
+    lines += ["", f"one surrogate step at {args.envs} envs, us per call (host clock, closed by a synchronise), alternating, three rounds:",
+              f"  dtc_sim_step      {spread([p[0] for p in probes])}",
+              f"  dtc_sim_step_act  {spread([p[1] for p in probes])}   (a new push on two of every three calls, one pending in every call; the host's lag draws included)",
+              "", f"mean step reward per iteration, {args.iters} iterations (the reference's schedule: pushes at env steps 1, 750, 751, 1500, ..., so in a "
+              f"short run the lag is what acts); nothing was tuned for the disturbances:"]
+    for tag, act in runs:
+        rows = learning_curve(args.envs, args.iters, {}, tilt=False, actuator=act)
+        lines.append(f"  {tag:11s} " + " ".join(f"{r[0]:+.5f}" for r in rows))
+    lines += ["", "bench.py runs no env step: its headline is not re-measured here."]
+    return lines
+
+
 ALL_FAMILIES = (0.1, 0.1, 0.1, 0.1, 0.15, 0.15, 0.1, 0.1, 0.1)
 
 
@@ -360,10 +414,11 @@ def main():
     ap.add_argument("--signal", action="store_true")
     ap.add_argument("--tilt", action="store_true")
     ap.add_argument("--terrain", action="store_true")
+    ap.add_argument("--actuator", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if args.tilt or args.terrain:
-        text = "\n".join((tilt_report if args.tilt else terrain_report)(args)) + "\n"
+    if args.tilt or args.terrain or args.actuator:
+        text = "\n".join((tilt_report if args.tilt else terrain_report if args.terrain else actuator_report)(args)) + "\n"
         print(text)
         if args.out:
             with open(args.out, "w") as f:

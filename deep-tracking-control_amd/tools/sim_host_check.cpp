@@ -1,4 +1,4 @@
-// Stand-alone host check of dtc_sim_step's argument validation, meant to be built with AddressSanitizer on the host side together
+// Stand-alone host check of the argument validation of dtc_sim_step and dtc_sim_step_act, meant to be built with AddressSanitizer on the host side together
 // with csrc/sim.hip and csrc/runtime.hip:
 //   hipcc --offload-arch=gfx950 -O1 -g -Xarch_host -fsanitize=address -Xarch_host -fno-omit-frame-pointer -I include -I csrc \
 //         csrc/sim.hip csrc/runtime.hip tools/sim_host_check.cpp -o sim_host_check
@@ -66,6 +66,51 @@ int main() {
     refused("overlapping dof_pos rows", dtc_sim_step(s, c, 4, nullptr));
     int64_t sizes[2] = {0, 0};
     if (dtc_sim_abi_sizes(sizes, 2) != 2 || sizes[0] != (int64_t)sizeof(DtcSimCfg) || sizes[1] != (int64_t)sizeof(DtcSimStep)) ++failures;
+
+    // dtc_sim_step_act: a good descriptor and good constants, then one bad member of DtcSimActuator at a time, with and without tilt
+    for (size_t i = 0; i < n_ptr; ++i) first[i] = dummy;
+    s->u_cmd = nullptr;
+    s->dof_pos_row_stride = s->dof_vel_row_stride = 24, s->dof_pos_elem_stride = s->dof_vel_elem_stride = 2;
+    *c = good_cfg();
+    DtcSimTilt* tilt = new DtcSimTilt{1.0f, 1e-6f};
+    DtcSimActuator* a = new DtcSimActuator;
+    const auto good_act = [&] {
+        std::memset(a, 0, sizeof *a);
+        a->lag_state = dummy, a->push_vel = dummy;
+        for (int it = 0; it < 4; ++it) a->lag_choice[it] = (uint8_t)(1 + it);
+        a->lag = 1, a->push = 1, a->push_now = 1, a->keep = 0.975f, a->floor2 = 1e-12f, a->push_span = 2.f, a->push_lo = -1.f;
+    };
+    for (int with_tilt = 0; with_tilt < 2; ++with_tilt) {
+        const DtcSimTilt* t = with_tilt ? tilt : nullptr;
+        good_act();
+        refused("act == NULL", dtc_sim_step_act(s, c, t, nullptr, 4, nullptr));
+        refused("act: st == NULL", dtc_sim_step_act(nullptr, c, t, a, 4, nullptr));
+        refused("act: cfg == NULL", dtc_sim_step_act(s, nullptr, t, a, 4, nullptr));
+        refused("act: N == 0", dtc_sim_step_act(s, c, t, a, 0, nullptr));
+        a->lag_state = nullptr;
+        refused("lag_state == NULL", dtc_sim_step_act(s, c, t, a, 4, nullptr));
+        good_act(), a->push_vel = nullptr;
+        refused("push_vel == NULL with pushes configured", dtc_sim_step_act(s, c, t, a, 4, nullptr));
+        good_act(), a->lag_choice[0] = 6;
+        refused("first lag choice 6", dtc_sim_step_act(s, c, t, a, 4, nullptr));
+        good_act(), a->lag_choice[3] = 255;
+        refused("last lag choice 255", dtc_sim_step_act(s, c, t, a, 4, nullptr));
+        good_act(), a->keep = 0.f;
+        refused("keep == 0", dtc_sim_step_act(s, c, t, a, 4, nullptr));
+        good_act(), a->keep = 1.0000001f;
+        refused("keep > 1", dtc_sim_step_act(s, c, t, a, 4, nullptr));
+        good_act(), a->keep = -0.5f;
+        refused("keep < 0", dtc_sim_step_act(s, c, t, a, 4, nullptr));
+        good_act(), a->floor2 = -1e-12f;
+        refused("negative floor", dtc_sim_step_act(s, c, t, a, 4, nullptr));
+        good_act(), a->push_span = -2.f;
+        refused("negative span", dtc_sim_step_act(s, c, t, a, 4, nullptr));
+    }
+    good_act(), tilt->max_slope = 0.f;
+    refused("act: max_slope == 0", dtc_sim_step_act(s, c, tilt, a, 4, nullptr));
+    if (dtc_sim_act_abi_sizes(sizes, 2) != 1 || sizes[0] != (int64_t)sizeof(DtcSimActuator)) ++failures;
+    delete a;
+    delete tilt;
     delete s;
     delete c;
     std::printf("%d failure(s)\n", failures);

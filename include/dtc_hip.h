@@ -42,7 +42,7 @@ extern "C" {
 #define DTC_ACT_SIGMOID 6
 
 /* library / device info ------------------------------------------------------------------ */
-#define DTC_ABI_VERSION 24                  /* bumped whenever a signature or a by-value struct layout changes       */
+#define DTC_ABI_VERSION 25                  /* bumped whenever a signature or a by-value struct layout changes       */
 int dtc_version(void);                       /* == DTC_ABI_VERSION of the build; the host binding refuses a mismatch   */
 /* sizeof() of the structs that cross the boundary, in the order DtcGridCfg, DtcObsCfg, DtcRowCopy, DtcSeg, DtcSegMat,
    DtcFwdLayer, DtcWgradJob, DtcPpoCfg, DtcProfRec, DtcWimgJob, DtcH2iWJob, DtcH2iOperand, DtcWgradH2iJob, DtcEnvStep, DtcH2iFwdLayer, DtcH2iDgradLayer, DtcGruFwdItem, DtcGruBwdItem: the binding compares them with its own layouts at load time (a library
@@ -524,6 +524,57 @@ typedef struct DtcSimTilt {
 /* sizeof() of DtcSimTilt, in a table of its own (dtc_sim_abi_sizes keeps its 2 entries). */
 int dtc_sim_tilt_abi_sizes(int64_t* out, int cap);
 int dtc_sim_step_tilt(const DtcSimStep* st, const DtcSimCfg* cfg, const DtcSimTilt* tilt, int N, void* stream);
+
+/* ---- surrogate legged env with actuator lag and random pushes (opt-in) ---------------------
+ * dtc_sim_step_act is dtc_sim_step (tilt == NULL) or dtc_sim_step_tilt (tilt != NULL) under the two disturbances the reference trains
+ * every DTC policy with: the lagged PD goal of _compute_torques (legged_robot.py:608-618, :827, :248-249) and the random pushes of
+ * _push_robots (:546-553, :673-678).  Still ONE launch (two further instantiations of the same kernel), still not physics: a push here
+ * is a kinematic slip velocity of the base with a chosen exponential decay, not a contact dynamics -- the stance feet of a pushed env
+ * slide over the ground, nothing resists, nothing topples.  push_decay_s and the floor (keep, floor2 below) are free constants of
+ * the surrogate, fitted to nothing.  `forces` stay untouched (max_push_force_xy is 0 in every reference config); control types "V"
+ * and "T" stay absent.  tests/sim_actuator_oracle.py restates everything below in numpy float32, bit for bit, and is the specification.
+ *
+ * New per-env state: lag_state [N,6,12] fp32, the scaled actions of the last six substeps, slot 0 the oldest, slot 5 the newest;
+ * push_vel [N,2] fp32, the pending push in the world frame.  Both are loaded once ahead of the substeps and stored once after them.
+ * Every value is a single-rounded fp32 operation in this order; everything not named is exactly as in dtc_sim_step / dtc_sim_step_tilt.
+ * Substep `it` (0-based), ahead of step 1:
+ *   L1. lag[i] = lag[i + 1] for i = 0..4
+ *   L2. lag[5] = a * action_scale                                           (a: the clipped action of this step)
+ *   L3. with `lag` set: goal = min(max(lag[lag_choice[it]] + default, lo), hi) stands where step 1 has goal; lag_choice[it] is the
+ *       same for every env, as the reference's one np.random.randint(1, 5) per substep is; slot 5 is the current action, and
+ *       with every choice 5 the step is dtc_sim_step's bit for bit.  With `lag` clear the goal is dtc_sim_step's, and L1, L2 still run.
+ * After step 7 (and T2, T3), ahead of step 8, with the c, s of step 4, for an env with push_vel != (0, 0) (a select: an env
+ * with no pending push keeps every bit of dtc_sim_step, the sign of a zero included):
+ *   P1. vb.x = vb.x + (c * p.x + s * p.y);   vb.y = vb.y + (c * p.y - s * p.x)          (p = push_vel, rotated into the yaw frame)
+ * After step 8:
+ *   P2. p.x = p.x * keep;   p.y = p.y * keep
+ *   P3. (p.x * p.x + p.y * p.y) < floor2: p.x = p.y = 0.0f
+ * Everything downstream follows from vb without further change: x, y, root_states[7:9], base_lin_vel, the foot velocities, the ring
+ * buffers.  After the last substep, with `push_now` set (the host sets it when common_step_counter % push_interval is 0 or 1,
+ * push_interval = ceil(push_interval_s / dt), legged_robot.py:1240, :673):
+ *   N1. pv = (push_span * u[0] + push_lo, push_span * u[1] + push_lo), with u = u_push[n] in [0, 1), or with u_push == NULL the words
+ *       x, y (24 bits each) of Philox4x32-10, key = seed, counter = (n, 1, call counter) -- the command resample draws (n, 0, ..)
+ *   N2. push_vel = pv;   root_states[7:9] = pv   (as the reference overwrites the root velocity after base_lin_vel was taken:
+ *       base_lin_vel, the foot rows and the ring buffers keep this step's twist; the push acts on the base from the next step on).
+ * lag_state and push_vel are then written.  With `push` clear push_vel and u_push are not touched (they may be NULL) and no push is
+ * ever pending.  DTC_ERR_ARG before any launch: act == NULL, lag_state == NULL, push set with push_vel == NULL, a lag_choice[it]
+ * (it < decimation) outside 0..5, keep outside (0, 1], a negative floor2 or push_span; and everything dtc_sim_step refuses. */
+typedef struct DtcSimActuator {
+    float* lag_state;                /* [N,6,12], read and written                                                        */
+    float* push_vel;                 /* [N,2], read and written (NULL allowed when push == 0)                             */
+    const float* u_push;             /* [N,2] or NULL (generated); read only when push_now                                */
+    uint8_t lag_choice[64];          /* the first `decimation` entries: the slot of substep `it` (0..5)                   */
+    int32_t lag;                     /* 1: L3 takes the lagged goal                                                       */
+    int32_t push;                    /* 1: pushes are configured (push_vel is live)                                       */
+    int32_t push_now;                /* 1: this step draws a new push (needs push)                                        */
+    float keep;                      /* float32(exp(-sim_dt / push_decay_s)), in (0, 1]                                   */
+    float floor2;                    /* float32(push_floor * push_floor) [m^2/s^2] (>= 0)                                 */
+    float push_span, push_lo;        /* float32(2 * max_push_vel_xy), float32(-max_push_vel_xy)                           */
+    int32_t reserved;
+} DtcSimActuator;
+/* sizeof() of DtcSimActuator, in a table of its own (the older tables keep their entries). */
+int dtc_sim_act_abi_sizes(int64_t* out, int cap);
+int dtc_sim_step_act(const DtcSimStep* st, const DtcSimCfg* cfg, const DtcSimTilt* tilt_or_null, const DtcSimActuator* act, int N, void* stream);
 
 /* ---- DTC curriculum terrain, generated on the device (opt-in) ------------------------------
  * dtc_terrain_generate (csrc/terrain.hip) fills the int16 height table [tot_rows, tot_cols] (border included: zeros) and
