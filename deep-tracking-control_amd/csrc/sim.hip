@@ -13,9 +13,12 @@
 // disturbances: the PD goal comes from a six-slot lag buffer of scaled actions, shifted at every substep, at a slot the host draws per
 // substep for all envs (legged_robot.py:608-618), and a random planar velocity (:546-553, :673-678) that rides on the base twist as a
 // slip velocity with a chosen exponential decay -- kinematic, not a contact dynamics; its decay and floor are free constants fitted
-// to nothing.  Deliberately absent from all: attitude and base dynamics (no free flight: at least one foot is always in contact),
-// `forces` (never touched), control types "V" and "T", and the heading command's yaw law (legged_robot.py:537-539), which stays with
-// the caller.
+// to nothing.  dtc_sim_step_fly, four further instantiations (any of the above), gives the base a vertical degree of freedom: a base
+// whose support falls away falls under gravity and lands when it reaches a support, and a support that rises by more than max_step_up
+// within a substep is a crash, reported as the base's own contact force so that dtc_check_termination ends the episode; max_step_up,
+// crash_force and the take-off rule are free constants.  Without it at least one foot is always in contact.  Deliberately absent from
+// all: control types "V" and "T", `forces` (never touched), contact dynamics, anything that topples the robot, and the heading
+// command's yaw law (legged_robot.py:537-539), which stays with the caller.
 //
 // One 64-lane wavefront per env, 4 envs per 256-thread workgroup (as csrc/envstep.hip).  Lanes 0..11 own the joints (leg l owns
 // 3l..3l+2) and lane 3l+i computes component i of foot l; the twelve foot components are then broadcast with v_readlane and every lane
@@ -25,7 +28,12 @@
 // unrolled constants).  Latency bound: ~0.8 KB read and ~1.2 KB written per env (dtc_sim_step_act: ~0.3 KB more each way).
 // -ffp-contract=off (build.py): every value is one single-rounded fp32 operation in the stated order, sums over legs run in leg order
 // from 0.0f, and tests/sim_oracle.py restates the step in numpy float32 bit for bit (tests/sim_tilt_oracle.py and
-// tests/sim_actuator_oracle.py: the other instantiations).
+// tests/sim_actuator_oracle.py: the other instantiations; tests/sim_flight_oracle.py: all four with FLY).
+//
+// Resources of the eight instantiations (compiler resource-usage remarks, gfx950): VGPRs / SGPRs / SGPRs spilled to VGPR lanes / scratch
+//   yaw  60 /  98 /  0 / 0    tilt  89 / 106 /  8 / 0    yaw + act  70 / 104 / 0 / 0    tilt + act  99 / 106 / 16 / 0
+//   with FLY:  64 / 104 /  0 / 0          87 / 106 / 16 / 0               76 / 106 / 6 / 0                96 / 106 / 24 / 0
+// Scratch must stay 0 for all eight (tests/test_abi_and_host.py pins it for every kernel).
 #include <cstddef>
 
 #include "common.hpp"
@@ -93,16 +101,29 @@ __device__ __forceinline__ void tilt_rotate_t(const TiltR& R, float nx, float ny
 static_assert(offsetof(DtcSimStep, actions_in) == 0 && sizeof(DtcSimStep) % 8 == 0, "descriptor layout the late loads rely on");
 // The first parameter: the descriptor alone, or (ACT) the descriptor with the actuator's by-value struct behind it, so that the late
 // loads find both at offsets the language fixes (0 and offsetof(SimDesc<true>, a)) whatever follows in the argument list.
-template <bool ACT> struct SimDesc { DtcSimStep s; };
-template <> struct SimDesc<true> { DtcSimStep s; DtcSimActuator a; };
+// (FLY: the flight struct comes last, found alike.)
+template <bool ACT, bool FLY = false> struct SimDesc { DtcSimStep s; };
+template <> struct SimDesc<true, false> { DtcSimStep s; DtcSimActuator a; };
+template <> struct SimDesc<false, true> { DtcSimStep s; DtcSimFlight f; };
+template <> struct SimDesc<true, true> { DtcSimStep s; DtcSimActuator a; DtcSimFlight f; };
 static_assert(offsetof(SimDesc<true>, s) == 0 && offsetof(SimDesc<true>, a) % 8 == 0 && sizeof(SimDesc<false>) == sizeof(DtcSimStep),
+              "descriptor layout the late loads rely on");
+using SimDescFly = SimDesc<false, true>;
+using SimDescActFly = SimDesc<true, true>;
+static_assert(offsetof(SimDescFly, s) == 0 && offsetof(SimDescActFly, s) == 0 && offsetof(SimDescFly, f) % 8 == 0 &&
+              offsetof(SimDescActFly, f) % 8 == 0 && offsetof(SimDescActFly, a) == offsetof(SimDesc<true>, a),
               "descriptor layout the late loads rely on");
 // TILT = false is dtc_sim_step, the yaw-only base; TILT = true is dtc_sim_step_tilt: the body z-axis n (yaw frame) lives in the
 // quaternion between steps and in three registers through the loop, and r = Rt p, sv = Rt u stand where the yaw-only step has p, u.
 // ACT = true is dtc_sim_step_act (either base): the PD goal comes from the six-slot lag buffer of scaled actions, which lanes 0..11
 // hold in registers through the loop, and a pending push (two wave-uniform registers) rides on the base twist and decays.
-template <bool TILT, bool ACT>
-__global__ __launch_bounds__(256) void sim_step_kernel(const SimDesc<ACT> d, const SimK k, int N) {
+// FLY = true is dtc_sim_step_fly (any of the four above): the base has a vertical degree of freedom.  Its z velocity, its world-frame
+// planar velocity and its yaw rate are carried from substep to substep (between calls: in root_states[7:10] and [12]); a substep
+// whose ballistic candidate stays clear of the support is airborne, every other one is grounded and computed as without FLY.  The
+// grounded values are always computed and an airborne env takes the carried ones by selects, so no division by a contact count of
+// zero reaches an output and a grounded env keeps the arithmetic of the other instantiations.
+template <bool TILT, bool ACT, bool FLY>
+__global__ __launch_bounds__(256) void sim_step_kernel(const SimDesc<ACT, FLY> d, const SimK k, int N) {
     const DtcSimStep& s = d.s;
     const int lane = threadIdx.x & 63;
     const int n = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
@@ -163,6 +184,9 @@ __global__ __launch_bounds__(256) void sim_step_kernel(const SimDesc<ACT> d, con
 
     float tau = 0.f, p[4][3], u[4][3], w = 0.f, vbx = 0.f, vby = 0.f, vz = 0.f, nc = 0.f;
     bool ct[4];
+    float Vwx = 0.f, Vwy = 0.f, gdt = 0.f;                                         // FLY: the carried planar velocity (world), g * dt
+    bool air = false, crashed = false;
+    if constexpr (FLY) Vwx = rs[7], Vwy = rs[8], vz = rs[9], w = rs[12], gdt = d.f.gravity * k.dt;
 #pragma unroll
     for (int l = 0; l < 4; ++l) {
         ct[l] = false;
@@ -243,9 +267,11 @@ __global__ __launch_bounds__(256) void sim_step_kernel(const SimDesc<ACT> d, con
                 num = num + (dpx * duy - dpy * dux);
                 den = den + (dpx * dpx + dpy * dpy);
             }
+        const float w_air = w;                                                     // FLY: the yaw rate an airborne substep keeps
         w = den > k.rmin2 ? -(num / den) : 0.0f;
         vbx = (-umx) + w * pmy;
         vby = (-umy) - w * pmx;
+        const float n_air[3] = {nx, ny, nz};                                       // FLY: the tilt an airborne substep keeps
         if constexpr (TILT) {
             // the new tilt.  Stance legs: those extended to within eps of the most extended one (body frame: the legs the env stands
             // on, whether or not the current plane has them on the ground).  Centred least squares of d_l = h_l - p_l.z =
@@ -296,10 +322,38 @@ __global__ __launch_bounds__(256) void sim_step_kernel(const SimDesc<ACT> d, con
             vby = pushed ? ay : vby;
         }
         // 8. integrate the base
-        x = x + (c * vbx - sn * vby) * k.dt;
-        y = y + (sn * vbx + c * vby) * k.dt;
-        vz = (bz - z) / k.dt;
-        z = bz;
+        if constexpr (FLY) {
+            // F1 the ballistic candidate, F2 the airborne test, F3 the take-off velocity of a grounded substep, F4 the crash,
+            // F5 the selects (include/dtc_hip.h)
+            const float vzb = vz - gdt;
+            const float zb = z + vzb * k.dt;
+            air = (zb - bz) > k.eps;
+            float suz = 0.f;
+#pragma unroll
+            for (int l = 0; l < 4; ++l)
+                if (ct[l]) suz = suz + sv[l][2];
+            const float vzg = -(suz / nc);
+            crashed = crashed || (!air && (bz - z) > d.f.max_step_up && elen != 1);
+            const float gx = c * vbx - sn * vby, gy = sn * vbx + c * vby;
+            Vwx = air ? Vwx : gx, Vwy = air ? Vwy : gy;
+            w = air ? w_air : w;
+            vz = air ? vzb : vzg;
+            z = air ? zb : bz;
+            nc = air ? 0.0f : nc;
+#pragma unroll
+            for (int l = 0; l < 4; ++l) ct[l] = ct[l] && !air;
+            if constexpr (TILT) {
+                nx = air ? n_air[0] : nx, ny = air ? n_air[1] : ny, nz = air ? n_air[2] : nz;
+                wx = air ? 0.0f : wx, wy = air ? 0.0f : wy;
+            }
+            x = x + Vwx * k.dt;
+            y = y + Vwy * k.dt;
+        } else {
+            x = x + (c * vbx - sn * vby) * k.dt;
+            y = y + (sn * vbx + c * vby) * k.dt;
+            vz = (bz - z) / k.dt;
+            z = bz;
+        }
         const float ee = k.half_dt * w;
         const float zn = qz + ee * qw, wn = qw - ee * qz;
         const float rq = sqrtf(zn * zn + wn * wn);
@@ -318,11 +372,19 @@ __global__ __launch_bounds__(256) void sim_step_kernel(const SimDesc<ACT> d, con
     unsigned long long args = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(args));
     const __attribute__((address_space(4))) DtcSimStep* o = (const __attribute__((address_space(4))) DtcSimStep*)args;
+    using DescFly = SimDesc<ACT, true>;
+    constexpr size_t fly_at = offsetof(DescFly, f);                                // FLY: where the flight struct lies in the segment
     const int C = k.C, T = k.T;
     const float cmd_old = lane < C ? o->commands[e * C + lane] : 0.f;               // the commands as they stand (cmd_buffer[-1])
     const float c = 1.0f - 2.0f * (qz * qz), sn = 2.0f * (qz * qw);
-    const float Vx = c * vbx - sn * vby, Vy = sn * vbx + c * vby;
-    const float fz = k.weight / nc;
+    float Vx = c * vbx - sn * vby, Vy = sn * vbx + c * vby;
+    float fz = k.weight / nc;
+    if constexpr (FLY) {                                                           // airborne: the carried world velocity, seen from the new yaw
+        const float ax = c * Vwx + sn * Vwy, ay = c * Vwy - sn * Vwx;
+        Vx = air ? Vwx : Vx, Vy = air ? Vwy : Vy;
+        vbx = air ? ax : vbx, vby = air ? ay : vby;
+        fz = air ? 0.0f : fz;
+    }
     // ACT: a new push (the host's flag, legged_robot.py:546-553, :673-678) is the pending push of the next step and overwrites the
     // root's planar velocity, after base_lin_vel and the foot velocities took the old one.  Every lane draws the same two values.
     float rvx = Vx, rvy = Vy;
@@ -418,7 +480,16 @@ __global__ __launch_bounds__(256) void sim_step_kernel(const SimDesc<ACT> d, con
         float v = 0.f;
 #pragma unroll
         for (int l = 0; l < 4; ++l) v = (i == k.feet[l] * 3 + 2 && ct[l]) ? fz : v;
+        if constexpr (FLY) {                                                       // a crash: the base's own contact force (body 0, z)
+            const __attribute__((address_space(4))) DtcSimFlight* of = (const __attribute__((address_space(4))) DtcSimFlight*)(args + fly_at);
+            v = (crashed && i == 2) ? of->crash_force : v;
+        }
         o->contact_forces[e * k.B * 3 + i] = v;
+    }
+    if constexpr (FLY) {
+        const __attribute__((address_space(4))) DtcSimFlight* of = (const __attribute__((address_space(4))) DtcSimFlight*)(args + fly_at);
+        if (lane == 0) of->airborne[e] = air ? 1 : 0;
+        if (lane == 1) of->crashed[e] = crashed ? 1 : 0;
     }
 
     // ---- bookkeeping, in the reference's order: episode length, the ring buffers [T, N, .] (each env shifts its own T entries:
@@ -496,9 +567,16 @@ extern "C" int dtc_sim_act_abi_sizes(int64_t* out, int cap) {
     return 1;
 }
 
-// dtc_sim_step (tilt == nullptr), dtc_sim_step_tilt and dtc_sim_step_act (act != nullptr, either base): one validation, one
-// descriptor, the four instantiations of one kernel
-static int sim_step_launch(const DtcSimStep* st, const DtcSimCfg* cfg, const DtcSimTilt* tilt, const DtcSimActuator* act, int N, void* stream) {
+extern "C" int dtc_sim_fly_abi_sizes(int64_t* out, int cap) {
+    const int64_t sz[] = {sizeof(DtcSimFlight)};
+    if (cap > 0 && out) out[0] = sz[0];
+    return 1;
+}
+
+// dtc_sim_step (tilt == nullptr), dtc_sim_step_tilt, dtc_sim_step_act (act != nullptr, either base) and dtc_sim_step_fly
+// (fly != nullptr, any of the four): one validation, one descriptor, the eight instantiations of one kernel
+static int sim_step_launch(const DtcSimStep* st, const DtcSimCfg* cfg, const DtcSimTilt* tilt, const DtcSimActuator* act, const DtcSimFlight* fly,
+                           int N, void* stream) {
     DTC_REQUIRE(st && cfg, "null descriptor");
     DTC_REQUIRE(N > 0 && N <= (1 << 24), "N %d outside 1..2^24", N);
     const DtcSimStep& s = *st;
@@ -550,32 +628,60 @@ static int sim_step_launch(const DtcSimStep* st, const DtcSimCfg* cfg, const Dtc
         DTC_REQUIRE(act->floor2 >= 0.f && act->push_span >= 0.f, "negative push floor %g or span %g", (double)act->floor2, (double)act->push_span);
     }
 
+    if (fly) {                                                                     // comparisons written so that a NaN is refused
+        DTC_REQUIRE(fly->airborne && fly->crashed, "null airborne / crashed");
+        DTC_REQUIRE(fly->gravity >= 0.f && fly->max_step_up > 0.f, "gravity %g < 0 or max_step_up %g <= 0", (double)fly->gravity,
+                    (double)fly->max_step_up);
+        DTC_REQUIRE(fly->crash_force > 100.f, "crash_force %g not above the termination threshold of 100 N", (double)fly->crash_force);
+        for (int l = 0; l < 4; ++l) DTC_REQUIRE(c.feet[l] != 0, "leg %d: foot body 0 is the base, which takes the crash force", l);
+    }
+
     hipStream_t hs = (hipStream_t)stream;
     const dim3 grid((unsigned)dtc::ceil_div(N, 4)), block(256);
+    if (fly) {
+        const char* name = act ? (tilt ? "sim_step_tilt_act_fly" : "sim_step_act_fly") : (tilt ? "sim_step_tilt_fly" : "sim_step_fly");
+        dtc::ProfScope prof(name, (double)N * (2050.0 + 12.0 * c.num_bodies + 8.0 * c.buffer_len * (3 + c.num_commands) + (act ? 592.0 : 0.0)), hs);
+        if (act) {
+            const SimDesc<true, true> d{s, *act, *fly};
+            if (tilt) hipLaunchKernelGGL((sim_step_kernel<true, true, true>), grid, block, 0, hs, d, k, N);
+            else hipLaunchKernelGGL((sim_step_kernel<false, true, true>), grid, block, 0, hs, d, k, N);
+        } else {
+            const SimDesc<false, true> d{s, *fly};
+            if (tilt) hipLaunchKernelGGL((sim_step_kernel<true, false, true>), grid, block, 0, hs, d, k, N);
+            else hipLaunchKernelGGL((sim_step_kernel<false, false, true>), grid, block, 0, hs, d, k, N);
+        }
+        return dtc::check_launch(name);
+    }
     const char* name = act ? (tilt ? "sim_step_tilt_act" : "sim_step_act") : (tilt ? "sim_step_tilt" : "sim_step");
     dtc::ProfScope prof(name, (double)N * (2048.0 + 12.0 * c.num_bodies + 8.0 * c.buffer_len * (3 + c.num_commands) + (act ? 592.0 : 0.0)), hs);
     if (act) {
         const SimDesc<true> d{s, *act};
-        if (tilt) hipLaunchKernelGGL((sim_step_kernel<true, true>), grid, block, 0, hs, d, k, N);
-        else hipLaunchKernelGGL((sim_step_kernel<false, true>), grid, block, 0, hs, d, k, N);
+        if (tilt) hipLaunchKernelGGL((sim_step_kernel<true, true, false>), grid, block, 0, hs, d, k, N);
+        else hipLaunchKernelGGL((sim_step_kernel<false, true, false>), grid, block, 0, hs, d, k, N);
     } else {
         const SimDesc<false> d{s};
-        if (tilt) hipLaunchKernelGGL((sim_step_kernel<true, false>), grid, block, 0, hs, d, k, N);
-        else hipLaunchKernelGGL((sim_step_kernel<false, false>), grid, block, 0, hs, d, k, N);
+        if (tilt) hipLaunchKernelGGL((sim_step_kernel<true, false, false>), grid, block, 0, hs, d, k, N);
+        else hipLaunchKernelGGL((sim_step_kernel<false, false, false>), grid, block, 0, hs, d, k, N);
     }
     return dtc::check_launch(name);
 }
 
 extern "C" int dtc_sim_step(const DtcSimStep* st, const DtcSimCfg* cfg, int N, void* stream) {
-    return sim_step_launch(st, cfg, nullptr, nullptr, N, stream);
+    return sim_step_launch(st, cfg, nullptr, nullptr, nullptr, N, stream);
 }
 
 extern "C" int dtc_sim_step_tilt(const DtcSimStep* st, const DtcSimCfg* cfg, const DtcSimTilt* tilt, int N, void* stream) {
     DTC_REQUIRE(tilt, "null DtcSimTilt");
-    return sim_step_launch(st, cfg, tilt, nullptr, N, stream);
+    return sim_step_launch(st, cfg, tilt, nullptr, nullptr, N, stream);
 }
 
 extern "C" int dtc_sim_step_act(const DtcSimStep* st, const DtcSimCfg* cfg, const DtcSimTilt* tilt, const DtcSimActuator* act, int N, void* stream) {
     DTC_REQUIRE(act, "null DtcSimActuator");
-    return sim_step_launch(st, cfg, tilt, act, N, stream);
+    return sim_step_launch(st, cfg, tilt, act, nullptr, N, stream);
+}
+
+extern "C" int dtc_sim_step_fly(const DtcSimStep* st, const DtcSimCfg* cfg, const DtcSimTilt* tilt, const DtcSimActuator* act, const DtcSimFlight* fly,
+                                int N, void* stream) {
+    DTC_REQUIRE(fly, "null DtcSimFlight");
+    return sim_step_launch(st, cfg, tilt, act, fly, N, stream);
 }

@@ -22,6 +22,13 @@ curriculum of reset_idx runs on state that evolves.  What this is NOT: the surro
 hole is simply out of contact, and an env whose four feet are all over a gap drops to the gap floor kinematically and climbs the far
 wall in one step -- there is no falling, no collision with a wall and no getting stuck; the terrain shapes the footholds, the height
 scan, the rewards and the curriculum, not a contact dynamics.
+
+`SimConfig.flight` (opt-in, a `sim.FlightConfig`; None: the env above, bit for bit, nothing new allocated) changes exactly that, in
+the same launch (`dtc_sim_step_fly`): a base whose support falls away falls under gravity and lands when it reaches a support, and a
+support that rises by more than `max_step_up` within a substep is a crash.  The env then owns `airborne` and `crashed` [N] uint8.
+Nothing else in `step()` changes: a crash reaches `reset_buf` through the base's contact force and check_termination, as a fall does
+in the reference, and a base that falls into a gap terminates through the existing base-height rule.  Still a surrogate: the
+flight is a point mass on a parabola, `max_step_up`, `crash_force` and the take-off rule are choices, and nothing topples.
 """
 from __future__ import annotations
 
@@ -165,6 +172,8 @@ class SurrogateLeggedEnv(VecEnv):
             self.lag_state, self.push_vel, self.common_step_counter = z(N, 6, D), z(N, 2), 0
             self.lag_buffer = [self.lag_state[:, i] for i in range(6)]
             self._actuator_rows = (self.lag_state, self.push_vel)
+        if s.flight is not None:
+            self.airborne, self.crashed = torch.zeros(N, dtype=torch.uint8, device=dev), torch.zeros(N, dtype=torch.uint8, device=dev)
         self.last_contacts = torch.zeros(N, 4, dtype=torch.bool, device=dev)
         self.contact_filt = torch.zeros(N, 4, dtype=torch.bool, device=dev)
         self.robot_mass = torch.full((N,), float(s.mass), **f)

@@ -1,13 +1,16 @@
-"""Host side of the surrogate legged env step (csrc/sim.hip, `dtc_sim_step`, `dtc_sim_step_tilt`, `dtc_sim_step_act`): the state the env kernels run
+"""Host side of the surrogate legged env step (csrc/sim.hip, `dtc_sim_step`, `dtc_sim_step_tilt`, `dtc_sim_step_act`, `dtc_sim_step_fly`): the state the env kernels run
 on when no simulator stands behind them.  One launch per env step stands where the reference calls Isaac Gym: `decimation` substeps
 of the PD law of LeggedRobot._compute_torques (control type "P"), a kinematic quadruped that rides on its stance feet over the int16
 terrain table, and the bookkeeping of post_physics_step up to the planner.  include/dtc_hip.h states every operation; it is a
-surrogate, not physics (no attitude or base dynamics, no free flight, no "V" / "T" control, no heading yaw law).  By default the
+surrogate, not physics (no attitude or contact dynamics, no "V" / "T" control, no heading yaw law; no free flight unless
+`SimConfig.flight` is set).  By default the
 base only yaws; `SimConfig.tilt` (opt-in) lets its roll and pitch follow the support points of the stance feet, still kinematically:
 after a reset the identity quaternion then gives one step with a tilt-rate spike.  `SimConfig.actuator` (opt-in, an
 `ActuatorConfig`) adds the two disturbances the reference trains under: the PD goal taken from a six-slot lag buffer of scaled
 actions at a slot the host draws per substep, and random pushes -- here a kinematic slip velocity of the base with a chosen decay,
-not a contact dynamics.
+not a contact dynamics.  `SimConfig.flight` (opt-in, a `FlightConfig`) gives the base a vertical degree of freedom: a base whose support
+falls away falls under gravity and lands when it reaches a support, and a support that rises by more than a climbable step is a
+crash that ends the episode through the base contact force.
 
 `SimConfig` holds the constants (Lite3 DTC values), `leg_tables(config)` the three small tables computed once in float64 from a
 two-link leg linearised at the default pose, and `SimStep` runs the launch on an env's own tensors (attribute names as in
@@ -33,6 +36,7 @@ _ENV_TENSORS = dict(Kp_factors=("D", torch.float32), Kd_factors=("D", torch.floa
                     projected_gravity=(3, torch.float32), base_pos=(3, torch.float32), base_quat=(4, torch.float32),
                     contact_filt=(4, torch.bool))
 _RING_BUFFERS = dict(lin_vel_buffer=2, ang_vel_buffer=1, cmd_buffer="C")
+TERMINATION_FORCE = 100.0       # N: the contact-force threshold of dtc_check_termination (legged_robot_dtc.py:229-248)
 
 
 @dataclass
@@ -58,6 +62,29 @@ class ActuatorConfig:
             raise ValueError(f"ActuatorConfig: lag_slots {self.lag_slots} outside 0..5")
         if not (self.push_interval_s > 0 and self.push_decay_s > 0 and self.max_push_vel_xy >= 0 and self.push_floor >= 0):
             raise ValueError("ActuatorConfig: push_interval_s and push_decay_s must be positive, max_push_vel_xy and push_floor not negative")
+
+
+@dataclass
+class FlightConfig:
+    """Free flight, landing and wall crashes of `dtc_sim_step_fly` (include/dtc_hip.h states the operations).  A substep whose
+    ballistic candidate (z velocity less `gravity` * sim_dt) stays more than contact_eps clear of the support is airborne; any other
+    is grounded as without flight, and leaves the base the z velocity its stance legs give it.  A grounded substep whose support
+    rises by more than `max_step_up` [m] is a crash: the base takes the contact force `crash_force` [N], which must exceed the
+    termination threshold (100 N), so check_termination ends the episode as it ends a fall in the reference.  `max_step_up` and
+    `crash_force` are free constants of the surrogate, chosen, not fitted to anything (and so is the take-off rule): 0.3 m lies
+    above every stair (0.18 m) and obstacle (0.2 m) the terrain generator makes and below a gap or a deep pit wall; 200 N is
+    twice the threshold."""
+    gravity: float = 9.81
+    max_step_up: float = 0.3
+    crash_force: float = 200.0
+
+    def validate(self):
+        if not (self.gravity >= 0 and math.isfinite(self.gravity)):
+            raise ValueError(f"FlightConfig: gravity {self.gravity} must be finite and not negative")
+        if not (self.max_step_up > 0 and math.isfinite(self.max_step_up)):
+            raise ValueError(f"FlightConfig: max_step_up {self.max_step_up} must be positive and finite")
+        if not (self.crash_force > TERMINATION_FORCE and math.isfinite(self.crash_force)):
+            raise ValueError(f"FlightConfig: crash_force {self.crash_force} must exceed the termination threshold of {TERMINATION_FORCE} N")
 
 
 @dataclass
@@ -101,6 +128,7 @@ class SimConfig:
     # of that size 1e-10.
     min_det: float = 1e-6
     actuator: ActuatorConfig | None = None   # lag buffer and pushes (dtc_sim_step_act); None: the entry points above, bit for bit
+    flight: FlightConfig | None = None       # free flight, landing, crashes (dtc_sim_step_fly); None: the entry points above, bit for bit
 
     @property
     def dt(self) -> float:
@@ -159,7 +187,9 @@ class SimStep:
     tensors of `env`; with `u_cmd` left out the kernel draws the command resamples itself (Philox, keyed by `seed` and a call
     counter).  With `config.actuator` the launch is `dtc_sim_step_act` on the env's `lag_state` [N,6,12] and `push_vel` [N,2] as
     well: `lag_choice` (`decimation` slots; left out: drawn from a RandomState(seed) this object owns, as the reference draws on
-    the host), `push` (the env's flag: this step draws a new push) and `u_push` [N,2] (left out: the kernel's Philox)."""
+    the host), `push` (the env's flag: this step draws a new push) and `u_push` [N,2] (left out: the kernel's Philox).  With
+    `config.flight` the launch is `dtc_sim_step_fly` (on whichever of the above the config asks for) and writes the env's `airborne`
+    and `crashed` [N] uint8 as well."""
 
     def __init__(self, num_envs: int, device, config: SimConfig, height_samples: torch.Tensor, *, seed: int = 0, tables: dict | None = None):
         dev = torch.device(device)
@@ -176,6 +206,8 @@ class SimStep:
         if config.actuator is not None:
             config.actuator.validate()
             self._lag_rng = np.random.RandomState(self.seed)
+        if config.flight is not None:
+            config.flight.validate()
 
     def cfg_struct(self) -> "_ffi.DtcSimCfg":
         k, c = self.cfg, _ffi.DtcSimCfg()
@@ -247,6 +279,7 @@ class SimStep:
         c = self.cfg_struct()
         tilt = _ffi.DtcSimTilt(float(k.max_slope), float(k.min_det)) if k.tilt else None
         drew_push = False
+        act = None
         if k.actuator is not None:
             act = self.act_struct(lag_choice, push)
             self._check("lag_state", env.lag_state, (N, 6, 12), torch.float32)
@@ -258,6 +291,14 @@ class SimStep:
                     self._check("u_push", u_push, (N, 2), torch.float32)
                     act.u_push = _ffi.ptr(u_push)
                 drew_push = bool(act.push_now) and u_push is None
+        if k.flight is not None:
+            f = k.flight
+            fly = _ffi.DtcSimFlight(float(f.gravity), float(f.max_step_up), float(f.crash_force))
+            for name in ("airborne", "crashed"):
+                self._check(name, getattr(env, name), (N,), torch.uint8)
+                setattr(fly, name, _ffi.ptr(getattr(env, name)))
+            _ffi.check(_ffi.lib().dtc_sim_step_fly(s, c, tilt, act, fly, N, _ffi.stream()), "dtc_sim_step_fly")
+        elif act is not None:
             _ffi.check(_ffi.lib().dtc_sim_step_act(s, c, tilt, act, N, _ffi.stream()), "dtc_sim_step_act")
         elif k.tilt:
             _ffi.check(_ffi.lib().dtc_sim_step_tilt(s, c, tilt, N, _ffi.stream()), "dtc_sim_step_tilt")

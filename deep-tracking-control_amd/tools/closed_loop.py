@@ -9,6 +9,8 @@
                                                                           # the rough table beside the generated DTC terrain
     python deep-tracking-control_amd/tools/closed_loop.py --actuator [--out profiles/closed_loop_actuator.txt]
                                                                           # the env beside the env with actuator lag and pushes
+    python deep-tracking-control_amd/tools/closed_loop.py --flight [--out profiles/closed_loop_flight.txt]
+                                                                          # the terrain env beside the one with free flight and crashes
 
 Per run and iteration: the mean step reward (mean of rew_buf over the iteration's 24 steps and all envs), the mean episode length
 (the runner's tracker: the last <= 100 finished episodes; "-" before the first one ends) and the mean length of the episodes in flight.
@@ -27,6 +29,10 @@ as one column, the mean terrain level and the share of envs reset per step per f
 With --actuator the two runs are the yaw-only env over the rough table without and with `SimConfig(actuator=ActuatorConfig())` (the
 reference's lag range and push schedule), default arithmetic, the same three interleaved rounds; dtc_sim_step beside
 dtc_sim_step_act, alternating; and the mean step reward per iteration of both, for which nothing was tuned.
+With --flight the two runs are the env on the generated DTC terrain (the Lite3 grid) without and with
+`SimConfig(flight=FlightConfig())`, default arithmetic, the same three interleaved rounds; dtc_sim_step beside dtc_sim_step_fly on
+that terrain, alternating; and, on a 6 x 9 grid that holds every family as one column, the share of envs airborne, crashed and
+reset per step per family over 200 steps of an untrained policy.  Nothing is asserted and nothing was tuned.
 """
 import argparse
 import os
@@ -54,12 +60,13 @@ def rough_env(num_envs, tilt, actuator=None):
     return SurrogateLeggedEnv(num_envs, DEV, SurrogateConfig(sim=SIM.SimConfig(tilt=tilt, actuator=actuator)), synthetic.reward_table(), seed=5)
 
 
-def make(num_envs, algo, seed=11, tilt=None, terrain=None, steps=STEPS, actuator=None):
+def make(num_envs, algo, seed=11, tilt=None, terrain=None, steps=STEPS, actuator=None, flight=None):
     """`tilt` None: the default env on the flat table; False / True: the yaw-only / the tilt env on the rough table (`actuator`, an
-    ActuatorConfig: with lag and pushes); `terrain`, a TerrainConfig: the env on the generated terrain."""
+    ActuatorConfig: with lag and pushes); `terrain`, a TerrainConfig: the env on the generated terrain (`flight`, a FlightConfig: with
+    free flight, landing and crashes)."""
     torch.manual_seed(seed)
     if terrain is not None:
-        env = SurrogateLeggedEnv(num_envs, DEV, SurrogateConfig(terrain=terrain), seed=5)
+        env = SurrogateLeggedEnv(num_envs, DEV, SurrogateConfig(sim=SIM.SimConfig(flight=flight), terrain=terrain), seed=5)
     else:
         env = SurrogateLeggedEnv(num_envs, DEV, SurrogateConfig(), seed=5) if tilt is None else rough_env(num_envs, tilt, actuator)
     runner = dict(policy_class_name="ActorCriticDecoder", algorithm_class_name="PPO", num_steps_per_env=steps, save_interval=10 ** 9)
@@ -107,8 +114,8 @@ def timed(fn, acc):
     return f
 
 
-def timing_round(num_envs, iters, algo, tilt=None, terrain=None, actuator=None):
-    r, env = make(num_envs, algo, tilt=tilt, terrain=terrain, actuator=actuator)
+def timing_round(num_envs, iters, algo, tilt=None, terrain=None, actuator=None, flight=None):
+    r, env = make(num_envs, algo, tilt=tilt, terrain=terrain, actuator=actuator, flight=flight)
     r.learn(2)                                                # warm-up: allocations, first launches
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -322,6 +329,85 @@ def actuator_report(args):
     return lines
 
 
+def flight_probe(num_envs, calls):
+    """dtc_sim_step beside dtc_sim_step_fly on the generated Lite3 terrain, same actions, alternating: us per call (median), and the
+    share of envs the flight env has in the air at the end."""
+    envs = [SurrogateLeggedEnv(num_envs, DEV, SurrogateConfig(sim=SIM.SimConfig(flight=f), terrain=TerrainConfig(seed=1)), seed=5)
+            for f in (None, SIM.FlightConfig())]
+    g = torch.Generator(device=DEV).manual_seed(3)
+    for e in envs:
+        e.reset()
+    acc = ([], [])
+    for i in range(calls + 20):
+        a, u = torch.randn(num_envs, 12, generator=g, device=DEV), torch.rand(num_envs, 3, generator=g, device=DEV)
+        for t, e in zip(acc, envs):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            e.sim.step(e, a, u)
+            torch.cuda.synchronize()
+            if i >= 20:
+                t.append(1e6 * (time.perf_counter() - t0))
+    return statistics.median(acc[0]), statistics.median(acc[1]), float(envs[1].airborne.float().mean())
+
+
+def flight_family_probe(num_envs, steps=200, rollout=25):
+    """An untrained policy on a 6 x 9 grid whose column j is family j, with flight: per family the share of its envs airborne (at the
+    end of the step), crashed and reset per step, and the mean terrain level at the start and at the end.  Rollouts without updates;
+    everything is summed on the device and read once."""
+    cfg = TerrainConfig(num_rows=6, num_cols=9, terrain_proportions=tuple([1 / 9] * 9), seed=1)
+    r, env = make(num_envs, {}, terrain=cfg, steps=rollout, flight=SIM.FlightConfig())
+    types = env.terrain_types
+    count = torch.bincount(types, minlength=9).double()
+    level0 = torch.zeros(9, dtype=torch.float64, device=DEV).index_add_(0, types, env.terrain_levels.double()) / count
+    sums = torch.zeros(3, 9, dtype=torch.float64, device=DEV)
+    inner = r.env.step
+
+    def step(actions):
+        out = inner(actions)
+        for row, flag in zip(sums, (env.airborne, env.crashed, out[2])):
+            row.index_add_(0, types, flag.double())
+        return out
+    object.__setattr__(r.env, "step", step)
+    state = dict(obs_dict=r.env.get_observations(), rew_buf=r.env.get_reward_buf())
+    for _ in range(steps // rollout):
+        r._collect(state, None, [])
+        r.alg.storage.clear()
+    level1 = torch.zeros(9, dtype=torch.float64, device=DEV).index_add_(0, types, env.terrain_levels.double()) / count
+    return (sums / count / (steps // rollout * rollout)).tolist(), level0.tolist(), level1.tolist(), count.tolist()
+
+
+def flight_report(args):
+    lite3 = TerrainConfig(seed=1)
+    runs = (("no flight", None), ("flight", SIM.FlightConfig()))
+    rounds = {tag: [] for tag, _ in runs}
+    for _ in range(3):
+        for tag, f in runs:
+            rounds[tag].append(timing_round(args.envs, args.iters, {}, terrain=lite3, flight=f))
+    lines = [f"closed loop on SurrogateLeggedEnv on the generated DTC terrain (the Lite3 grid), without and with SimConfig(flight=FlightConfig()) "
+             f"(gravity 9.81, max_step_up 0.3 m, crash_force 200 N): {args.envs} envs x {STEPS} steps per iteration, {args.iters} iterations, PPO, "
+             f"default arithmetic, fixed seeds",
+             "", "three interleaved rounds, median (min .. max):"]
+    for tag, _ in runs:
+        rs = rounds[tag]
+        lines.append(f"  {tag:11s} env-steps/s, whole loop {spread([r['steps_per_s'] for r in rs], '{:.0f}')}")
+        lines.append(f"  {'':11s} ms per iteration, each call closed by a synchronise: env.step x{STEPS} {spread([r['env_ms'] for r in rs], '{:.2f}')}"
+                     f" | act() x{STEPS} {spread([r['act_ms'] for r in rs], '{:.2f}')} | update() {spread([r['update_ms'] for r in rs], '{:.2f}')}")
+    probes = [flight_probe(args.envs, args.calls) for _ in range(3)]
+    lines += ["", f"one surrogate step at {args.envs} envs on that terrain, us per call (host clock, closed by a synchronise), alternating, three rounds:",
+              f"  dtc_sim_step      {spread([p[0] for p in probes])}",
+              f"  dtc_sim_step_fly  {spread([p[1] for p in probes])}   (envs in the air at the end, under random actions: "
+              f"{100 * statistics.mean(p[2] for p in probes):.1f} %)"]
+    share, level0, level1, count = flight_family_probe(args.envs)
+    lines += ["", f"an untrained policy with flight, {args.envs} envs on a 6 x 9 grid (column j = family j, max_init_terrain_level 5), 200 steps, no update;",
+              "per step, the share of a family's envs that end it airborne, that crashed in it, and that were reset in it:",
+              "  family              envs   airborne   crashed   reset     mean terrain_level start -> end"]
+    for j, name in enumerate(FAMILIES):
+        lines.append(f"  {name:19s} {int(count[j]):5d}   {100 * share[0][j]:6.2f} %   {100 * share[1][j]:5.2f} %   {100 * share[2][j]:5.2f} %   "
+                     f"{level0[j]:.3f} -> {level1[j]:.3f}")
+    lines += ["", "bench.py runs no env step: its headline is not re-measured here."]
+    return lines
+
+
 ALL_FAMILIES = (0.1, 0.1, 0.1, 0.1, 0.15, 0.15, 0.1, 0.1, 0.1)
 
 
@@ -415,10 +501,12 @@ def main():
     ap.add_argument("--tilt", action="store_true")
     ap.add_argument("--terrain", action="store_true")
     ap.add_argument("--actuator", action="store_true")
+    ap.add_argument("--flight", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if args.tilt or args.terrain or args.actuator:
-        text = "\n".join((tilt_report if args.tilt else terrain_report if args.terrain else actuator_report)(args)) + "\n"
+    if args.tilt or args.terrain or args.actuator or args.flight:
+        report = tilt_report if args.tilt else terrain_report if args.terrain else actuator_report if args.actuator else flight_report
+        text = "\n".join(report(args)) + "\n"
         print(text)
         if args.out:
             with open(args.out, "w") as f:

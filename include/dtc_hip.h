@@ -387,8 +387,9 @@ int dtc_env_reset(const DtcResetStep* st, const DtcResetCfg* cfg, int N, void* s
  * one wavefront per env, each env row loaded once and stored once.  It is a surrogate, not physics: state that is consistent,
  * evolves, responds to actions and can terminate.  In dtc_sim_step the base only yaws (the quaternion keeps x = y = 0,
  * projected_gravity is (0, 0, -1)); dtc_sim_step_tilt, below, adds a kinematic roll and pitch.  Absent on purpose from both:
- * attitude and base dynamics (no free flight: the base rides on its stance feet), lag buffers, pushes (`forces` are not
- * touched), control types "V" and "T", and the heading command's yaw law (legged_robot.py:537-539 stays with the caller).
+ * attitude and base dynamics (the base rides on its stance feet; free flight, landing and crashes: dtc_sim_step_fly, below), lag
+ * buffers and pushes (dtc_sim_step_act, below; `forces` are never touched), control types "V" and "T", contact dynamics, anything
+ * that topples the robot, and the heading command's yaw law (legged_robot.py:537-539 stays with the caller).
  *
  * Every value is a single-rounded fp32 operation in the order below (-ffp-contract=off; tests/sim_oracle.py restates it in numpy
  * float32, bit for bit).  Joint j = 3 l + k is joint k of leg l; sums over legs run in leg order 0..3 from 0.0f.  Once per step:
@@ -575,6 +576,53 @@ typedef struct DtcSimActuator {
 /* sizeof() of DtcSimActuator, in a table of its own (the older tables keep their entries). */
 int dtc_sim_act_abi_sizes(int64_t* out, int cap);
 int dtc_sim_step_act(const DtcSimStep* st, const DtcSimCfg* cfg, const DtcSimTilt* tilt_or_null, const DtcSimActuator* act, int N, void* stream);
+
+/* ---- surrogate legged env with free flight, landing and wall crashes (opt-in) --------------
+ * dtc_sim_step_fly is any of the four steps above (tilt_or_null, act_or_null) with a vertical degree of freedom of the base: a base
+ * whose support falls away falls under gravity, lands when it reaches a support, and a support that rises by more than max_step_up
+ * within one substep is a collision that ends the episode through the reference's own rule, a base contact force above the
+ * termination threshold (dtc_check_termination: 100 N).  Still ONE launch (four further instantiations of the same kernel), still not
+ * physics: the flight is a point mass on a parabola, a landing dissipates whatever velocity the base arrives with, nothing tumbles.
+ * The take-off rule F3, max_step_up and crash_force are choices of the surrogate, fitted to nothing.  Still absent: control types
+ * "V" and "T", `forces`, contact dynamics (stance feet neither slip under load nor push back), and anything that topples the robot.
+ * tests/sim_flight_oracle.py restates everything below in numpy float32, bit for bit, and is the specification.
+ *
+ * Carried state, no new fp32 tensor: vz, the base's z velocity, V = (V.x, V.y), its planar velocity in the world frame, and w, its yaw
+ * rate.  At the first substep of a call they are root_states[9], root_states[7:9] and root_states[12]; the step writes them back there.
+ * fresh = (episode_length_buf == 0 on entry): the step after a reset, which places the base on its support as dtc_sim_step does.
+ * Every value is a single-rounded fp32 operation in this order; everything not named is exactly as in the step underneath.
+ * One substep: steps 1..7 (T1..T3, L1..L3, P1) run as stated above and give base_z, contact_l, n_c, sv_l (= u_l without tilt), vb
+ * (with a pending push), w', n_new, the tilt rate.  Then, in place of "vz = (base_z - z) / dt; z = base_z" of step 8:
+ *   F1. vzb = vz - (gravity * dt);   zb = z + vzb * dt                                      (the ballistic candidate)
+ *   F2. airborne = (zb - base_z) > contact_eps
+ *   F3. vzg = -((sum over contact legs of sv_l.z, leg order, from 0.0f) / n_c): the take-off velocity the stance legs give the
+ *       base.  It is not (base_z - z) / dt: a terrain discontinuity moves a grounded base, but gives it no momentum.
+ *   F4. crashed = crashed or (not airborne and (base_z - z) > max_step_up and not fresh)    (sticky through the call)
+ *   F5. grounded: V = (c * vb.x - s * vb.y, s * vb.x + c * vb.y);  w = w';  vz = vzg;  z = base_z;  n = n_new
+ *       airborne: V, w and (tilt) n keep their values, the tilt rate is 0;  vz = vzb;  z = zb;  every contact_l is false, n_c = 0;
+ *       a pending push (P1) adds nothing; it still decays (P2, P3).  All by selects: the grounded values are computed for every
+ *       env, so no division by n_c = 0 reaches an output and a grounded env keeps the arithmetic of the step underneath.
+ *   F6. x = x + V.x * dt;   y = y + V.y * dt;   the yaw pair is integrated with w as in step 8.
+ * After the last substep, with c, s of the NEW yaw pair: a grounded env continues as in the step underneath, with the carried vz
+ * wherever that step has vz (root_states[9], base_lin_vel through Rt^T with tilt, the foot velocities).  An airborne env (the last
+ * substep's flag) takes V itself for root_states[7:9] and the foot velocities, vb = (c * V.x + s * V.y, c * V.y - s * V.x) for
+ * base_lin_vel and lin_vel_buffer, and weight / n_c is replaced by 0: no foot force, contact = false.  N1, N2 overwrite
+ * root_states[7:9] as before, so a push drawn in the air is the planar velocity the next call starts from.
+ *   contact_forces[n][0] = (0, 0, crash_force) for a crashed env (body 0, the base: the env's termination_contact_indices);
+ *   airborne[n] = the last substep's flag;   crashed[n] = the sticky flag.
+ * DTC_ERR_ARG before any launch: fly == NULL, airborne or crashed NULL, gravity < 0, max_step_up <= 0, crash_force <= 100, a foot
+ * that is body 0; and everything the step underneath refuses. */
+typedef struct DtcSimFlight {
+    float gravity;                   /* m/s^2 (>= 0)                                                                      */
+    float max_step_up;               /* m: a grounded substep whose support rises by more is a crash (> 0)                */
+    float crash_force;               /* N: written to contact_forces[n][0][2] of a crashed env (> 100)                    */
+    uint8_t* airborne;               /* [N], written                                                                      */
+    uint8_t* crashed;                /* [N], written                                                                      */
+} DtcSimFlight;
+/* sizeof() of DtcSimFlight, in a table of its own (the older tables keep their entries). */
+int dtc_sim_fly_abi_sizes(int64_t* out, int cap);
+int dtc_sim_step_fly(const DtcSimStep* st, const DtcSimCfg* cfg, const DtcSimTilt* tilt_or_null, const DtcSimActuator* act_or_null,
+                     const DtcSimFlight* fly, int N, void* stream);
 
 /* ---- DTC curriculum terrain, generated on the device (opt-in) ------------------------------
  * dtc_terrain_generate (csrc/terrain.hip) fills the int16 height table [tot_rows, tot_cols] (border included: zeros) and
