@@ -18,7 +18,9 @@
 // within a substep is a crash, reported as the base's own contact force so that dtc_check_termination ends the episode; max_step_up,
 // crash_force and the take-off rule are free constants.  Without it at least one foot is always in contact.  Deliberately absent from
 // all: control types "V" and "T", `forces` (never touched), contact dynamics, anything that topples the robot, and the heading
-// command's yaw law (legged_robot.py:537-539), which stays with the caller.
+// command's yaw law (legged_robot.py:537-539), which stays with the caller.  Contact with anything but the soles of the feet is not
+// here either: dtc_sim_contacts (csrc/sim_contacts.hip, opt-in, a launch of its own behind this one) writes thigh, shank and
+// stumble forces for the rewards, and holds nothing back.
 //
 // One 64-lane wavefront per env, 4 envs per 256-thread workgroup (as csrc/envstep.hip).  Lanes 0..11 own the joints (leg l owns
 // 3l..3l+2) and lane 3l+i computes component i of foot l; the twelve foot components are then broadcast with v_readlane and every lane
@@ -38,6 +40,7 @@
 
 #include "common.hpp"
 #include "philox.hpp"
+#include "terrain_lookup.hpp"
 
 namespace {
 
@@ -59,17 +62,9 @@ __device__ __forceinline__ float bcast(float v, int src_lane) {                 
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src_lane));
 }
 
-// _get_heights (legged_robot.py:1301-1316) for one world point; the clamp keeps every index inside the table whatever fx, fy hold
+// _get_heights (legged_robot.py:1301-1316) for one world point: the lookup rule lives in terrain_lookup.hpp, shared with sim_contacts.hip
 __device__ __forceinline__ float terrain_height(const int16_t* __restrict__ hs, const SimK& k, float fx, float fy) {
-    const float wx = (fx + k.border) / k.hscale;
-    const float wy = (fy + k.border) / k.hscale;
-    long long cx = (long long)wx, cy = (long long)wy;                              // .long(): truncation toward zero
-    cx = cx < 0 ? 0 : (cx > k.rows - 2 ? k.rows - 2 : cx);
-    cy = cy < 0 ? 0 : (cy > k.cols - 2 ? k.cols - 2 : cy);
-    const int16_t h1 = hs[cx * k.cols + cy], h2 = hs[(cx + 1) * k.cols + cy], h3 = hs[cx * k.cols + cy + 1];
-    int16_t h = h1 < h2 ? h1 : h2;
-    h = h < h3 ? h : h3;
-    return (float)h * k.vscale;
+    return dtc::terrain_height(hs, k, fx, fy);
 }
 
 // The tilt rotation Rt, the minimal rotation that takes z to n = (nx, ny, nz): third column n, third row (-nx, -ny, nz), and the

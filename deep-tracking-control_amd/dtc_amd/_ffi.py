@@ -214,6 +214,13 @@ class DtcSimFlight(C.Structure):
     _fields_ = [(k, C.c_float) for k in ("gravity", "max_step_up", "crash_force")] + [("airborne", C.c_void_p), ("crashed", C.c_void_p)]
 
 
+class DtcSimContacts(C.Structure):
+    """include/dtc_hip.h: the constants, tables and flag tensors of dtc_sim_contacts (leg collisions, foot stumbles); field order as there."""
+    _fields_ = ([(k, C.c_void_p) for k in ("knee_nominal", "knee_jacobian", "leg_contact", "stumbled")] + [("shanks", C.c_int32 * 4)] +
+                [(k, C.c_float) for k in ("body_radius", "stiffness", "max_force", "probe", "stumble_height", "wall_damping", "min_speed")] +
+                [("reserved", C.c_int32)])
+
+
 class DtcTerrainCfg(C.Structure):
     """include/dtc_hip.h: the configuration of dtc_terrain_generate; field order as there."""
     _fields_ = ([(k, C.c_double) for k in ("horizontal_scale", "vertical_scale", "border_size", "terrain_length", "terrain_width")] +
@@ -280,6 +287,8 @@ _SIGS = {
     "dtc_sim_fly_abi_sizes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
     "dtc_sim_step_fly": (C.c_int, [C.POINTER(DtcSimStep), C.POINTER(DtcSimCfg), C.POINTER(DtcSimTilt), C.POINTER(DtcSimActuator),
                                    C.POINTER(DtcSimFlight), C.c_int, c_stream]),
+    "dtc_sim_contact_abi_sizes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
+    "dtc_sim_contacts": (C.c_int, [C.POINTER(DtcSimStep), C.POINTER(DtcSimCfg), C.POINTER(DtcSimContacts), C.c_int, c_stream]),
     "dtc_terrain_abi_sizes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
     "dtc_terrain_generate": (C.c_int, [C.POINTER(DtcTerrainCfg), C.c_void_p, C.c_void_p, c_stream]),
     "dtc_check_termination": (C.c_int, [c_f32p, C.c_int, c_i32p, C.c_int, c_i64p, C.c_int64, c_f32p, c_f32p, c_f32p,
@@ -503,6 +512,9 @@ def _check_abi(l):
     theirs += list(sizes[:n])
     mine += [DtcSimFlight]                                                # ... and by its flight entry point's
     n = l.dtc_sim_fly_abi_sizes(sizes, 32)
+    theirs += list(sizes[:n])
+    mine += [DtcSimContacts]                                              # ... and by its contact entry point's
+    n = l.dtc_sim_contact_abi_sizes(sizes, 32)
     theirs += list(sizes[:n])
     mine += [DtcTerrainCfg]                                               # ... and by the terrain generator's
     n = l.dtc_terrain_abi_sizes(sizes, 32)

@@ -29,6 +29,14 @@ support that rises by more than `max_step_up` within a substep is a crash.  The 
 Nothing else in `step()` changes: a crash reaches `reset_buf` through the base's contact force and check_termination, as a fall does
 in the reference, and a base that falls into a gap terminates through the existing base-height rule.  Still a surrogate: the
 flight is a point mass on a parabola, `max_step_up`, `crash_force` and the take-off rule are choices, and nothing topples.
+
+`SimConfig.contacts` (opt-in, a `sim.ContactConfig`; None: the env above, bit for bit, nothing new allocated or launched) runs
+`dtc_sim_contacts` directly behind the surrogate step: thighs and shanks that penetrate the terrain and a swing foot that flies into
+a riser get contact forces, so the reward terms `collision`, `stumble`, `feet_stumble` and `foot_clearance` see non-zero inputs
+through the tensors they already read (`CONTACT_SCALES` holds scales for the first two; `reward_scales` stays the caller's).  The
+env then owns `leg_contact` [N,8] and `stumbled` [N,4] uint8.  The forces feed the rewards and nothing else: a colliding shank is
+not held back, a stumbling foot is not stopped but lifted onto the riser as before, nothing topples, the torso has no contact of
+its own, and every constant is a choice.
 """
 from __future__ import annotations
 
@@ -45,6 +53,9 @@ from .vec_env import VecEnv
 # raw reward scales (multiplied by dt, as the reference does): a Lite3-style set in which every term reads surrogate state
 _SCALES = dict(action_rate=-0.01, ang_vel_xy=-0.005, dof_acc=-2.5e-8, dof_pos_limits=-10.0, feet_air_time=1.0, lin_vel_z=-0.2,
                smooth=-0.0015, torques=-1e-6, tracking_ang_vel=0.5, tracking_lin_vel=1.0, tracking_optimal_footholds=0.2)
+# the two terms `SimConfig.contacts` gives an input to, for a caller to add to `reward_scales` (the default set is not touched):
+# collision is the Lite3 DTC value (lite3_dtc_config.py:161), stumble is a choice of this project
+CONTACT_SCALES = dict(collision=-1.5, stumble=-0.5)
 
 
 @dataclass
@@ -174,6 +185,10 @@ class SurrogateLeggedEnv(VecEnv):
             self._actuator_rows = (self.lag_state, self.push_vel)
         if s.flight is not None:
             self.airborne, self.crashed = torch.zeros(N, dtype=torch.uint8, device=dev), torch.zeros(N, dtype=torch.uint8, device=dev)
+        self._contact_flags = ()
+        if s.contacts is not None:
+            self.leg_contact, self.stumbled = torch.zeros(N, 8, dtype=torch.uint8, device=dev), torch.zeros(N, 4, dtype=torch.uint8, device=dev)
+            self._contact_flags = (self.leg_contact, self.stumbled)
         self.last_contacts = torch.zeros(N, 4, dtype=torch.bool, device=dev)
         self.contact_filt = torch.zeros(N, 4, dtype=torch.bool, device=dev)
         self.robot_mass = torch.full((N,), float(s.mass), **f)
@@ -256,6 +271,8 @@ class SurrogateLeggedEnv(VecEnv):
             push = s.actuator.push and self.common_step_counter % s.push_interval in (0, 1)
             self.sim.step(self, actions.to(self.device, torch.float32).contiguous(), draws.get("u_cmd"), lag_choice=draws.get("lag_choice"),
                           u_push=draws.get("u_push"), push=push)
+        if s.contacts is not None:                                                       # leg collisions and stumbles, on what the step wrote
+            self.sim.contacts(self)
         if s.heading_command:                                                            # legged_robot.py:537-539
             if s.tilt:                                                                   # forward = quat_apply(q, (1, 0, 0))
                 qx, qy, qz, qw = self.base_quat.unbind(dim=1)
@@ -275,6 +292,8 @@ class SurrogateLeggedEnv(VecEnv):
                 t.masked_fill_(bad.view(-1, *([1] * (t.dim() - 1))), 0.0)
             for t in (self.lin_vel_buffer, self.ang_vel_buffer, self.cmd_buffer):
                 t.masked_fill_(bad.view(1, -1, 1), 0.0)
+            for t in self._contact_flags:
+                t.masked_fill_(bad.view(-1, 1), 0)
         self.foot_positions = self.rigid_body_state[:, self.feet_indices, 0:3]
         self.foot_velocities = self.rigid_body_state[:, self.feet_indices, 7:10]
         self.hip_positions = self.rigid_body_state[:, self.thigh_indices, 0:3]

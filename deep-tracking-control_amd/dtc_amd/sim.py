@@ -3,14 +3,17 @@ on when no simulator stands behind them.  One launch per env step stands where t
 of the PD law of LeggedRobot._compute_torques (control type "P"), a kinematic quadruped that rides on its stance feet over the int16
 terrain table, and the bookkeeping of post_physics_step up to the planner.  include/dtc_hip.h states every operation; it is a
 surrogate, not physics (no attitude or contact dynamics, no "V" / "T" control, no heading yaw law; no free flight unless
-`SimConfig.flight` is set).  By default the
+`SimConfig.flight` is set; no contact with anything but the soles of the feet unless `SimConfig.contacts` is set, and then
+forces that feed the rewards only).  By default the
 base only yaws; `SimConfig.tilt` (opt-in) lets its roll and pitch follow the support points of the stance feet, still kinematically:
 after a reset the identity quaternion then gives one step with a tilt-rate spike.  `SimConfig.actuator` (opt-in, an
 `ActuatorConfig`) adds the two disturbances the reference trains under: the PD goal taken from a six-slot lag buffer of scaled
 actions at a slot the host draws per substep, and random pushes -- here a kinematic slip velocity of the base with a chosen decay,
 not a contact dynamics.  `SimConfig.flight` (opt-in, a `FlightConfig`) gives the base a vertical degree of freedom: a base whose support
 falls away falls under gravity and lands when it reaches a support, and a support that rises by more than a climbable step is a
-crash that ends the episode through the base contact force.
+crash that ends the episode through the base contact force.  `SimConfig.contacts` (opt-in, a `ContactConfig`) adds a second launch,
+`dtc_sim_contacts` (csrc/sim_contacts.hip), behind the step: contact forces of thighs and shanks that penetrate the terrain and of a
+swing foot that flies into a riser, for the reward terms that read them.  Nothing is held back by those forces and nothing topples.
 
 `SimConfig` holds the constants (Lite3 DTC values), `leg_tables(config)` the three small tables computed once in float64 from a
 two-link leg linearised at the default pose, and `SimStep` runs the launch on an env's own tensors (attribute names as in
@@ -88,6 +91,47 @@ class FlightConfig:
 
 
 @dataclass
+class ContactConfig:
+    """Leg collisions and foot stumbles of `dtc_sim_contacts` (include/dtc_hip.h states the operations), a launch of its own behind
+    the step.  Thigh and shank are capsules of `body_radius` sampled at three and four points; the deepest sample's penetration of
+    the terrain gives the body a vertical contact force `stiffness` * depth, capped at `max_force`.  A foot faster than `min_speed`
+    whose look-ahead point, `probe` ahead along its planar velocity, stands more than `stumble_height` above it has hit a riser:
+    its horizontal contact force opposes the velocity with `wall_damping` * speed, capped at `max_force`.  `shanks`: the body rows
+    of the four shanks, where the knee position is written.  The forces feed the rewards (collision, stumble, feet_stumble,
+    foot_clearance) and nothing else: a colliding shank is not held back, a stumbling foot is not stopped (the support rule still
+    lifts it onto the riser), nothing topples, and the torso has no contact of its own.  Every constant here is a free choice of
+    the surrogate, chosen, not fitted to anything: 0.02 m is a slim leg link, 5000 N/m reaches the collision threshold of 0.1 N
+    at 0.02 mm and the cap at 0.04 m, 0.05 m is one terrain cell, 0.03 m lies under every stair riser the generator makes."""
+    shanks: tuple = (3, 7, 11, 15)           # body rows; the knee position is written there
+    body_radius: float = 0.02                # m, capsule radius of thigh and shank
+    stiffness: float = 5000.0                # N/m, penetration spring
+    max_force: float = 200.0                 # N, cap of every force this kernel writes
+    probe: float = 0.05                      # m, look-ahead of a moving foot (one terrain cell)
+    stumble_height: float = 0.03             # m, a face this much above the foot point is a riser
+    wall_damping: float = 200.0              # N s/m, horizontal force per foot speed at a riser
+    min_speed: float = 0.05                  # m/s, below it a foot does not stumble
+
+    def validate(self, sim: "SimConfig | None" = None):
+        """The fields alone; with `sim`, the shank rows against its body layout as well."""
+        for name in ("stiffness", "max_force", "probe", "wall_damping"):
+            v = getattr(self, name)
+            if not (v > 0 and math.isfinite(v)):
+                raise ValueError(f"ContactConfig: {name} {v} must be positive and finite")
+        for name in ("body_radius", "stumble_height", "min_speed"):
+            v = getattr(self, name)
+            if not (v >= 0 and math.isfinite(v)):
+                raise ValueError(f"ContactConfig: {name} {v} must be finite and not negative")
+        shanks = tuple(int(v) for v in self.shanks)
+        if len(shanks) != 4 or len(set(shanks)) != 4:
+            raise ValueError(f"ContactConfig: shanks {self.shanks} must be four different body rows")
+        if sim is not None:
+            taken = {0, *(int(v) for v in sim.feet), *(int(v) for v in sim.thighs)}
+            for v in shanks:
+                if not 0 <= v < int(sim.num_bodies) or v in taken:
+                    raise ValueError(f"ContactConfig: shank row {v} is the base, a foot, a thigh or outside 0..{int(sim.num_bodies) - 1}")
+
+
+@dataclass
 class SimConfig:
     """Constants of the surrogate step (names as in DtcSimCfg, include/dtc_hip.h); defaults: the Lite3 DTC values."""
     sim_dt: float = 0.005
@@ -129,6 +173,7 @@ class SimConfig:
     min_det: float = 1e-6
     actuator: ActuatorConfig | None = None   # lag buffer and pushes (dtc_sim_step_act); None: the entry points above, bit for bit
     flight: FlightConfig | None = None       # free flight, landing, crashes (dtc_sim_step_fly); None: the entry points above, bit for bit
+    contacts: ContactConfig | None = None    # leg collisions, foot stumbles (dtc_sim_contacts, a second launch); None: no such launch
 
     @property
     def dt(self) -> float:
@@ -167,6 +212,23 @@ def leg_tables(config: SimConfig) -> dict:
         for k in range(2):
             jac[l, :, 1 + k] = (dxs[k], -dzs[k] * math.sin(a), dzs[k] * math.cos(a))
     return dict(hip_offset=hip, foot_nominal=nominal, leg_jacobian=jac)
+
+
+def knee_tables(config: SimConfig) -> dict:
+    """knee_nominal [4,3], knee_jacobian [4,3,3] (float64): the knee of the leg of `leg_tables`,
+    knee = hip + (-l1 sin(t1), l1 cos(t1) sin(a), -l1 cos(t1) cos(a)), with its Jacobian at the default pose (no t2 column)."""
+    l1, _ = config.link_lengths
+    hip = np.asarray(config.hip_offset, dtype=np.float64)
+    q0 = np.asarray(config.default_dof_pos, dtype=np.float64).reshape(4, 3)
+    nominal, jac = np.zeros((4, 3)), np.zeros((4, 3, 3))
+    for l in range(4):
+        a, t1, _ = q0[l]
+        xs, zs = -l1 * math.sin(t1), -l1 * math.cos(t1)
+        dxs, dzs = -l1 * math.cos(t1), l1 * math.sin(t1)
+        nominal[l] = hip[l] + (xs, -zs * math.sin(a), zs * math.cos(a))
+        jac[l, :, 0] = (0.0, -zs * math.cos(a), -zs * math.sin(a))
+        jac[l, :, 1] = (dxs, -dzs * math.sin(a), dzs * math.cos(a))
+    return dict(knee_nominal=nominal, knee_jacobian=jac)
 
 
 def joint_tables(config: SimConfig) -> dict:
@@ -208,6 +270,9 @@ class SimStep:
             self._lag_rng = np.random.RandomState(self.seed)
         if config.flight is not None:
             config.flight.validate()
+        if config.contacts is not None:
+            config.contacts.validate(config)
+            self.knee = {k: torch.as_tensor(v, dtype=torch.float32).to(dev).contiguous() for k, v in knee_tables(config).items()}
 
     def cfg_struct(self) -> "_ffi.DtcSimCfg":
         k, c = self.cfg, _ffi.DtcSimCfg()
@@ -306,3 +371,36 @@ class SimStep:
             _ffi.check(_ffi.lib().dtc_sim_step(s, c, N, _ffi.stream()), "dtc_sim_step")
         if u_cmd is None or drew_push:
             self.counter += 1
+
+    def contacts(self, env):
+        """`dtc_sim_contacts` on the tensors of `env`, as `step` just wrote them: the thigh, shank and foot-xy rows of
+        `contact_forces`, the knee positions (shank rows of `rigid_body_state`), `leg_contact` [N,8] and `stumbled` [N,4] uint8.
+        Needs `config.contacts`."""
+        k, N = self.cfg, self.N
+        if k.contacts is None:
+            raise _ffi.DtcError("SimStep: contacts() needs config.contacts")
+        B = int(k.num_bodies)
+        s = _ffi.DtcSimStep()
+        for name, tail in (("base_pos", (3,)), ("base_quat", (4,)), ("rigid_body_state", (B, 13)), ("contact_forces", (B, 3))):
+            self._check(name, getattr(env, name), (N,) + tail, torch.float32)
+            setattr(s, name, _ffi.ptr(getattr(env, name)))
+        t = env.dof_pos                                                  # an interleaved view of dof_state [N,D,2], or dense
+        if not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != torch.float32 or tuple(t.shape) != (N, 12):
+            raise _ffi.DtcError(f"SimStep: dof_pos must be a float32 tensor of shape {(N, 12)} on {self.device}")
+        s.dof_pos, s.dof_pos_row_stride, s.dof_pos_elem_stride = _ffi.ptr(t), t.stride(0), t.stride(1)
+        s.default_dof_pos, s.height_samples = _ffi.ptr(self.tables["default_dof_pos"]), _ffi.ptr(self.height_samples)
+        con = self.contact_struct()
+        for name, width in (("leg_contact", 8), ("stumbled", 4)):
+            self._check(name, getattr(env, name), (N, width), torch.uint8)
+            setattr(con, name, _ffi.ptr(getattr(env, name)))
+        _ffi.check(_ffi.lib().dtc_sim_contacts(s, self.cfg_struct(), con, N, _ffi.stream()), "dtc_sim_contacts")
+
+    def contact_struct(self) -> "_ffi.DtcSimContacts":
+        """The constants and the two knee tables of dtc_sim_contacts (the two flag pointers are left NULL)."""
+        c, con = self.cfg.contacts, _ffi.DtcSimContacts()
+        con.knee_nominal, con.knee_jacobian = _ffi.ptr(self.knee["knee_nominal"]), _ffi.ptr(self.knee["knee_jacobian"])
+        for l in range(4):
+            con.shanks[l] = int(c.shanks[l])
+        for name in ("body_radius", "stiffness", "max_force", "probe", "stumble_height", "wall_damping", "min_speed"):
+            setattr(con, name, float(getattr(c, name)))
+        return con

@@ -11,6 +11,8 @@
                                                                           # the env beside the env with actuator lag and pushes
     python deep-tracking-control_amd/tools/closed_loop.py --flight [--out profiles/closed_loop_flight.txt]
                                                                           # the terrain env beside the one with free flight and crashes
+    python deep-tracking-control_amd/tools/closed_loop.py --contacts [--out profiles/closed_loop_contacts.txt]
+                                                                          # the terrain env beside the one with leg collisions and stumbles
 
 Per run and iteration: the mean step reward (mean of rew_buf over the iteration's 24 steps and all envs), the mean episode length
 (the runner's tracker: the last <= 100 finished episodes; "-" before the first one ends) and the mean length of the episodes in flight.
@@ -33,6 +35,12 @@ With --flight the two runs are the env on the generated DTC terrain (the Lite3 g
 `SimConfig(flight=FlightConfig())`, default arithmetic, the same three interleaved rounds; dtc_sim_step beside dtc_sim_step_fly on
 that terrain, alternating; and, on a 6 x 9 grid that holds every family as one column, the share of envs airborne, crashed and
 reset per step per family over 200 steps of an untrained policy.  Nothing is asserted and nothing was tuned.
+With --contacts the two runs are the env on the generated DTC terrain (the Lite3 grid) without and with
+`SimConfig(contacts=ContactConfig())`, default arithmetic and the default reward scales, the same three interleaved rounds;
+dtc_sim_step beside dtc_sim_contacts, the launch behind it, on that terrain; on the 6 x 9 one-family-per-column grid the share of
+env steps with any leg_contact and with any stumbled per family over 200 steps of an untrained policy; and the learning signal: 256
+envs, 30 iterations on a stairs-only terrain with CONTACT_SCALES added to the default scales, the share of env steps with a leg
+collision in iterations 1-5 and in iterations 26-30.  Nothing is asserted and nothing was tuned.
 """
 import argparse
 import os
@@ -47,6 +55,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 
 from dtc_amd import sim as SIM, synthetic  # noqa: E402
 from dtc_amd.env import SurrogateConfig, SurrogateLeggedEnv  # noqa: E402
+from dtc_amd.env.surrogate import _SCALES, CONTACT_SCALES  # noqa: E402
 from dtc_amd.runners import OnPolicyRunner  # noqa: E402
 from dtc_amd.runners.on_policy_runner import _EpisodeTracker  # noqa: E402
 from dtc_amd.terrain import FAMILIES, Terrain, TerrainConfig  # noqa: E402
@@ -60,13 +69,15 @@ def rough_env(num_envs, tilt, actuator=None):
     return SurrogateLeggedEnv(num_envs, DEV, SurrogateConfig(sim=SIM.SimConfig(tilt=tilt, actuator=actuator)), synthetic.reward_table(), seed=5)
 
 
-def make(num_envs, algo, seed=11, tilt=None, terrain=None, steps=STEPS, actuator=None, flight=None):
+def make(num_envs, algo, seed=11, tilt=None, terrain=None, steps=STEPS, actuator=None, flight=None, contacts=None, scales=None):
     """`tilt` None: the default env on the flat table; False / True: the yaw-only / the tilt env on the rough table (`actuator`, an
     ActuatorConfig: with lag and pushes); `terrain`, a TerrainConfig: the env on the generated terrain (`flight`, a FlightConfig: with
-    free flight, landing and crashes)."""
+    free flight, landing and crashes; `contacts`, a ContactConfig: with leg collisions and stumbles; `scales`: reward scales in
+    place of the default set)."""
     torch.manual_seed(seed)
     if terrain is not None:
-        env = SurrogateLeggedEnv(num_envs, DEV, SurrogateConfig(sim=SIM.SimConfig(flight=flight), terrain=terrain), seed=5)
+        kw = {} if scales is None else dict(reward_scales=dict(scales))
+        env = SurrogateLeggedEnv(num_envs, DEV, SurrogateConfig(sim=SIM.SimConfig(flight=flight, contacts=contacts), terrain=terrain, **kw), seed=5)
     else:
         env = SurrogateLeggedEnv(num_envs, DEV, SurrogateConfig(), seed=5) if tilt is None else rough_env(num_envs, tilt, actuator)
     runner = dict(policy_class_name="ActorCriticDecoder", algorithm_class_name="PPO", num_steps_per_env=steps, save_interval=10 ** 9)
@@ -114,8 +125,8 @@ def timed(fn, acc):
     return f
 
 
-def timing_round(num_envs, iters, algo, tilt=None, terrain=None, actuator=None, flight=None):
-    r, env = make(num_envs, algo, tilt=tilt, terrain=terrain, actuator=actuator, flight=flight)
+def timing_round(num_envs, iters, algo, tilt=None, terrain=None, actuator=None, flight=None, contacts=None):
+    r, env = make(num_envs, algo, tilt=tilt, terrain=terrain, actuator=actuator, flight=flight, contacts=contacts)
     r.learn(2)                                                # warm-up: allocations, first launches
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -408,6 +419,118 @@ def flight_report(args):
     return lines
 
 
+def contacts_probe(num_envs, calls):
+    """dtc_sim_step, then dtc_sim_contacts on what it wrote, on the generated Lite3 terrain under random actions: us per call of each
+    (median), and the share of envs with any leg contact and with any stumble at the end."""
+    env = SurrogateLeggedEnv(num_envs, DEV, SurrogateConfig(sim=SIM.SimConfig(contacts=SIM.ContactConfig()), terrain=TerrainConfig(seed=1)), seed=5)
+    g = torch.Generator(device=DEV).manual_seed(3)
+    env.reset()
+    acc = ([], [])
+    for i in range(calls + 20):
+        a, u = torch.randn(num_envs, 12, generator=g, device=DEV), torch.rand(num_envs, 3, generator=g, device=DEV)
+        for t, fn in zip(acc, (lambda: env.sim.step(env, a, u), lambda: env.sim.contacts(env))):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if i >= 20:
+                t.append(1e6 * (time.perf_counter() - t0))
+    return (statistics.median(acc[0]), statistics.median(acc[1]), float(env.leg_contact.any(dim=1).float().mean()),
+            float(env.stumbled.any(dim=1).float().mean()))
+
+
+def contacts_family_probe(num_envs, steps=200, rollout=25):
+    """An untrained policy on a 6 x 9 grid whose column j is family j, with contacts: per family the share of env steps with any
+    leg_contact, with any stumbled, and with a reset.  Rollouts without updates; everything is summed on the device and read once."""
+    cfg = TerrainConfig(num_rows=6, num_cols=9, terrain_proportions=tuple([1 / 9] * 9), seed=1)
+    r, env = make(num_envs, {}, terrain=cfg, steps=rollout, contacts=SIM.ContactConfig())
+    types = env.terrain_types
+    count = torch.bincount(types, minlength=9).double()
+    sums = torch.zeros(3, 9, dtype=torch.float64, device=DEV)
+    inner = r.env.step
+
+    def step(actions):
+        out = inner(actions)
+        for row, flag in zip(sums, (env.leg_contact.any(dim=1), env.stumbled.any(dim=1), out[2])):
+            row.index_add_(0, types, flag.double())
+        return out
+    object.__setattr__(r.env, "step", step)
+    state = dict(obs_dict=r.env.get_observations(), rew_buf=r.env.get_reward_buf())
+    for _ in range(steps // rollout):
+        r._collect(state, None, [])
+        r.alg.storage.clear()
+    return (sums / count / (steps // rollout * rollout)).tolist(), count.tolist()
+
+
+STAIRS_ONLY = (0.0, 0.0, 0.5, 0.5)                            # column 0: stairs down, column 1: stairs up
+
+
+def collision_curve(num_envs=256, iters=30):
+    """The learning signal of the collision term: PPO on a stairs-only terrain (the Lite3 grid) with CONTACT_SCALES added to the
+    default scales.  Per iteration: the share of env steps with any leg_contact, with any stumbled, and the mean step reward."""
+    r, env = make(num_envs, {}, terrain=TerrainConfig(terrain_proportions=STAIRS_ONLY, seed=1), contacts=SIM.ContactConfig(),
+                  scales=dict(_SCALES, **CONTACT_SCALES))
+    sums, rows = torch.zeros(3, dtype=torch.float64, device=DEV), []
+    inner = r.env.step
+
+    def step(actions):
+        out = inner(actions)
+        sums[0] += env.leg_contact.any(dim=1).double().mean()
+        sums[1] += env.stumbled.any(dim=1).double().mean()
+        sums[2] += out[1].double().mean()
+        return out
+    object.__setattr__(r.env, "step", step)
+    for _ in range(iters):
+        r.learn(1)
+        rows.append(tuple((sums / STEPS).tolist()))
+        sums.zero_()
+    return rows
+
+
+def contacts_report(args):
+    lite3 = TerrainConfig(seed=1)
+    runs = (("no contacts", None), ("contacts", SIM.ContactConfig()))
+    rounds = {tag: [] for tag, _ in runs}
+    for _ in range(3):
+        for tag, c in runs:
+            rounds[tag].append(timing_round(args.envs, args.iters, {}, terrain=lite3, contacts=c))
+    c = SIM.ContactConfig()
+    lines = [f"closed loop on SurrogateLeggedEnv on the generated DTC terrain (the Lite3 grid), without and with SimConfig(contacts=ContactConfig()) "
+             f"(body_radius {c.body_radius} m, stiffness {c.stiffness:.0f} N/m, max_force {c.max_force:.0f} N, probe {c.probe} m, stumble_height "
+             f"{c.stumble_height} m, wall_damping {c.wall_damping:.0f} N s/m, min_speed {c.min_speed} m/s): {args.envs} envs x {STEPS} steps per "
+             f"iteration, {args.iters} iterations, PPO, default arithmetic, the default reward scales, fixed seeds",
+             "", "three interleaved rounds, median (min .. max):"]
+    for tag, _ in runs:
+        rs = rounds[tag]
+        lines.append(f"  {tag:11s} env-steps/s, whole loop {spread([r['steps_per_s'] for r in rs], '{:.0f}')}")
+        lines.append(f"  {'':11s} ms per iteration, each call closed by a synchronise: env.step x{STEPS} {spread([r['env_ms'] for r in rs], '{:.2f}')}"
+                     f" | act() x{STEPS} {spread([r['act_ms'] for r in rs], '{:.2f}')} | update() {spread([r['update_ms'] for r in rs], '{:.2f}')}")
+    probes = [contacts_probe(args.envs, args.calls) for _ in range(3)]
+    lines += ["", f"one surrogate step and the contact launch behind it at {args.envs} envs on that terrain, us per call (host clock, each closed by a "
+              "synchronise), three rounds:",
+              f"  dtc_sim_step      {spread([p[0] for p in probes])}",
+              f"  dtc_sim_contacts  {spread([p[1] for p in probes])}   (envs with any leg contact / any stumble at the end, under random actions: "
+              f"{100 * statistics.mean(p[2] for p in probes):.1f} % / {100 * statistics.mean(p[3] for p in probes):.1f} %)"]
+    share, count = contacts_family_probe(args.envs)
+    lines += ["", f"an untrained policy with contacts, {args.envs} envs on a 6 x 9 grid (column j = family j, max_init_terrain_level 5), 200 steps, no update;",
+              "the share of a family's env steps with any leg_contact, with any stumbled, and with a reset:",
+              "  family              envs   leg_contact   stumbled   reset"]
+    for j, name in enumerate(FAMILIES):
+        lines.append(f"  {name:19s} {int(count[j]):5d}   {100 * share[0][j]:8.2f} %   {100 * share[1][j]:6.2f} %   {100 * share[2][j]:5.2f} %")
+    rows = collision_curve()
+    first, last = statistics.mean(r[0] for r in rows[:5]), statistics.mean(r[0] for r in rows[25:30])
+    lines += ["", "learning signal: 256 envs, 30 iterations, PPO, a stairs-only terrain (the Lite3 grid, stairs down and stairs up), the default scales "
+              f"plus CONTACT_SCALES {CONTACT_SCALES}; per iteration the share of env steps with any leg_contact:",
+              "  " + " ".join(f"{100 * r[0]:.2f}" for r in rows) + "   [%]",
+              "  with any stumbled:",
+              "  " + " ".join(f"{100 * r[1]:.2f}" for r in rows) + "   [%]",
+              "  mean step reward:",
+              "  " + " ".join(f"{r[2]:+.5f}" for r in rows),
+              f"  leg collisions, iterations 1-5: {100 * first:.3f} %   iterations 26-30: {100 * last:.3f} %   difference: {100 * (last - first):+.3f} points"]
+    lines += ["", "bench.py runs no env step: its headline is not re-measured here."]
+    return lines
+
+
 ALL_FAMILIES = (0.1, 0.1, 0.1, 0.1, 0.15, 0.15, 0.1, 0.1, 0.1)
 
 
@@ -502,10 +625,12 @@ def main():
     ap.add_argument("--terrain", action="store_true")
     ap.add_argument("--actuator", action="store_true")
     ap.add_argument("--flight", action="store_true")
+    ap.add_argument("--contacts", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if args.tilt or args.terrain or args.actuator or args.flight:
-        report = tilt_report if args.tilt else terrain_report if args.terrain else actuator_report if args.actuator else flight_report
+    if args.tilt or args.terrain or args.actuator or args.flight or args.contacts:
+        report = (tilt_report if args.tilt else terrain_report if args.terrain else actuator_report if args.actuator else
+                  flight_report if args.flight else contacts_report)
         text = "\n".join(report(args)) + "\n"
         print(text)
         if args.out:

@@ -389,7 +389,8 @@ int dtc_env_reset(const DtcResetStep* st, const DtcResetCfg* cfg, int N, void* s
  * projected_gravity is (0, 0, -1)); dtc_sim_step_tilt, below, adds a kinematic roll and pitch.  Absent on purpose from both:
  * attitude and base dynamics (the base rides on its stance feet; free flight, landing and crashes: dtc_sim_step_fly, below), lag
  * buffers and pushes (dtc_sim_step_act, below; `forces` are never touched), control types "V" and "T", contact dynamics, anything
- * that topples the robot, and the heading command's yaw law (legged_robot.py:537-539 stays with the caller).
+ * that topples the robot, and the heading command's yaw law (legged_robot.py:537-539 stays with the caller).  Contact with anything
+ * but the soles of the feet: dtc_sim_contacts, below, a launch of its own, whose forces feed the rewards and hold nothing back.
  *
  * Every value is a single-rounded fp32 operation in the order below (-ffp-contract=off; tests/sim_oracle.py restates it in numpy
  * float32, bit for bit).  Joint j = 3 l + k is joint k of leg l; sums over legs run in leg order 0..3 from 0.0f.  Once per step:
@@ -623,6 +624,70 @@ typedef struct DtcSimFlight {
 int dtc_sim_fly_abi_sizes(int64_t* out, int cap);
 int dtc_sim_step_fly(const DtcSimStep* st, const DtcSimCfg* cfg, const DtcSimTilt* tilt_or_null, const DtcSimActuator* act_or_null,
                      const DtcSimFlight* fly, int N, void* stream);
+
+/* ---- surrogate legged env: leg collisions and foot stumbles on the terrain (opt-in) --------
+ * dtc_sim_contacts (csrc/sim_contacts.hip) is a launch of its own that runs directly behind any dtc_sim_step* on what that launch
+ * wrote, once per env step (the env kernels read contact forces once per step, after the last substep, as the reference refreshes
+ * them at the top of post_physics_step).  It gives the contact-force rows of the thighs and shanks and the horizontal force of the
+ * feet a content, so that the reward terms `collision`, `stumble`, `feet_stumble` and `foot_clearance` (csrc/rewards.hip) see
+ * non-zero inputs in a closed-loop run.  One wavefront per env, lanes 8 l + j serve leg l: j = 0..2 the thigh samples, j = 3..6 the
+ * shank samples; the eight lanes share the leg's stores.  No LDS, no atomics, no scratch.
+ *
+ * What this model is NOT: the forces feed the rewards and nothing else.  A colliding shank is not held back, a stumbling foot is
+ * not stopped (it is still lifted onto the riser by the support rule of step 6), nothing topples, the torso has no contact of its
+ * own (its row belongs to the crash of dtc_sim_step_fly), and `forces`, friction and control types "V" and "T" stay absent.  Every
+ * constant of DtcSimContacts is a free choice of the surrogate, fitted to nothing.
+ *
+ * Inputs, as the step just wrote them: B = base_pos, q = base_quat (x, y, z, w), dof_pos (strides as in DtcSimStep),
+ * H_l = rigid_body_state[thigh_l][0:3] (the hip point), F_l = rigid_body_state[foot_l][0:3], V_l = rigid_body_state[foot_l][7:9],
+ * the height table, default_dof_pos, and two tables of dtc_amd.sim.knee_tables: knee_nominal [4,3] and knee_jacobian [4,3,3], the
+ * knee of a leg (hip + (-l1 sin t1, l1 cos t1 sin a, -l1 cos t1 cos a)) linearised at the default pose as leg_jacobian is.
+ * Every value is a single-rounded fp32 operation in the order below (-ffp-contract=off); tests/sim_contact_oracle.py restates it in
+ * numpy float32, bit for bit, and is the specification.  Per leg l, with dq = dof_pos[3 l .. 3 l + 2] - default:
+ *   C1. k[i] = knee_nominal[l][i] + ((Jk[l][i][0] * dq0 + Jk[l][i][1] * dq1) + Jk[l][i][2] * dq2)
+ *       rot(q, v): qv = (q.x, q.y, q.z);  t = 2 * (qv x v), t.x = 2 * (q.y * v.z - q.z * v.y), t.y = 2 * (q.z * v.x - q.x * v.z),
+ *       t.z = 2 * (q.x * v.y - q.y * v.x);  c = qv x t likewise;  rot.i = (v.i + q.w * t.i) + c.i
+ *       K = (B.x + rot.x, B.y + rot.y, B.z + rot.z)            -> rigid_body_state[shank_l][0:3] (the other columns are left alone)
+ *   C2. sample j: X = A + s * (E - A), per component, with (A, E, s) = (H, K, (j + 1) / 4) for j = 0..2 and (K, F, (j - 3) / 4)
+ *       for j = 3..6 (s = 0 gives K + 0 * (F - K)); the foot point itself stays the step's business
+ *   C3. pen_j = (terrain_height(X.x, X.y) + body_radius) - X.z, the lookup rule of step 5 of dtc_sim_step
+ *       d = 0.0f, then in sample order d = pen_j > d ? pen_j : d (a NaN is never selected): d_thigh over j = 0..2, d_shank over 3..6
+ *   C4. f = stiffness * d;  Fb = d > 0 ? (f < max_force ? f : max_force) : 0
+ *       contact_forces[thigh_l] = (0, 0, Fb_thigh);  contact_forces[shank_l] = (0, 0, Fb_shank);
+ *       leg_contact[n][2 l] = d_thigh > 0;  leg_contact[n][2 l + 1] = d_shank > 0
+ *   C5. sp = sqrt(V.x * V.x + V.y * V.y);  e = (V.x / sp, V.y / sp);  P = (F.x + e.x * probe, F.y + e.y * probe);
+ *       rise = terrain_height(P.x, P.y) - F.z;  hit = sp > min_speed && rise > stumble_height;
+ *       m = wall_damping * sp;  mag = m < max_force ? m : max_force;
+ *       contact_forces[foot_l][0] = hit ? -(mag * e.x) : 0;  contact_forces[foot_l][1] = hit ? -(mag * e.y) : 0;
+ *       stumbled[n][l] = hit.  contact_forces[foot_l][2] is NOT written.
+ * Everything else stays byte for byte: the base row of contact_forces (flight's crash force), the hip rows, every other row and
+ * column of rigid_body_state.  Every comparison is false for a NaN, so an env row of NaN gives no flag and zero forces, and the
+ * lookup's clamp keeps every index inside the table.
+ * `st`, `cfg`: the descriptor and constants of the dtc_sim_step* call this one follows; of `st` only base_pos, base_quat, dof_pos
+ * with its strides, default_dof_pos, height_samples, rigid_body_state and contact_forces are read here (the others may be NULL).
+ * DTC_ERR_ARG before any launch (comparisons written so that a NaN is refused): a null descriptor or a null pointer among those
+ * named, among the two tables or the two flag tensors; N outside 1..2^24; stiffness, max_force, probe or wall_damping not > 0 or
+ * not finite; body_radius, stumble_height or min_speed negative or not finite; a shank that is body 0, a foot, a thigh, another
+ * leg's shank or outside 0..num_bodies - 1; and what dtc_sim_step refuses of num_dof, num_bodies, feet, thighs, the table's shape
+ * and scale and the dof_pos strides. */
+typedef struct DtcSimContacts {
+    const float* knee_nominal;       /* [4,3] base frame                                                                  */
+    const float* knee_jacobian;      /* [4,3,3]: d knee_l[i] / d q[3 l + k] at the default pose                           */
+    uint8_t* leg_contact;            /* [N,8], written: (thigh, shank) of leg 0, 1, 2, 3                                  */
+    uint8_t* stumbled;               /* [N,4], written                                                                    */
+    int32_t shanks[4];               /* body rows, leg order; the knee position is written there                         */
+    float body_radius;               /* m, capsule radius of thigh and shank (>= 0)                                       */
+    float stiffness;                 /* N/m, penetration spring (> 0)                                                     */
+    float max_force;                 /* N, cap of every force this kernel writes (> 0)                                    */
+    float probe;                     /* m, look-ahead of a moving foot (> 0)                                              */
+    float stumble_height;            /* m, a face this much above the foot point is a riser (>= 0)                        */
+    float wall_damping;              /* N s/m, horizontal force per foot speed at a riser (> 0)                           */
+    float min_speed;                 /* m/s, below it a foot does not stumble (>= 0)                                      */
+    int32_t reserved;
+} DtcSimContacts;
+/* sizeof() of DtcSimContacts, in a table of its own (the older tables keep their entries). */
+int dtc_sim_contact_abi_sizes(int64_t* out, int cap);
+int dtc_sim_contacts(const DtcSimStep* st, const DtcSimCfg* cfg, const DtcSimContacts* con, int N, void* stream);
 
 /* ---- DTC curriculum terrain, generated on the device (opt-in) ------------------------------
  * dtc_terrain_generate (csrc/terrain.hip) fills the int16 height table [tot_rows, tot_cols] (border included: zeros) and
