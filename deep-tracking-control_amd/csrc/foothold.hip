@@ -6,7 +6,10 @@
 //
 // Two kernels share the per-point arithmetic:
 //   * foothold_plan_fast_kernel  -- the reference's 33 x 21 grid without debug outputs (the hot path; see its header);
-//   * foothold_plan_kernel       -- any grid up to 64 x 32 and the debug outputs (score table, nominal index, slope).
+//   * foothold_plan_kernel       -- any grid from 2 x 2 to 64 x 32 and the debug outputs (score table, nominal index, slope).  Its dynamic
+//     LDS request, (2 * 4 P + 96) * 4 bytes, reaches 65 920 B at 64 x 32; the MI355X grants 163 840 B per workgroup, and the host
+//     refuses a grid the device does not hold.  The candidate patch is used where patch_ok (make_params: the disc fits 8 cells,
+//     both tables strictly increasing and uniform) and ny >= 8; every other grid takes the full scan.
 //
 // Generic kernel: one 64-lane wavefront per env, 4 envs per 256-thread workgroup.  The 4 height rows
 // of a workgroup are one contiguous, 16-byte aligned chunk of 4*P floats (P = nx*ny = 693),
@@ -1023,6 +1026,16 @@ __global__ __launch_bounds__(256) void foothold_rewards_kernel(const float* __re
     if (miss) miss[n] = minz < 0.0f ? 1.0f : 0.0f;
 }
 
+constexpr double PATCH_MAX_DEV = 0.03;      // cells a table entry may lie off its uniform position (derivation: make_params)
+
+bool uniform_table(const float* t, int n) {
+    const double d = ((double)t[n - 1] - (double)t[0]) / (double)(n - 1);
+    if (!(d > 0.0) || !(d < 1e30)) return false;          // decreasing, constant, NaN or infinite
+    for (int i = 0; i < n; ++i)
+        if (!(fabs((double)t[i] - ((double)t[0] + (double)i * d)) <= PATCH_MAX_DEV * d)) return false;
+    return true;
+}
+
 int make_params(const DtcGridCfg* cfg, GridParams& gp) {
     DTC_REQUIRE(cfg != nullptr, "grid cfg is null");
     DTC_REQUIRE(cfg->nx >= 2 && cfg->nx <= 64 && cfg->ny >= 2 && cfg->ny <= 32, "grid %dx%d unsupported (nx<=64, ny<=32)",
@@ -1040,14 +1053,31 @@ int make_params(const DtcGridCfg* cfg, GridParams& gp) {
     gp.inv_dy = (float)(gp.ny - 1) / (gp.y[gp.ny - 1] - gp.y0);
     gp.rad_x = 0.16f * gp.inv_dx + 0.05f;
     gp.rad_y = 0.16f * gp.inv_dy + 0.05f;
-    gp.patch_ok = (2.0f * gp.rad_x < 7.0f) && (2.0f * gp.rad_y < 7.0f) ? 1 : 0;
+    // the placement assumes table[i] = table[0] + i / inv_d: it holds only for a strictly increasing, uniform table.  A point
+    // that lies delta cells off its uniform position moves the in-radius index range by delta, so delta plus the float
+    // rounding of u has to stay inside the 0.05 cells of slack in rad: PATCH_MAX_DEV = 0.03 leaves 0.02 cells (> 0.9 mm
+    // at the finest eligible spacing) to the rounding.  Any other table takes the full scan.
+    gp.patch_ok = (2.0f * gp.rad_x < 7.0f) && (2.0f * gp.rad_y < 7.0f) && uniform_table(gp.x, gp.nx) && uniform_table(gp.y, gp.ny) ? 1 : 0;
     return DTC_OK;
 }
+
+// dynamic LDS of the generic kernel: two [4][P] float rows + the coordinate tables
+size_t generic_lds_bytes(int P) {
+    const int P4 = (ENVS_PER_BLOCK * P + 3) & ~3;
+    return (size_t)(2 * P4 + 96) * sizeof(float);
+}
+
+bool takes_fast_kernel(const GridParams& gp) { return gp.nx == 33 && gp.ny == 21 && !getenv("DTC_PLANNER_GENERIC"); }
 
 template <bool VEC, bool DEBUG>
 void launch(int grid, size_t lds, hipStream_t s, const float* mh, const float* rs, const float* th, const float* cmd,
             const GridParams& gp, int64_t* idx, float* obs, float* world, float* pred, float* p2r, float* score,
             int64_t* nom, float* slope, float* hw, int N) {
+    // a request beyond the 64 KiB every launch may make (64 x 32 only) is announced to the runtime first; a refusal shows
+    // as the launch error check_launch reports
+    if (lds > 65536)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&foothold_plan_kernel<VEC, DEBUG>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL((foothold_plan_kernel<VEC, DEBUG>), dim3(grid), dim3(256), lds, s, mh, rs, th, cmd, gp, idx, obs,
                        world, pred, p2r, score, nom, slope, hw, N);
 }
@@ -1067,12 +1097,11 @@ extern "C" int dtc_foothold_plan(const float* measured_heights, const float* roo
     DTC_REQUIRE(measured_heights && root_states && thigh_pos && commands, "null input");
     DTC_REQUIRE(idx && foothold_obs && opt_world && pred && pred_to_robot, "null output");
     hipStream_t s = (hipStream_t)stream;
-    const int P4 = (ENVS_PER_BLOCK * gp.P + 3) & ~3;
-    const size_t lds = (size_t)(2 * P4 + 96) * sizeof(float);
+    const size_t lds = generic_lds_bytes(gp.P);
     const int grid = (int)dtc::ceil_div(N, ENVS_PER_BLOCK);
     const double bytes = (double)N * (gp.P * 4.0 + 13 * 4 + 4 * 4 + 12 * 4 + 32 + 32 + 48 + 96);
     const bool debug = score_or_null || nominal_idx_or_null || slope_or_null || heights_world_or_null;
-    if (!debug && gp.nx == 33 && gp.ny == 21 && !getenv("DTC_PLANNER_GENERIC")) {
+    if (!debug && takes_fast_kernel(gp)) {
         // four envs per wave, 16 per workgroup (a persistent split measured slower: without new workgroups to backfill, the
         // chip drains unevenly); the descriptors of the per-env arrays need N * 52 bytes < 4 GiB
         DTC_REQUIRE(N <= 40000000, "N too large for the 32-bit buffer offsets of the planner");
@@ -1082,6 +1111,14 @@ extern "C" int dtc_foothold_plan(const float* measured_heights, const float* roo
                            const_cast<float*>(measured_heights), root_states, thigh_pos, commands, gp, TableParams{}, idx,
                            foothold_obs, opt_world, pred, pred_to_robot, N, StepArgs{});
         return dtc::check_launch("foothold_plan");
+    }
+    {   // 64 x 32 asks for 65 920 B of LDS per workgroup: refuse, before any launch, what the device does not grant
+        int dev = 0, lds_max = 0;
+        DTC_REQUIRE(hipGetDevice(&dev) == hipSuccess &&
+                    hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess,
+                    "foothold_plan: cannot read the device's LDS limit");
+        DTC_REQUIRE(lds <= (size_t)lds_max, "grid %dx%d needs %zu B of LDS per workgroup, the device grants %d", gp.nx, gp.ny, lds,
+                    lds_max);
     }
     const bool vec = dtc::aligned16(measured_heights);
     dtc::ProfScope prof(debug ? "foothold_plan_debug" : "foothold_plan", bytes, s);
@@ -1093,6 +1130,21 @@ extern "C" int dtc_foothold_plan(const float* measured_heights, const float* roo
     else launch<false, false>(DTC_FH_ARGS);
 #undef DTC_FH_ARGS
     return dtc::check_launch("foothold_plan");
+}
+
+// Host only: which path a grid takes.  out = { patch_ok (the 8 x 8 candidate patch may be PLACED: 2 * rad < 7 on both axes and
+// both tables strictly increasing and uniform; the generic kernel uses it only where ny >= 8), P, dynamic LDS bytes of the
+// generic kernel, 1 if the non-debug call takes the fast kernel else 0 }
+extern "C" int dtc_foothold_grid_info(const DtcGridCfg* cfg, int32_t out[4]) {
+    GridParams gp;
+    int rc = make_params(cfg, gp);
+    if (rc != DTC_OK) return rc;
+    DTC_REQUIRE(out != nullptr, "out is null");
+    out[0] = gp.patch_ok;
+    out[1] = gp.P;
+    out[2] = (int32_t)generic_lds_bytes(gp.P);
+    out[3] = takes_fast_kernel(gp) ? 1 : 0;
+    return DTC_OK;
 }
 
 extern "C" int dtc_get_heights(const int16_t* height_samples, int rows, int cols, const float* root_states,

@@ -42,6 +42,17 @@ class GridConfig:
         return len(self.points_x) * len(self.points_y)
 
 
+def grid_info(grid: GridConfig | None = None) -> dict:
+    """Which path a grid takes (host only, no device needed): `patch_ok` -- the 8 x 8 candidate patch may be placed (the
+    0.16 m disc fits into 8 cells on both axes and both tables are strictly increasing and uniform; the generic kernel uses
+    it only where ny >= 8, any other grid takes the exact full scan), `num_points`, `lds_bytes` of the generic kernel per
+    workgroup, and `fast` -- the call without debug outputs takes the 33 x 21 fast kernel."""
+    import ctypes
+    out = (ctypes.c_int32 * 4)()
+    _ffi.check(_ffi.lib().dtc_foothold_grid_info((grid or GridConfig()).c_struct(), out), "dtc_foothold_grid_info")
+    return dict(patch_ok=bool(out[0]), num_points=int(out[1]), lds_bytes=int(out[2]), fast=bool(out[3]))
+
+
 def plan(measured_heights: torch.Tensor, root_states: torch.Tensor, thigh_pos: torch.Tensor,
          commands: torch.Tensor, grid: GridConfig | None = None, want_score: bool = False,
          want_debug: bool = False) -> dict:

@@ -74,6 +74,14 @@ int dtc_foothold_plan(const float* measured_heights /*[N,P]*/, const float* root
                       float* score_or_null, int64_t* nominal_idx_or_null, float* slope_or_null,
                       float* heights_world_or_null, int N, void* stream);
 
+/* Host only (no device needed): which path a grid takes.  out[0] = 1 if the 8 x 8 candidate patch may be placed (the disc of
+ * 0.16 m fits into 8 cells on both axes AND both tables are strictly increasing and uniform to 0.03 cells; the generic kernel
+ * uses the patch only where ny >= 8, every other grid takes the exact full scan), out[1] = P = nx * ny, out[2] = bytes of
+ * dynamic LDS per workgroup of the generic kernel ((2 * 4 * P + 96) * 4: 65 920 B at the largest grid, 64 x 32;
+ * dtc_foothold_plan refuses a grid whose request exceeds the device's per-workgroup limit before it launches anything),
+ * out[3] = 1 if the call without debug outputs takes the 33 x 21 fast kernel. */
+int dtc_foothold_grid_info(const DtcGridCfg* cfg, int32_t out[4]);
+
 /* Consumers of the planner output in the same env step (legged_robot_dtc.py:577-586 and :536-539):
  * tracking[n] = sum_legs contact ? -log(0.8 + ||foot_xy - optimal_xy||) : 0   (_reward_tracking_optimal_footholds)
  * miss[n]     = min_legs foot_z < 0 ? 1 : 0                                    (_reward_foothold_miss)

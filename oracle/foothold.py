@@ -6,7 +6,7 @@ Follows legged_gym/envs/base/legged_robot_dtc.py:
   :123-148  terrain score (clamp, central differences, mean / unbiased var, thresholds)
   :152-164  distance to the nominal foothold, 0.16 m radius mask
   :169-175  combine + exception mask
-  :180-181  per-leg argmin over the 693 grid points (topk k=1, smallest; ties -> lowest index)
+  :180-181  per-leg argmin over the P = NX*NY grid points (topk k=1, smallest; ties -> lowest index)
   :184-201  observation decode (with the reference's swapped x/y table indexing) + world position
 Constants: legged_robot_config.py:210 (dt), lite3_dtc_config.py:109 (decimation) -> t_stance 0.02.
 
@@ -17,23 +17,27 @@ kernels use -- per lane two running sums over its float4 chunks (see wave_sum) f
 xor-butterfly (offsets 1,2,4,8,16,32 = the kernel's DPP quad / half-row / row / cross-row steps) -- and every other operation is a single correctly
 rounded float32 op in reference order.  The HIP kernel is therefore expected to agree with
 this file BIT FOR BIT on every output; this file in turn is pinned against the imported
-reference by tests/golden/scorer_*.npz (knife-edge policy: SURVEY.md §8c G4).
+reference by tests/golden/scorer*.npz (knife-edge policy: SURVEY.md §8c G4).
+
+Any grid.  NX, NY and P = NX*NY come from the two coordinate tables (the reference's grid is 33 x 21 = 693).  The
+gradient keeps the reference's hard-coded divisors 0.1 / 0.05 (legged_robot_dtc.py:134, `spacing = 0.05`) whatever the
+tables' real spacing.  The reference decodes the observation by gathering from the tables repeated four times, so it
+is defined only where NY <= 4*NX and NX <= 4*NY; plan() asserts that.
 """
 import numpy as np
 
 from . import quat
 
 F = np.float32
-NX, NY, NP = 33, 21, 693
 _BFLY = [np.arange(64) ^ o for o in (1, 2, 4, 8, 16, 32)]
 
 
 def wave_sum(v, valid=None):
-    """Sum over the last axis (693) in the kernel's canonical order.  v [N,693] float32.
-    Lane k owns the float4 chunks q = k + 64 j (elements 4q .. 4q+3, zero past 693) and keeps two running sums --
+    """Sum over the last axis (P points) in the kernel's canonical order.  v [N,P] float32.
+    Lane k owns the float4 chunks q = k + 64 j while 4q < P (elements 4q .. 4q+3, zero past P) and keeps two running sums --
     elements 0, 2 of every chunk in one, elements 1, 3 in the other (a packed add), chunks in ascending j, both
     starting from +0 -- adds the two, and the 64 lane sums are folded by the xor-butterfly."""
-    n = v.shape[0]
+    n, NP = v.shape
     nch = (NP + 255) // 256
     pad = np.zeros((n, nch * 256), dtype=F)
     pad[:, :NP] = v
@@ -55,7 +59,7 @@ def plan(measured_heights, root_states, thigh_pos, commands, points_x, points_y,
          t_stance=0.02, fdbk_gain=0.03, want_debug=False):
     """All inputs float32 numpy.  Returns dict with idx [N,4] int64, foothold_obs [N,8],
     optimal_footholds_world [N,4,3], pred_footholds [N,4,3], pred_footholds_to_robot [N,4,3]
-    (+ foothold_score [N,693,4], nominal_idx [N,4], slope [N,33,21] when want_debug)."""
+    (+ foothold_score [N,P,4], nominal_idx [N,4], slope [N,NX,NY] when want_debug)."""
     mh = np.ascontiguousarray(measured_heights, dtype=F)
     rs = np.asarray(root_states, dtype=F)
     th = np.asarray(thigh_pos, dtype=F)
@@ -63,6 +67,10 @@ def plan(measured_heights, root_states, thigh_pos, commands, points_x, points_y,
     X = np.asarray(points_x, dtype=F)
     Y = np.asarray(points_y, dtype=F)
     N = mh.shape[0]
+    NX, NY = len(X), len(Y)
+    NP = NX * NY
+    assert NX >= 2 and NY >= 2 and mh.shape[1] == NP, (mh.shape, NX, NY)
+    assert NY <= 4 * NX and NX <= 4 * NY, "the reference's decode gathers from tables repeated four times"
     base = rs[:, 0:3]
     q = rs[:, 3:7]
 
@@ -120,8 +128,7 @@ def plan(measured_heights, root_states, thigh_pos, commands, points_x, points_y,
     idx = np.argmin(tot, axis=1).astype(np.int64)      # first occurrence == lowest index on ties
 
     # ---- decode (:184-201)
-    Ytile = np.tile(Y, 4)
-    obs = np.concatenate([X[idx % NY], Ytile[idx // NY]], axis=1).astype(F)
+    obs = np.concatenate([np.tile(X, 4)[idx % NY], np.tile(Y, 4)[idx // NY]], axis=1).astype(F)
     rows = np.arange(N)[:, None]
     world = np.stack([hx[rows, idx], hy[rows, idx], mh[rows, idx]], axis=2).astype(F)
     out = dict(idx=idx, foothold_obs=obs, optimal_footholds_world=world, pred_footholds=pred,

@@ -32,3 +32,124 @@ def scorer_extra_inputs(tag):
     return inp
 
 
+# ---------------------------------------------------------------------------------------- planner on other grids
+def _lin(a, b, n):
+    import numpy as np
+    return np.linspace(a, b, n).astype(np.float32)
+
+
+def _cubic(half, n):
+    """Non-uniform table, denser in the centre: half * (t + t^3) / 2 for t = linspace(-1, 1, n)."""
+    import numpy as np
+    t = np.linspace(-1.0, 1.0, n)
+    return (half * 0.5 * (t + t ** 3)).astype(np.float32)
+
+
+def planner_grid(name):
+    """(points_x, points_y) float32 of the grids the generic planner is tested on (tests/test_hip_planner_grids.py says
+    what each one exercises).  All lie inside the range where the reference's decode is defined (ny <= 4 nx, nx <= 4 ny)."""
+    import numpy as np
+    ref_x = np.asarray(S.MEASURED_POINTS_X, dtype=np.float32)
+    ref_y = np.asarray(S.MEASURED_POINTS_Y, dtype=np.float32)
+
+    def centred(nx, ny, d):
+        return _lin(-d * (nx - 1) / 2, d * (nx - 1) / 2, nx), _lin(-d * (ny - 1) / 2, d * (ny - 1) / 2, ny)
+
+    table = {
+        "17x11@0.05": lambda: centred(17, 11, 0.05),
+        "17x11@0.1": lambda: (_lin(-0.8, 0.8, 17), _lin(-0.5, 0.5, 11)),           # stock legged_gym
+        "9x8@0.05": lambda: centred(9, 8, 0.05),
+        "9x7@0.05": lambda: centred(9, 7, 0.05),
+        "13x9@0.047": lambda: centred(13, 9, 0.047),
+        "13x9@0.046": lambda: centred(13, 9, 0.046),
+        "2x2": lambda: centred(2, 2, 0.05),
+        "8x16@0.05": lambda: centred(8, 16, 0.05),
+        "63x32@0.025": lambda: centred(63, 32, 0.025),
+        "64x32@0.025": lambda: centred(64, 32, 0.025),
+        "33x21": lambda: (ref_x, ref_y),
+        "33x21-cubic": lambda: (_cubic(0.8, 33), _cubic(0.5, 21)),
+        "33x21-reversed": lambda: (ref_x[::-1].copy(), ref_y[::-1].copy()),
+    }
+    return table[name]()
+
+
+PLANNER_KINDS = ("random", "border", "rough", "exceptions", "flat")
+
+
+def planner_inputs(N, X, Y, seed, kind="random"):
+    """Mock env state for the planner on the grid (X, Y), in the manner of S.scorer_inputs: root_states [N,13],
+    thigh_pos [N,4,3], commands [N,4], measured_heights [N, len(X) * len(Y)] (stepping stones, quantised to 0.005).
+    The thigh offsets are scaled to the grid's extent (0.17 / 0.8 and 0.1 / 0.5 of the half extents, the reference
+    robot on the reference grid) so that most nominal footholds fall inside it.  `kind` as the stress cases of
+    tests/test_hip_kernels.py: border (fast base and commands push the nominal footholds to and past the border), rough
+    (large random steps: most candidates invalid), exceptions (heights more than 1 m off the base), flat (exact ties)."""
+    import math
+    import numpy as np
+    X, Y = np.asarray(X, dtype=np.float32), np.asarray(Y, dtype=np.float32)
+    P = len(X) * len(Y)
+    cx, cy = 0.5 * float(X.max() + X.min()), 0.5 * float(Y.max() + Y.min())
+    hx, hy = 0.5 * float(X.max() - X.min()), 0.5 * float(Y.max() - Y.min())
+    g = torch.Generator().manual_seed(seed)
+    ru = lambda *s: torch.rand(*s, generator=g)               # noqa: E731
+    rn = lambda *s: torch.randn(*s, generator=g)              # noqa: E731
+    root = torch.zeros(N, 13)
+    root[:, 0] = 20.0 + 40.0 * ru(N)
+    root[:, 1] = 20.0 + 10.0 * ru(N)
+    root[:, 2] = 0.3 + 0.3 * ru(N)
+    yaw = (2 * ru(N) - 1) * math.pi
+    q = torch.stack([0.05 * rn(N), 0.05 * rn(N), torch.sin(yaw / 2), torch.cos(yaw / 2)], dim=1)
+    root[:, 3:7] = q / q.norm(dim=1, keepdim=True)
+    root[:, 7:13] = 0.5 * rn(N, 6)
+    commands = 0.5 * rn(N, 4)
+    ox, oy = 0.2125 * hx, 0.2 * hy
+    off = torch.tensor([[cx + ox, cy + oy], [cx + ox, cy - oy], [cx - ox, cy + oy], [cx - ox, cy - oy]])
+    c, s = torch.cos(yaw), torch.sin(yaw)
+    thigh = torch.empty(N, 4, 3)
+    thigh[:, :, 0] = root[:, None, 0] + c[:, None] * off[None, :, 0] - s[:, None] * off[None, :, 1]
+    thigh[:, :, 1] = root[:, None, 1] + s[:, None] * off[None, :, 0] + c[:, None] * off[None, :, 1]
+    thigh[:, :, 2] = root[:, None, 2]
+    flat = ru(N, P) < 0.7
+    steps = torch.randint(-400, 20, (N, P), generator=g).float() * 0.005
+    # 0.3225, not the 0.32 of S.scorer_inputs: base-relative heights of -0.32 + 0.005 k sit EXACTLY on the +-1.0 exception
+    # and +-0.5 clamp thresholds for some k, where the side taken is a matter of the last float32 bit of (mh - base z) and
+    # no property of the planner (a float64 reference then disagrees by a whole score class); half a quantum off, none does
+    heights = (root[:, 2:3] - 0.3225) + torch.where(flat, torch.zeros_like(steps), steps)
+    if kind == "border":
+        root[:, 7:10] *= 12.0 * hx / 0.8
+        commands[:, :2] *= 8.0 * hx / 0.8
+        thigh[:, :, :2] += (hx / 0.8) * 0.5 * (ru(N, 4, 2) - 0.5)
+    elif kind == "rough":
+        heights = heights + 0.25 * (ru(N, P) - 0.5) * (ru(N, 1) < 0.5)
+    elif kind == "exceptions":
+        heights = torch.where(ru(N, P) < 0.4, heights + 3.0, heights)
+    elif kind == "flat":
+        heights = (root[:, 2:3] - 0.3).expand(N, P)
+    else:
+        assert kind == "random", kind
+    return dict(root_states=root, thigh_pos=thigh.contiguous(), commands=commands, measured_heights=heights.contiguous())
+
+
+# the two grids of tests/golden/scorer_grids.npz, 512 envs each: (tag, grid name, kinds mixed over the envs, seed)
+SCORER_GRID_CASES = (("g17x11", "17x11@0.1", 9101), ("g8x16", "8x16@0.05", 9102))
+
+
+def scorer_grid_inputs(tag):
+    """Inputs of one `scorer_grids` fixture case: 512 envs, the five kinds in blocks (random 256, then 64 of each other)."""
+    name, seed = {t: (n, s) for t, n, s in SCORER_GRID_CASES}[tag]
+    X, Y = planner_grid(name)
+    parts = [planner_inputs(256, X, Y, seed, "random")] + [planner_inputs(64, X, Y, seed + 1 + i, k)
+                                                          for i, k in enumerate(PLANNER_KINDS[1:])]
+    return X, Y, {k: torch.cat([p[k] for p in parts]).contiguous() for k in parts[0]}
+
+
+# every grid of tests/test_hip_planner_grids.py / tests/test_planner_grid_oracle.py, and the (N, kind, seed) cases run on each
+PLANNER_GRIDS = ("17x11@0.05", "17x11@0.1", "9x8@0.05", "9x7@0.05", "13x9@0.047", "13x9@0.046", "2x2", "8x16@0.05",
+                 "63x32@0.025", "64x32@0.025", "33x21", "33x21-cubic", "33x21-reversed")
+
+
+def planner_cases(name):
+    """N in {1, 3, 5, 257}: a partial workgroup of the generic kernel (4 envs each), a full one plus a tail, and many;
+    the two largest grids N in {1, 5} only.  Every N with every kind, each under a seed of its own."""
+    gi = PLANNER_GRIDS.index(name)
+    ns = (1, 5) if name.startswith(("63x32", "64x32")) else (1, 3, 5, 257)
+    return [(N, kind, 7000 + 100 * gi + 10 * ni + ki) for ni, N in enumerate(ns) for ki, kind in enumerate(PLANNER_KINDS)]

@@ -1,7 +1,7 @@
 """Generate the committed golden fixtures by RUNNING THE REFERENCE (read-only import from
 /root/reference) on the deterministic synthetic inputs of dtc_amd.synthetic.
 
-    python tests/golden/make_golden.py [gae ppo scorer heights init gru lstm composite observations]
+    python tests/golden/make_golden.py [gae ppo scorer scorer_grids heights init gru lstm composite observations]
 
 Runs only in the build container (the reference does not exist on the GPU box).  The fixtures
 hold outputs only -- inputs are regenerated from seeds on the test side -- so they stay small.
@@ -239,13 +239,20 @@ def gen_init():
 
 
 # ------------------------------------------------------------------------------------ G4
-def _ref_scorer(inp):
+def _ref_scorer(inp, grid=None):
+    """`grid` = (points_x, points_y): run the reference on another measurement grid (cfg.terrain.measured_points_x / _y,
+    measured_y_dim and the env's height_points overridden on the instance)."""
     from legged_gym.envs.base.legged_robot_dtc import LeggedRobotDTC
     from legged_gym.envs.lite3.lite3_dtc_config import Lite3DTCCfg
     N = inp["root_states"].shape[0]
     noop = lambda *a, **k: None
     m = types.SimpleNamespace()
     m.cfg, m.num_envs, m.device, m.num_bodies = Lite3DTCCfg(), N, "cpu", 17
+    if grid is not None:
+        m.cfg.terrain = type(m.cfg.terrain)()                     # the instance's own copy: the class keeps the reference's grid
+        m.cfg.terrain.measured_points_x = [float(v) for v in grid[0]]
+        m.cfg.terrain.measured_points_y = [float(v) for v in grid[1]]
+        m.cfg.terrain.measured_y_dim = len(grid[1])
     m.gym = types.SimpleNamespace(refresh_actor_root_state_tensor=noop, refresh_net_contact_force_tensor=noop,
                                   refresh_rigid_body_state_tensor=noop)
     m.sim = m.viewer = None
@@ -263,6 +270,11 @@ def _ref_scorer(inp):
     rbs[:, m.thigh_indices, 0:3] = inp["thigh_pos"]
     m.rigid_body_state = rbs.view(N * 17, 13)
     m.height_points = S.height_points().unsqueeze(0).repeat(N, 1, 1)
+    if grid is not None:                                          # legged_robot.py:1263-1277 (_init_height_points)
+        gx, gy = torch.meshgrid(torch.tensor(m.cfg.terrain.measured_points_x), torch.tensor(m.cfg.terrain.measured_points_y), indexing="ij")
+        pts = torch.zeros(N, gx.numel(), 3)
+        pts[:, :, 0], pts[:, :, 1] = gx.flatten(), gy.flatten()
+        m.height_points = pts
     m.measured_heights = inp["measured_heights"].clone()
     for k in ("_post_physics_step_callback", "check_termination", "compute_reward", "reset_idx",
               "compute_observations"):
@@ -328,6 +340,36 @@ def gen_scorer():
     out["rew_tracking"] = LeggedRobotDTC._reward_tracking_optimal_footholds(mock).numpy()
     out["rew_miss"] = LeggedRobotDTC._reward_foothold_miss(mock).numpy()
     save("scorer", **out)
+
+
+def gen_scorer_grids():
+    """The planner block of the reference on two other measurement grids (cases.SCORER_GRID_CASES: stock legged_gym
+    17 x 11 at 0.1 m, and 8 x 16 at 0.05 m where ny > nx wraps the decode), 512 envs each; recorded as gen_scorer does."""
+    torch.set_num_threads(GOLDEN_THREADS)
+    from cases import SCORER_GRID_CASES, scorer_grid_inputs
+    from oracle import foothold as OF
+    out = {}
+    for tag, _, _ in SCORER_GRID_CASES:
+        X, Y, inp = scorer_grid_inputs(tag)
+        m = _ref_scorer(inp, grid=(X, Y))
+        sc = m.foothold_score.numpy()
+        srt = np.sort(sc, axis=1)
+        out[tag + "_idx"] = m.optimal_foothold_indice.squeeze(1).numpy().astype(np.int16)
+        out[tag + "_gap"] = (srt[:, 1, :] - srt[:, 0, :]).astype(np.float32)
+        out[tag + "_nominal_idx"] = m.nominal_footholds_indice.numpy().astype(np.int16)
+        out[tag + "_foothold_obs"] = m.foothold_obs.numpy()[::4]
+        out[tag + "_world"] = m.optimal_footholds_world.numpy()[::4]
+        out[tag + "_pred"] = m.pred_footholds.numpy()[::4]
+        out[tag + "_pred_to_robot"] = m.pred_footholds_to_robot.numpy()[::4]
+        out[tag + "_slope_sample"] = m.slope.numpy()[::64]
+        out[tag + "_score_sample"] = sc[::64]
+        # the cap the tests assert (<= 4 knife-edge mismatches per case), verified here against the oracle
+        o = OF.plan(inp["measured_heights"].numpy(), inp["root_states"].numpy(), inp["thigh_pos"].numpy(), inp["commands"].numpy(), X, Y)
+        mism = np.argwhere(o["idx"] != out[tag + "_idx"].astype(np.int64))
+        print(f"{tag}: oracle differs from the reference on {len(mism)} (env, leg) pairs; gaps",
+              [float(out[tag + "_gap"][e, l]) for e, l in mism])
+        assert len(mism) <= 4 and all(out[tag + "_gap"][e, l] <= 1e-5 for e, l in mism)
+    save("scorer_grids", **out)
 
 
 # ------------------------------------------------------------------------------------ G6
@@ -615,7 +657,7 @@ def gen_composite():
     save("composite", **out)
 
 
-TASKS = dict(lstm=gen_lstm, teacher=gen_teacher, student=gen_student, observations=gen_observations, composite=gen_composite, gru=gen_gru, gae=gen_gae, ppo=gen_ppo, init=gen_init, scorer=gen_scorer, heights=gen_heights)
+TASKS = dict(scorer_grids=gen_scorer_grids, lstm=gen_lstm, teacher=gen_teacher, student=gen_student, observations=gen_observations, composite=gen_composite, gru=gen_gru, gae=gen_gae, ppo=gen_ppo, init=gen_init, scorer=gen_scorer, heights=gen_heights)
 
 if __name__ == "__main__":
     for t in (sys.argv[1:] or list(TASKS)):

@@ -274,6 +274,26 @@ def test_env_post_physics_other_grid_and_bad_arguments():
                                        d["height_noise_offset"], d["u_obs"], d["noise_scale_vec"], d["u_heights"], cfg)
     assert torch.equal(got["optimal_foothold_indice"], p["optimal_foothold_indice"]) and torch.equal(got["reset_buf"].bool(), reset)
     assert torch.equal(got["height_mean"], mean) and torch.equal(got["privileged_obs_buf"], ob["privileged_obs_buf"])
+    # ... and the planner part equals the oracle on that grid; with the terrain table as input, heights + plan
+    from oracle import foothold as OF, heights as OH
+    npy = lambda t: t.cpu().numpy()                                                                  # noqa: E731
+    o = OF.plan(npy(mh), npy(d["root_states"]), npy(d["thigh_pos"]), npy(d["commands"][:, :4]), grid.points_x, grid.points_y)
+    for res in (got, p):
+        np.testing.assert_array_equal(npy(res["optimal_foothold_indice"]).squeeze(1), o["idx"])
+        np.testing.assert_array_equal(npy(res["foothold_obs"]), o["foothold_obs"])
+        np.testing.assert_array_equal(npy(res["optimal_footholds_world"]), o["optimal_footholds_world"])
+        np.testing.assert_array_equal(npy(res["pred_footholds"]), o["pred_footholds"])
+        np.testing.assert_array_equal(npy(res["pred_footholds_to_robot"]), o["pred_footholds_to_robot"])
+    gen = torch.Generator().manual_seed(31)
+    coarse = torch.randint(-60, 120, (110, 70), generator=gen)
+    tab = (coarse.repeat_interleave(16, 0).repeat_interleave(16, 1) + torch.randint(-2, 3, (1760, 1120), generator=gen)).to(torch.int16)
+    got_t = foothold.EnvStep(N, DEV, grid=grid, cfg=cfg)(max_episode_length=1000, height_samples=tab.to(DEV), **_fused_kwargs(d, True))
+    ref_h = OH.get_heights(tab.numpy(), npy(d["root_states"]), grid.points_x, grid.points_y)
+    np.testing.assert_array_equal(npy(got_t["measured_heights"]), ref_h)
+    o = OF.plan(ref_h, npy(d["root_states"]), npy(d["thigh_pos"]), npy(d["commands"][:, :4]), grid.points_x, grid.points_y)
+    np.testing.assert_array_equal(npy(got_t["optimal_foothold_indice"]).squeeze(1), o["idx"])
+    np.testing.assert_array_equal(npy(got_t["foothold_obs"]), o["foothold_obs"])
+    np.testing.assert_array_equal(npy(got_t["optimal_footholds_world"]), o["optimal_footholds_world"])
     with pytest.raises(ValueError):
         step(max_episode_length=1000, **_fused_kwargs(d, True))                        # neither heights nor a table
     bad = foothold.EnvStep(N, DEV, cfg=foothold.ObsConfig(num_foothold_obs=4))

@@ -112,8 +112,20 @@ def test_scorer_matches_reference_golden(golden):
     h = foothold.plan(inp["measured_heights"], inp["root_states"], inp["thigh_pos"], inp["commands"])
     idx = _np(h["optimal_foothold_indice"]).squeeze(1)
     ref = g["main_idx"].astype(np.int64)
-    for e, l in np.argwhere(idx != ref):
-        assert g["main_gap"][e, l] <= 1e-5
+    mism = np.argwhere(idx != ref)
+    # the oracle alone differs from this fixture on 0 of the 32768 (env, leg) pairs (measured on the CPU), and the kernel
+    # equals the oracle bit for bit: no knife-edge allowance is needed here
+    assert len(mism) <= 0, mism
+    if len(mism):         # what a raised bound would have to satisfy: the kernel's choice is a near-minimum of the oracle's table
+        from oracle import foothold as OF
+        rows = np.unique(mism[:, 0])
+        c = {k: v.cpu() for k, v in inp.items()}
+        o = OF.plan(*(_np(c[k])[rows] for k in ("measured_heights", "root_states", "thigh_pos", "commands")),
+                    S.MEASURED_POINTS_X, S.MEASURED_POINTS_Y, want_debug=True)
+        for e, l in mism:
+            r = int(np.searchsorted(rows, e))
+            assert g["main_gap"][e, l] <= 1e-5
+            assert o["foothold_score"][r, ref[e, l], l] - o["foothold_score"][r, idx[e, l], l] <= 1e-5
     np.testing.assert_allclose(_np(h["pred_footholds"])[::4], g["main_pred"], rtol=0, atol=4e-6)
 
 
@@ -225,6 +237,13 @@ def test_plan_from_table_other_grid_runs_the_two_launches():
     two = foothold.plan(mh, inp["root_states"], inp["thigh_pos"], inp["commands"], grid=grid)
     assert torch.equal(fused["measured_heights"], mh)
     assert torch.equal(fused["optimal_foothold_indice"], two["optimal_foothold_indice"])
+    # ... and both equal the oracle (heights + plan) on that grid
+    from oracle import foothold as OF, heights as OH
+    ref_h = OH.get_heights(_np(tab), _np(inp["root_states"]), grid.points_x, grid.points_y)
+    np.testing.assert_array_equal(_np(fused["measured_heights"]), ref_h)
+    o = OF.plan(ref_h, _np(inp["root_states"]), _np(inp["thigh_pos"]), _np(inp["commands"]), grid.points_x, grid.points_y)
+    _assert_scorer_equal(o, fused, debug=False)
+    _assert_scorer_equal(o, two, debug=False)
 
 
 def test_patch_env_hooks_write_the_reference_attributes():
