@@ -221,6 +221,12 @@ class DtcSimContacts(C.Structure):
                 [("reserved", C.c_int32)])
 
 
+class DtcSimBalance(C.Structure):
+    """include/dtc_hip.h: the constants and the two state tensors of dtc_sim_balance (support-polygon balance, falls); field order as there."""
+    _fields_ = ([("lean", C.c_void_p), ("fallen", C.c_void_p)] +
+                [(k, C.c_float) for k in ("gravity", "h_min", "lean_eps", "fall_angle", "fall_force", "dt")] + [("com_offset", C.c_float * 2)])
+
+
 class DtcTerrainCfg(C.Structure):
     """include/dtc_hip.h: the configuration of dtc_terrain_generate; field order as there."""
     _fields_ = ([(k, C.c_double) for k in ("horizontal_scale", "vertical_scale", "border_size", "terrain_length", "terrain_width")] +
@@ -290,6 +296,8 @@ _SIGS = {
                                    C.POINTER(DtcSimFlight), C.c_int, c_stream]),
     "dtc_sim_contact_abi_sizes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
     "dtc_sim_contacts": (C.c_int, [C.POINTER(DtcSimStep), C.POINTER(DtcSimCfg), C.POINTER(DtcSimContacts), C.c_int, c_stream]),
+    "dtc_sim_balance_abi_sizes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
+    "dtc_sim_balance": (C.c_int, [C.POINTER(DtcSimStep), C.POINTER(DtcSimCfg), C.POINTER(DtcSimBalance), C.c_int, c_stream]),
     "dtc_terrain_abi_sizes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
     "dtc_terrain_generate": (C.c_int, [C.POINTER(DtcTerrainCfg), C.c_void_p, C.c_void_p, c_stream]),
     "dtc_check_termination": (C.c_int, [c_f32p, C.c_int, c_i32p, C.c_int, c_i64p, C.c_int64, c_f32p, c_f32p, c_f32p,
@@ -517,7 +525,10 @@ def _check_abi(l):
     mine += [DtcSimContacts]                                              # ... and by its contact entry point's
     n = l.dtc_sim_contact_abi_sizes(sizes, 32)
     theirs += list(sizes[:n])
-    mine += [DtcTerrainCfg]                                               # ... and by the terrain generator's
+    mine += [DtcSimBalance]                                               # ... and by its balance entry point's
+    n = l.dtc_sim_balance_abi_sizes(sizes, 32)
+    theirs += list(sizes[:n])
+    mine += [DtcTerrainCfg]                                            # ... and by the terrain generator's
     n = l.dtc_terrain_abi_sizes(sizes, 32)
     theirs += list(sizes[:n])
     if l.dtc_version() != ABI_VERSION or theirs != [C.sizeof(t) for t in mine]:

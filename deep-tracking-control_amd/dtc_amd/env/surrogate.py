@@ -37,6 +37,17 @@ through the tensors they already read (`CONTACT_SCALES` holds scales for the fir
 env then owns `leg_contact` [N,8] and `stumbled` [N,4] uint8.  The forces feed the rewards and nothing else: a colliding shank is
 not held back, a stumbling foot is not stopped but lifted onto the riser as before, nothing topples, the torso has no contact of
 its own, and every constant is a choice.
+
+`SimConfig.balance` (opt-in, a `sim.BalanceConfig`; None: the env above, bit for bit, nothing new allocated or launched) runs
+`dtc_sim_balance` between the surrogate step and `dtc_sim_contacts`: a point-mass inverted pendulum about the edge of the support
+polygon of the stance feet.  A base whose xy leaves the support of its stance feet leans, faster the further it leans; over its
+support a lean is restored and lands.  The lean is laid over `base_quat`, `root_states`, `projected_gravity`, `base_lin_vel`,
+`base_ang_vel`, `base_pos` and the base row of `rigid_body_state`, so the `orientation`, `ang_vel_xy` and base-height terms see it
+(`BALANCE_SCALES` holds scales for a caller to add), and a lean beyond `fall_angle` ends the episode through the base's contact
+force and check_termination.  The env then owns `lean` [N,4] float32 (cleared by a reset) and `fallen` [N] uint8, and
+`extras["episode"]["fall_rate"]` is the share of envs that fell in the step (a device scalar).  Still a surrogate: the link
+positions are not rotated (planner and contacts see the un-leaned feet and hips), pushes do not feed the lean rate, there
+is no friction and no slipping pivot, crossed feet are neglected, and every constant is a choice.
 """
 from __future__ import annotations
 
@@ -56,6 +67,9 @@ _SCALES = dict(action_rate=-0.01, ang_vel_xy=-0.005, dof_acc=-2.5e-8, dof_pos_li
 # the two terms `SimConfig.contacts` gives an input to, for a caller to add to `reward_scales` (the default set is not touched):
 # collision is the Lite3 DTC value (lite3_dtc_config.py:161), stumble is a choice of this project
 CONTACT_SCALES = dict(collision=-1.5, stumble=-0.5)
+# the two terms that read what `SimConfig.balance` writes, likewise for a caller to add: the Lite3 DTC values
+# (lite3_dtc_config.py:150, :162); the default set is not touched
+BALANCE_SCALES = dict(orientation=-0.5, termination=-0.1)
 
 
 @dataclass
@@ -189,6 +203,10 @@ class SurrogateLeggedEnv(VecEnv):
         if s.contacts is not None:
             self.leg_contact, self.stumbled = torch.zeros(N, 8, dtype=torch.uint8, device=dev), torch.zeros(N, 4, dtype=torch.uint8, device=dev)
             self._contact_flags = (self.leg_contact, self.stumbled)
+        self._balance_rows = ()
+        if s.balance is not None:
+            self.lean, self.fallen = z(N, 4), torch.zeros(N, dtype=torch.uint8, device=dev)
+            self._balance_rows = (self.lean,)
         self.last_contacts = torch.zeros(N, 4, dtype=torch.bool, device=dev)
         self.contact_filt = torch.zeros(N, 4, dtype=torch.bool, device=dev)
         self.robot_mass = torch.full((N,), float(s.mass), **f)
@@ -257,7 +275,7 @@ class SurrogateLeggedEnv(VecEnv):
                        base_lin_vel_last=self.base_lin_vel_last, episode_length_buf=self.episode_length_buf, contact_filt=self.contact_filt,
                        last_contacts=self.last_contacts, lin_vel_buffer=self.lin_vel_buffer, ang_vel_buffer=self.ang_vel_buffer,
                        cmd_buffer=self.cmd_buffer, u=draws.get("u_reset"), command_ranges=self.command_ranges,
-                       extra_rows=self._actuator_rows,
+                       extra_rows=self._actuator_rows + self._balance_rows,
                        height_noise=float(self._height_noise.normal(0, 0.02)) if hn is None else float(hn))
 
     def step(self, actions: torch.Tensor, draws: dict | None = None):
@@ -271,6 +289,8 @@ class SurrogateLeggedEnv(VecEnv):
             push = s.actuator.push and self.common_step_counter % s.push_interval in (0, 1)
             self.sim.step(self, actions.to(self.device, torch.float32).contiguous(), draws.get("u_cmd"), lag_choice=draws.get("lag_choice"),
                           u_push=draws.get("u_push"), push=push)
+        if s.balance is not None:                                                        # the lean over the support polygon, and falls
+            self.sim.balance(self)
         if s.contacts is not None:                                                       # leg collisions and stumbles, on what the step wrote
             self.sim.contacts(self)
         if s.heading_command:                                                            # legged_robot.py:537-539
@@ -288,12 +308,14 @@ class SurrogateLeggedEnv(VecEnv):
             # sums and every later step: its rows are zeroed here, ahead of every consumer, and it is reset in this step
             bad = ~(torch.isfinite(self.dof_state).flatten(1).all(dim=1) & torch.isfinite(self.root_states).all(dim=1))
             for t in (self.dof_state, self.root_states, self.rigid_body_state, self.contact_forces, self.torques, self.base_lin_vel,
-                      self.base_ang_vel, self.last_base_ang_vel, self.base_pos, self.base_quat) + self._actuator_rows:
+                      self.base_ang_vel, self.last_base_ang_vel, self.base_pos, self.base_quat) + self._actuator_rows + self._balance_rows:
                 t.masked_fill_(bad.view(-1, *([1] * (t.dim() - 1))), 0.0)
             for t in (self.lin_vel_buffer, self.ang_vel_buffer, self.cmd_buffer):
                 t.masked_fill_(bad.view(1, -1, 1), 0.0)
             for t in self._contact_flags:
                 t.masked_fill_(bad.view(-1, 1), 0)
+            if s.balance is not None:
+                self.fallen.masked_fill_(bad, 0)
         self.foot_positions = self.rigid_body_state[:, self.feet_indices, 0:3]
         self.foot_velocities = self.rigid_body_state[:, self.feet_indices, 7:10]
         self.hip_positions = self.rigid_body_state[:, self.thigh_indices, 0:3]
@@ -338,6 +360,8 @@ class SurrogateLeggedEnv(VecEnv):
         self.obs_buf = torch.clip(self._out["obs_buf"], -c.clip_observations, c.clip_observations)
         self.privileged_obs_buf = torch.clip(self._out["privileged_obs_buf"], -c.clip_observations, c.clip_observations)
         self.extras = {"time_outs": self.time_out_buf.bool(), "episode": dict(self._episode)}
+        if s.balance is not None:
+            self.extras["episode"]["fall_rate"] = self.fallen.float().mean()
         return self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf.bool(), self.extras
 
     # ------------------------------------------------------------------ the rest of the env contract

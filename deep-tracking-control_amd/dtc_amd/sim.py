@@ -13,7 +13,11 @@ not a contact dynamics.  `SimConfig.flight` (opt-in, a `FlightConfig`) gives the
 falls away falls under gravity and lands when it reaches a support, and a support that rises by more than a climbable step is a
 crash that ends the episode through the base contact force.  `SimConfig.contacts` (opt-in, a `ContactConfig`) adds a second launch,
 `dtc_sim_contacts` (csrc/sim_contacts.hip), behind the step: contact forces of thighs and shanks that penetrate the terrain and of a
-swing foot that flies into a riser, for the reward terms that read them.  Nothing is held back by those forces and nothing topples.
+swing foot that flies into a riser, for the reward terms that read them.  Nothing is held back by those forces and nothing topples
+unless `SimConfig.balance` (opt-in, a `BalanceConfig`) is set: a further launch, `dtc_sim_balance` (csrc/sim_balance.hip), between
+the step and the contacts, a point-mass inverted pendulum about the edge of the support polygon of the stance feet whose lean is
+laid over the base's attitude, height and angular velocity and, beyond `fall_angle`, ends the episode through the base's contact
+force.  An overlay, not attitude dynamics: it rotates no link, knows no friction and takes no push.
 
 `SimConfig` holds the constants (Lite3 DTC values), `leg_tables(config)` the three small tables computed once in float64 from a
 two-link leg linearised at the default pose, and `SimStep` runs the launch on an env's own tensors (attribute names as in
@@ -132,6 +136,42 @@ class ContactConfig:
 
 
 @dataclass
+class BalanceConfig:
+    """Support-polygon balance and falls of `dtc_sim_balance` (include/dtc_hip.h states the operations B1..B9), a launch of its own
+    behind the step and in front of `dtc_sim_contacts`.  A point-mass inverted pendulum about the edge of the support of the
+    stance feet (four or three: the polygon in the order FL, FR, HR, HL; two: the segment; one: the point; none: no torque): a lean
+    vector [rad, world frame] accelerates away from the support while the base's xy (plus `com_offset`, base frame) lies outside it,
+    is restored while inside and lands at zero, and is laid over the attitude, height and angular velocity the step wrote.  A lean
+    beyond `fall_angle` is a fall: the base takes the contact force `fall_force`, which must exceed the termination threshold
+    (100 N), so check_termination ends the episode as it ends a fall in the reference.  The pendulum's length is the base's height
+    over the highest stance foot, floored at `h_min`; a lean over its support shorter than `lean_eps` lands.  What it is not: the
+    link positions are not rotated (planner and contacts see the un-leaned feet and hips; the contacts' knee turns with the leaned
+    quaternion), pushes do not feed the lean rate, there is no friction and no slipping pivot, crossed feet are neglected.  Every constant is a free choice of the
+    surrogate, fitted to nothing: 0.8 rad is past any attitude a quadruped recovers from, 200 N is twice the threshold, 0.05 m
+    keeps a crouched base a pendulum of finite rate, 1e-3 rad is under every observation noise."""
+    gravity: float = 9.81
+    h_min: float = 0.05                      # m, floor of the pendulum's length
+    lean_eps: float = 1e-3                   # rad, a lean over its support shorter than this lands
+    fall_angle: float = 0.8                  # rad, a lean beyond it is a fall
+    fall_force: float = 200.0                # N, the base's contact force of a fallen env
+    com_offset: tuple = (0.0, 0.0)           # m, base frame: the centre of mass relative to the base's origin
+
+    def validate(self):
+        for name in ("h_min", "fall_angle", "fall_force"):
+            v = getattr(self, name)
+            if not (v > 0 and math.isfinite(v)):
+                raise ValueError(f"BalanceConfig: {name} {v} must be positive and finite")
+        if not self.fall_force > TERMINATION_FORCE:
+            raise ValueError(f"BalanceConfig: fall_force {self.fall_force} must exceed the termination threshold of {TERMINATION_FORCE} N")
+        for name in ("gravity", "lean_eps"):
+            v = getattr(self, name)
+            if not (v >= 0 and math.isfinite(v)):
+                raise ValueError(f"BalanceConfig: {name} {v} must be finite and not negative")
+        if len(self.com_offset) != 2 or not all(math.isfinite(v) for v in self.com_offset):
+            raise ValueError(f"BalanceConfig: com_offset {self.com_offset} must be two finite numbers")
+
+
+@dataclass
 class SimConfig:
     """Constants of the surrogate step (names as in DtcSimCfg, include/dtc_hip.h); defaults: the Lite3 DTC values."""
     sim_dt: float = 0.005
@@ -174,6 +214,7 @@ class SimConfig:
     actuator: ActuatorConfig | None = None   # lag buffer and pushes (dtc_sim_step_act); None: the entry points above, bit for bit
     flight: FlightConfig | None = None       # free flight, landing, crashes (dtc_sim_step_fly); None: the entry points above, bit for bit
     contacts: ContactConfig | None = None    # leg collisions, foot stumbles (dtc_sim_contacts, a second launch); None: no such launch
+    balance: BalanceConfig | None = None     # support-polygon balance, falls (dtc_sim_balance, a launch of its own); None: no such launch
 
     @property
     def dt(self) -> float:
@@ -273,6 +314,8 @@ class SimStep:
         if config.contacts is not None:
             config.contacts.validate(config)
             self.knee = {k: torch.as_tensor(v, dtype=torch.float32).to(dev).contiguous() for k, v in knee_tables(config).items()}
+        if config.balance is not None:
+            config.balance.validate()
 
     def cfg_struct(self) -> "_ffi.DtcSimCfg":
         k, c = self.cfg, _ffi.DtcSimCfg()
@@ -394,6 +437,38 @@ class SimStep:
             self._check(name, getattr(env, name), (N, width), torch.uint8)
             setattr(con, name, _ffi.ptr(getattr(env, name)))
         _ffi.check(_ffi.lib().dtc_sim_contacts(s, self.cfg_struct(), con, N, _ffi.stream()), "dtc_sim_contacts")
+
+    def balance(self, env):
+        """`dtc_sim_balance` on the tensors of `env`, as `step` just wrote them: the env's `lean` [N,4] and `fallen` [N] uint8, and
+        with a lean the base's attitude, height and angular velocity in `base_quat`, `root_states`, `base_pos`,
+        `projected_gravity`, `base_lin_vel`, `base_ang_vel`, the base row of `rigid_body_state` and, for a fallen env, of
+        `contact_forces`.  Needs `config.balance`."""
+        k, N = self.cfg, self.N
+        if k.balance is None:
+            raise _ffi.DtcError("SimStep: balance() needs config.balance")
+        B = int(k.num_bodies)
+        s = _ffi.DtcSimStep()
+        for name, tail, dtype in (("root_states", (13,), torch.float32), ("base_pos", (3,), torch.float32), ("base_quat", (4,), torch.float32),
+                                  ("projected_gravity", (3,), torch.float32), ("base_lin_vel", (3,), torch.float32),
+                                  ("base_ang_vel", (3,), torch.float32), ("rigid_body_state", (B, 13), torch.float32),
+                                  ("contact_forces", (B, 3), torch.float32), ("contact_filt", (4,), torch.bool),
+                                  ("episode_length_buf", (), torch.int64)):
+            self._check(name, getattr(env, name), (N,) + tail, dtype)
+            setattr(s, name, _ffi.ptr(getattr(env, name)))
+        bal = self.balance_struct()
+        for name, tail, dtype in (("lean", (4,), torch.float32), ("fallen", (), torch.uint8)):
+            self._check(name, getattr(env, name), (N,) + tail, dtype)
+            setattr(bal, name, _ffi.ptr(getattr(env, name)))
+        _ffi.check(_ffi.lib().dtc_sim_balance(s, self.cfg_struct(), bal, N, _ffi.stream()), "dtc_sim_balance")
+
+    def balance_struct(self) -> "_ffi.DtcSimBalance":
+        """The constants of dtc_sim_balance (the two pointers are left NULL)."""
+        k, b, bal = self.cfg, self.cfg.balance, _ffi.DtcSimBalance()
+        for name in ("gravity", "h_min", "lean_eps", "fall_angle", "fall_force"):
+            setattr(bal, name, float(getattr(b, name)))
+        bal.dt = float(np.float32(float(k.sim_dt) * int(k.decimation)))
+        bal.com_offset[0], bal.com_offset[1] = float(b.com_offset[0]), float(b.com_offset[1])
+        return bal
 
     def contact_struct(self) -> "_ffi.DtcSimContacts":
         """The constants and the two knee tables of dtc_sim_contacts (the two flag pointers are left NULL)."""

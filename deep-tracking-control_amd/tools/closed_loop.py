@@ -13,6 +13,8 @@
                                                                           # the terrain env beside the one with free flight and crashes
     python deep-tracking-control_amd/tools/closed_loop.py --contacts [--out profiles/closed_loop_contacts.txt]
                                                                           # the terrain env beside the one with leg collisions and stumbles
+    python deep-tracking-control_amd/tools/closed_loop.py --balance [--out profiles/closed_loop_balance.txt]
+                                                                          # the terrain env beside the one with support-polygon balance and falls
 
 Per run and iteration: the mean step reward (mean of rew_buf over the iteration's 24 steps and all envs), the mean episode length
 (the runner's tracker: the last <= 100 finished episodes; "-" before the first one ends) and the mean length of the episodes in flight.
@@ -41,6 +43,12 @@ dtc_sim_step beside dtc_sim_contacts, the launch behind it, on that terrain; on 
 env steps with any leg_contact and with any stumbled per family over 200 steps of an untrained policy; and the learning signal: 256
 envs, 30 iterations on a stairs-only terrain with CONTACT_SCALES added to the default scales, the share of env steps with a leg
 collision in iterations 1-5 and in iterations 26-30.  Nothing is asserted and nothing was tuned.
+With --balance the two runs are the env on the generated DTC terrain (the Lite3 grid) without and with
+`SimConfig(balance=BalanceConfig())`, default arithmetic and the default reward scales, the same three interleaved rounds;
+dtc_sim_step beside dtc_sim_balance, the launch behind it, on that terrain; on the 6 x 9 one-family-per-column grid the share of
+env steps that lean, that end fallen and that end in a reset per family over 200 steps of an untrained policy; and the learning
+signal: 256 envs, 30 iterations on the Lite3 terrain with BALANCE_SCALES added to the default scales, the share of env steps
+that end fallen in iterations 1-5 and in iterations 26-30.  Nothing is asserted and nothing was tuned.
 """
 import argparse
 import os
@@ -55,7 +63,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 
 from dtc_amd import sim as SIM, synthetic  # noqa: E402
 from dtc_amd.env import SurrogateConfig, SurrogateLeggedEnv  # noqa: E402
-from dtc_amd.env.surrogate import _SCALES, CONTACT_SCALES  # noqa: E402
+from dtc_amd.env.surrogate import _SCALES, BALANCE_SCALES, CONTACT_SCALES  # noqa: E402
 from dtc_amd.runners import OnPolicyRunner  # noqa: E402
 from dtc_amd.runners.on_policy_runner import _EpisodeTracker  # noqa: E402
 from dtc_amd.terrain import FAMILIES, Terrain, TerrainConfig  # noqa: E402
@@ -69,15 +77,15 @@ def rough_env(num_envs, tilt, actuator=None):
     return SurrogateLeggedEnv(num_envs, DEV, SurrogateConfig(sim=SIM.SimConfig(tilt=tilt, actuator=actuator)), synthetic.reward_table(), seed=5)
 
 
-def make(num_envs, algo, seed=11, tilt=None, terrain=None, steps=STEPS, actuator=None, flight=None, contacts=None, scales=None):
+def make(num_envs, algo, seed=11, tilt=None, terrain=None, steps=STEPS, actuator=None, flight=None, contacts=None, scales=None, balance=None):
     """`tilt` None: the default env on the flat table; False / True: the yaw-only / the tilt env on the rough table (`actuator`, an
     ActuatorConfig: with lag and pushes); `terrain`, a TerrainConfig: the env on the generated terrain (`flight`, a FlightConfig: with
-    free flight, landing and crashes; `contacts`, a ContactConfig: with leg collisions and stumbles; `scales`: reward scales in
-    place of the default set)."""
+    free flight, landing and crashes; `contacts`, a ContactConfig: with leg collisions and stumbles; `balance`, a BalanceConfig: with
+    the support-polygon lean and falls; `scales`: reward scales in place of the default set)."""
     torch.manual_seed(seed)
     if terrain is not None:
         kw = {} if scales is None else dict(reward_scales=dict(scales))
-        env = SurrogateLeggedEnv(num_envs, DEV, SurrogateConfig(sim=SIM.SimConfig(flight=flight, contacts=contacts), terrain=terrain, **kw), seed=5)
+        env = SurrogateLeggedEnv(num_envs, DEV, SurrogateConfig(sim=SIM.SimConfig(flight=flight, contacts=contacts, balance=balance), terrain=terrain, **kw), seed=5)
     else:
         env = SurrogateLeggedEnv(num_envs, DEV, SurrogateConfig(), seed=5) if tilt is None else rough_env(num_envs, tilt, actuator)
     runner = dict(policy_class_name="ActorCriticDecoder", algorithm_class_name="PPO", num_steps_per_env=steps, save_interval=10 ** 9)
@@ -125,8 +133,8 @@ def timed(fn, acc):
     return f
 
 
-def timing_round(num_envs, iters, algo, tilt=None, terrain=None, actuator=None, flight=None, contacts=None):
-    r, env = make(num_envs, algo, tilt=tilt, terrain=terrain, actuator=actuator, flight=flight, contacts=contacts)
+def timing_round(num_envs, iters, algo, tilt=None, terrain=None, actuator=None, flight=None, contacts=None, balance=None):
+    r, env = make(num_envs, algo, tilt=tilt, terrain=terrain, actuator=actuator, flight=flight, contacts=contacts, balance=balance)
     r.learn(2)                                                # warm-up: allocations, first launches
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -531,6 +539,119 @@ def contacts_report(args):
     return lines
 
 
+def balance_probe(num_envs, calls):
+    """dtc_sim_step, then dtc_sim_balance on what it wrote, on the generated Lite3 terrain under random actions: us per call of each
+    (median), and the share of envs that lean and that are fallen at the end."""
+    env = SurrogateLeggedEnv(num_envs, DEV, SurrogateConfig(sim=SIM.SimConfig(balance=SIM.BalanceConfig()), terrain=TerrainConfig(seed=1)), seed=5)
+    g = torch.Generator(device=DEV).manual_seed(3)
+    env.reset()
+    acc = ([], [])
+    for i in range(calls + 20):
+        a, u = torch.randn(num_envs, 12, generator=g, device=DEV), torch.rand(num_envs, 3, generator=g, device=DEV)
+        for t, fn in zip(acc, (lambda: env.sim.step(env, a, u), lambda: env.sim.balance(env))):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if i >= 20:
+                t.append(1e6 * (time.perf_counter() - t0))
+    return (statistics.median(acc[0]), statistics.median(acc[1]), float(env.lean[:, :2].any(dim=1).float().mean()), float(env.fallen.float().mean()))
+
+
+def balance_family_probe(num_envs, steps=200, rollout=25):
+    """An untrained policy on a 6 x 9 grid whose column j is family j, with balance: per family the share of env steps that lean,
+    that end fallen, and that end in a reset.  Rollouts without updates; everything is summed on the device and read once."""
+    cfg = TerrainConfig(num_rows=6, num_cols=9, terrain_proportions=tuple([1 / 9] * 9), seed=1)
+    r, env = make(num_envs, {}, terrain=cfg, steps=rollout, balance=SIM.BalanceConfig())
+    types = env.terrain_types
+    count = torch.bincount(types, minlength=9).double()
+    sums = torch.zeros(3, 9, dtype=torch.float64, device=DEV)
+    inner, leaning = r.env.step, [None]
+    balance = env.sim.balance
+
+    def launch(e):                                            # the lean as the launch leaves it: the reset behind it clears a fallen env's
+        balance(e)
+        leaning[0] = e.lean[:, :2].any(dim=1)
+    env.sim.balance = launch
+
+    def step(actions):
+        out = inner(actions)
+        for row, flag in zip(sums, (leaning[0], env.fallen, out[2])):
+            row.index_add_(0, types, flag.double())
+        return out
+    object.__setattr__(r.env, "step", step)
+    state = dict(obs_dict=r.env.get_observations(), rew_buf=r.env.get_reward_buf())
+    for _ in range(steps // rollout):
+        r._collect(state, None, [])
+        r.alg.storage.clear()
+    return (sums / count / (steps // rollout * rollout)).tolist(), count.tolist()
+
+
+def fall_curve(num_envs=256, iters=30):
+    """The learning signal of a fall: PPO on the Lite3 terrain with BALANCE_SCALES added to the default scales.  Per iteration:
+    the share of env steps that end fallen (the mean of extras["episode"]["fall_rate"] over the rollout), that end in a reset, and
+    the mean step reward."""
+    r, env = make(num_envs, {}, terrain=TerrainConfig(seed=1), balance=SIM.BalanceConfig(), scales=dict(_SCALES, **BALANCE_SCALES))
+    sums, rows = torch.zeros(3, dtype=torch.float64, device=DEV), []
+    inner = r.env.step
+
+    def step(actions):
+        out = inner(actions)
+        sums[0] += out[3]["episode"]["fall_rate"].double()
+        sums[1] += out[2].double().mean()
+        sums[2] += out[1].double().mean()
+        return out
+    object.__setattr__(r.env, "step", step)
+    for _ in range(iters):
+        r.learn(1)
+        rows.append(tuple((sums / STEPS).tolist()))
+        sums.zero_()
+    return rows
+
+
+def balance_report(args):
+    lite3 = TerrainConfig(seed=1)
+    runs = (("no balance", None), ("balance", SIM.BalanceConfig()))
+    rounds = {tag: [] for tag, _ in runs}
+    for _ in range(3):
+        for tag, b in runs:
+            rounds[tag].append(timing_round(args.envs, args.iters, {}, terrain=lite3, balance=b))
+    b = SIM.BalanceConfig()
+    lines = [f"closed loop on SurrogateLeggedEnv on the generated DTC terrain (the Lite3 grid), without and with SimConfig(balance=BalanceConfig()) "
+             f"(gravity {b.gravity} m/s^2, h_min {b.h_min} m, lean_eps {b.lean_eps} rad, fall_angle {b.fall_angle} rad, fall_force {b.fall_force:.0f} N, "
+             f"com_offset {b.com_offset}): {args.envs} envs x {STEPS} steps per iteration, {args.iters} iterations, PPO, default arithmetic, the "
+             "default reward scales, fixed seeds", "", "three interleaved rounds, median (min .. max):"]
+    for tag, _ in runs:
+        rs = rounds[tag]
+        lines.append(f"  {tag:11s} env-steps/s, whole loop {spread([r['steps_per_s'] for r in rs], '{:.0f}')}")
+        lines.append(f"  {'':11s} ms per iteration, each call closed by a synchronise: env.step x{STEPS} {spread([r['env_ms'] for r in rs], '{:.2f}')}"
+                     f" | act() x{STEPS} {spread([r['act_ms'] for r in rs], '{:.2f}')} | update() {spread([r['update_ms'] for r in rs], '{:.2f}')}")
+    probes = [balance_probe(args.envs, args.calls) for _ in range(3)]
+    lines += ["", f"one surrogate step and the balance launch behind it at {args.envs} envs on that terrain, us per call (host clock, each closed by a "
+              "synchronise), three rounds:",
+              f"  dtc_sim_step     {spread([p[0] for p in probes])}",
+              f"  dtc_sim_balance  {spread([p[1] for p in probes])}   (envs that lean / are fallen at the end, under random actions with no reset between: "
+              f"{100 * statistics.mean(p[2] for p in probes):.1f} % / {100 * statistics.mean(p[3] for p in probes):.1f} %)"]
+    share, count = balance_family_probe(args.envs)
+    lines += ["", f"an untrained policy with balance, {args.envs} envs on a 6 x 9 grid (column j = family j, max_init_terrain_level 5), 200 steps, no update;",
+              "the share of a family's env steps that lean, that end fallen, and that end in a reset:",
+              "  family              envs   leaning    fallen    reset"]
+    for j, name in enumerate(FAMILIES):
+        lines.append(f"  {name:19s} {int(count[j]):5d}   {100 * share[0][j]:6.2f} %   {100 * share[1][j]:5.2f} %   {100 * share[2][j]:5.2f} %")
+    rows = fall_curve()
+    first, last = statistics.mean(r[0] for r in rows[:5]), statistics.mean(r[0] for r in rows[25:30])
+    lines += ["", "learning signal: 256 envs, 30 iterations, PPO, the Lite3 terrain, the default scales "
+              f"plus BALANCE_SCALES {BALANCE_SCALES}; per iteration the share of env steps that end fallen (fall_rate):",
+              "  " + " ".join(f"{100 * r[0]:.2f}" for r in rows) + "   [%]",
+              "  that end in a reset:",
+              "  " + " ".join(f"{100 * r[1]:.2f}" for r in rows) + "   [%]",
+              "  mean step reward:",
+              "  " + " ".join(f"{r[2]:+.5f}" for r in rows),
+              f"  fall_rate, iterations 1-5: {100 * first:.3f} %   iterations 26-30: {100 * last:.3f} %   difference: {100 * (last - first):+.3f} points"]
+    lines += ["", "bench.py runs no env step: its headline is not re-measured here."]
+    return lines
+
+
 ALL_FAMILIES = (0.1, 0.1, 0.1, 0.1, 0.15, 0.15, 0.1, 0.1, 0.1)
 
 
@@ -626,11 +747,12 @@ def main():
     ap.add_argument("--actuator", action="store_true")
     ap.add_argument("--flight", action="store_true")
     ap.add_argument("--contacts", action="store_true")
+    ap.add_argument("--balance", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if args.tilt or args.terrain or args.actuator or args.flight or args.contacts:
+    if args.tilt or args.terrain or args.actuator or args.flight or args.contacts or args.balance:
         report = (tilt_report if args.tilt else terrain_report if args.terrain else actuator_report if args.actuator else
-                  flight_report if args.flight else contacts_report)
+                  flight_report if args.flight else contacts_report if args.contacts else balance_report)
         text = "\n".join(report(args)) + "\n"
         print(text)
         if args.out:

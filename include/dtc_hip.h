@@ -697,6 +697,85 @@ typedef struct DtcSimContacts {
 int dtc_sim_contact_abi_sizes(int64_t* out, int cap);
 int dtc_sim_contacts(const DtcSimStep* st, const DtcSimCfg* cfg, const DtcSimContacts* con, int N, void* stream);
 
+/* ---- surrogate legged env: support-polygon balance and falls (opt-in) ----------------------
+ * dtc_sim_balance (csrc/sim_balance.hip) is a launch of its own that runs directly behind any dtc_sim_step*, and in front of
+ * dtc_sim_contacts, on what the step wrote, once per env step.  It is an overlay: a point-mass inverted pendulum about the edge of
+ * the support polygon of the stance feet.  Per env it owns lean [N,4] fp32 = (p.x, p.y, v.x, v.y): p is the world-frame horizontal
+ * direction in which the body tips times the tip angle [rad], v its rate; and fallen [N] uint8.  One lane per env, 64-thread
+ * workgroups.  No LDS, no atomics, no scratch.  The ABI version stays: no existing signature or struct changes.
+ *
+ * What this model is NOT: attitude dynamics.  The link positions are not rotated with the lean: the feet and hips in
+ * rigid_body_state stay where the step put them, so the planner and dtc_sim_contacts see the un-leaned positions (dtc_sim_contacts
+ * runs behind this launch and turns its knee, C1, with the leaned base_quat about the lowered base_pos: its sample points run from
+ * the un-leaned hip through that knee to the un-leaned foot).  Pushes do not
+ * feed the lean rate.  There is no friction and no slipping pivot.  The stance feet are joined in the fixed order FL, FR, HR, HL
+ * (legs 0, 1, 3, 2); crossed feet are neglected, a self-intersecting outline gives whatever the rule below gives.  Control types
+ * "V" / "T" and `forces` stay absent.  Every constant of DtcSimBalance is a free choice of the surrogate, fitted to nothing.
+ * The next step reads what this launch wrote where it carries state in root_states: the yaw pair (renormalised there; L below
+ * scales q.z and q.w alike, so the yaw is kept), under dtc_sim_step_tilt the plane normal n, which a stance of three or more
+ * extended legs replaces by its fit and a smaller one KEEPS, lean included (the lean is then composed onto it again: in that
+ * case the attitude tips faster than |p| says), and under dtc_sim_step_fly z (lower by the drop of B8).
+ *
+ * Inputs, as the step just wrote them: B = base_pos, q = base_quat (x, y, z, w), F_l = rigid_body_state[foot_l][0:3],
+ * stance_l = contact_filt[l] != 0, fresh = (episode_length_buf == 1: the step after a reset), projected_gravity, base_lin_vel,
+ * base_ang_vel, root_states[10:12], contact_forces[0][2], lean.  Only + - * /, sqrt and comparisons, each a single-rounded fp32
+ * operation in the order below (-ffp-contract=off, no libm call); tests/sim_balance_oracle.py restates it in numpy float32, bit for
+ * bit, and is the specification.  Every comparison is false for a NaN.
+ *   B1. V[0 .. k - 1]: the F_l of the stance legs in the order 0, 1, 3, 2, packed to the front; k = their number; V[k ..] = 0.
+ *   B2. ry = sqrt(q.z * q.z + q.w * q.w);  zy = q.z / ry;  wy = q.w / ry;  cy = 1 - 2 * (zy * zy);  sy = 2 * (zy * wy);
+ *       c = (B.x + (cy * ox - sy * oy),  B.y + (sy * ox + cy * oy)),  (ox, oy) = com_offset
+ *   B3. area = (V1.x - V0.x) * (V2.y - V0.y) - (V1.y - V0.y) * (V2.x - V0.x), for k = 4 plus
+ *       ((V2.x - V0.x) * (V3.y - V0.y) - (V2.y - V0.y) * (V3.x - V0.x)).   best = +inf, N = V0.xy; then edge j = 0..3 from V[j] to E,
+ *       E = V[0] for j = 3 or j + 1 == k, else V[j + 1];  active: j == 0 ? k >= 1 : (k >= 2 and j < (k == 2 ? 1 : k)):
+ *       e = E - V[j];  w = c - V[j];  ee = e.x * e.x + e.y * e.y;  t = (w.x * e.x + w.y * e.y) / ee;
+ *       t = t > 0 ? (t < 1 ? t : 1) : 0  (one foot: 0 / 0 gives 0, the point itself);  G = V[j] + t * e;  r = c - G;
+ *       d2 = r.x * r.x + r.y * r.y;  active and d2 < best: best = d2, N = G.   cr = e.x * w.y - e.y * w.x;
+ *       left = every active edge has cr >= 0;  right = every active edge has cr <= 0.
+ *       inside = k >= 3 and ((area > 0 and left) or (area < 0 and right));  dist = sqrt(best);  d = inside ? -dist : dist;
+ *       u = ((c.x - N.x) / dist, (c.y - N.y) / dist)
+ *   B4. top = V0.z, then for slot 1..3: k > slot and V[slot].z > top: top = V[slot].z;  h0 = B.z - top;  h = h0 > h_min ? h0 : h_min
+ *   B5. den = h * h + d * d;  m0 = sqrt(p.x * p.x + p.y * p.y);  outside = k >= 1 and d > 0;  within = k >= 1 and not outside;
+ *       outside:              a.i = (gravity * (d * u.i + h * p.i)) / den
+ *       within and m0 > 0:    a.i = -(((gravity * (-d)) * p.i) / (m0 * den))                              (restoring)
+ *       else (k = 0: airborne, no torque; or upright over the support):  a = 0
+ *   B6. v' = v + a * dt;  p' = p + v' * dt;  dot = p'.x * p.x + p'.y * p.y;  m1 = sqrt(p'.x * p'.x + p'.y * p'.y);
+ *       lands = within and (not (m0 > 0) or dot <= 0 or m1 < lean_eps);  lands or fresh: p' = v' = 0 (the arrival rate is
+ *       dissipated, as a landing of dtc_sim_step_fly is).  A lean only lands over its support: outside it passes through zero.
+ *   B7. m = sqrt(p'.x * p'.x + p'.y * p'.y);  fell = m > fall_angle;  fallen[n] = fell;
+ *       fell: contact_forces[n][0][2] = (f0 < fall_force ? fall_force : f0), f0 its value (a crash force of dtc_sim_step_fly is
+ *       never lowered); dtc_check_termination then ends the episode by the reference's rule.  Otherwise the row is not written.
+ *   B8. l = (-(p'.y * 0.5), p'.x * 0.5);  ln = sqrt((l.x * l.x + l.y * l.y) + 1);  L = (l.x / ln, l.y / ln, 0, 1 / ln): the rotation
+ *       about the horizontal axis z x p' by 2 atan(m / 2) (m - m^3 / 12: at fall_angle 0.8 it is 0.761).  q' = L (x) q:
+ *       q'.x = (L.w * q.x + L.x * q.w) + L.y * q.z;   q'.y = (L.w * q.y - L.x * q.z) + L.y * q.w;
+ *       q'.z = (L.w * q.z + L.x * q.y) - L.y * q.x;   q'.w = (L.w * q.w - L.x * q.x) - L.y * q.y;   qc = (-q'.x, -q'.y, -q'.z, q'.w);
+ *       with rot(q, v) of C1 above:  g = rot(qc, (0, 0, -1));  lv = rot(qc, rot(q, base_lin_vel));
+ *       ww = rot(q, base_ang_vel);  av = rot(qc, (ww.x + (-v'.y), ww.y + v'.x, ww.z))   (the lean rate is omega = z x v');
+ *       z1 = B.z - (h * (m * m)) * 0.5
+ *   B9. lean[n] = (p'.x, p'.y, v'.x, v'.y).  rigid_body_state[n][0][0:7] = (B.x, B.y, zz, qq) with (zz, qq) = (z1, q') if m > 0, else
+ *       (B.z, q).  With m > 0 only: base_quat = root_states[3:7] = q';  projected_gravity = g;  base_lin_vel = lv;  base_ang_vel = av;
+ *       root_states[10] += -v'.y;  root_states[11] += v'.x;  root_states[2] = base_pos[2] = z1.  With m > 0 false (upright, or
+ *       a NaN) those tensors keep their bytes.
+ * Everything else stays byte for byte: every other row and column of rigid_body_state and contact_forces, every input.
+ * `st`, `cfg`: the descriptor and constants of the dtc_sim_step* call this one follows; of `st` only the tensors named above are
+ * read here (the others may be NULL), of `cfg` num_bodies and feet.  DTC_ERR_ARG before any launch (comparisons written so that a
+ * NaN is refused): a null descriptor or a null pointer among those named or lean / fallen; N outside 1..2^24; h_min, fall_angle or
+ * dt not > 0 or not finite; fall_force not > 100 (the termination threshold) or not finite; gravity or lean_eps negative or not
+ * finite; a com_offset that is not finite; num_bodies < 2; a foot that is body 0 or outside 1..num_bodies - 1. */
+typedef struct DtcSimBalance {
+    float* lean;                     /* [N,4], read and written: (p.x, p.y, v.x, v.y)                                     */
+    uint8_t* fallen;                 /* [N], written                                                                      */
+    float gravity;                   /* m/s^2 (>= 0)                                                                      */
+    float h_min;                     /* m, floor of the pendulum's length (> 0)                                           */
+    float lean_eps;                  /* rad, a lean over its support shorter than this lands (>= 0)                       */
+    float fall_angle;                /* rad, |p| above it is a fall (> 0)                                                 */
+    float fall_force;                /* N, raised into contact_forces[n][0][2] of a fallen env (> 100)                    */
+    float dt;                        /* s, float32(sim_dt * decimation): one integration step per env step (> 0)          */
+    float com_offset[2];             /* m, base frame: the centre of mass relative to the base's origin                   */
+} DtcSimBalance;
+/* sizeof() of DtcSimBalance, in a table of its own (the older tables keep their entries). */
+int dtc_sim_balance_abi_sizes(int64_t* out, int cap);
+int dtc_sim_balance(const DtcSimStep* st, const DtcSimCfg* cfg, const DtcSimBalance* bal, int N, void* stream);
+
 /* ---- DTC curriculum terrain, generated on the device (opt-in) ------------------------------
  * dtc_terrain_generate (csrc/terrain.hip) fills the int16 height table [tot_rows, tot_cols] (border included: zeros) and
  * terrain_origins [R, C, 3] fp32 from one seed, as ONE launch: the first blocks write the table, the last R * C blocks the origins
