@@ -433,6 +433,44 @@ __device__ __forceinline__ void h2i_tile(CTileArgs& L, const MseEpiH& mse, const
     // The K loop exists twice: the row operand as ONE image (every layer but the actor's first) keeps no descriptor state in the loop
     const int a_total = A.total, a_nseg = A.nseg, a_tblocks = A.tblocks;
     f32x16 acc[TM][TN];
+    // What the epilogue reads per lane besides the accumulators -- the bias of the lane's columns (forward), the sign-record words of its
+    // (row group, column) pairs (data gradient of a ReLU layer), the target rows of its rows (MSE) -- is requested in the K loop's
+    // prologue, with the exponents: at its point of use, behind the loop's closing barrier, each was one more exposed round trip.
+    // (The saved activations of an ELU layer's data gradient stay where they are used: DESIGN.md 4.5.)
+    const bool full = (m0 + BMT <= M) && (n0 + BN <= N);
+    const int r16 = lane >> 2, c8 = lane & 3;
+    float bias_pre[TN];
+    unsigned rmask_pre[TM][TN];
+    long long tidx_pre[TM][2];
+    auto epilogue_operands = [&]() {
+        if constexpr (EPI == EPI_FWD) {
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const int col = n0 + co[j] + l31;
+                bias_pre[j] = (bias && col < N) ? bias[col] : 0.f;
+            }
+        } else if constexpr (EPI == EPI_DGRAD) {
+            if (dg.rmask) {
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j) {
+                    const int mcol = n0 + co[j] + l31;
+                    // (uniform) a group behind M has no record words: its rows are zeros; a group that straddles M holds 0 bits for its rows >= M
+                    const bool grp = full || m0 + ro[i] < M;
+                    rmask_pre[i][j] = (grp && mcol < N) ? dg.rmask[((long long)((m0 + ro[i]) >> 5) * 2 + half) * dg.ldm + mcol] : 0u;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int row = m0 + ro[i] + r16 + 16 * q;
+                tidx_pre[i][q] = mse.tidx[row < M ? row : 0];
+            }
+        }
+    };
     auto k_loop = [&](auto multi_c) {
     constexpr bool MULTI = decltype(multi_c)::value;
     // ---- loader cursor (one stage ahead of the MFMAs)
@@ -471,29 +509,52 @@ __device__ __forceinline__ void h2i_tile(CTileArgs& L, const MseEpiH& mse, const
     // its predecessor's exponent, per row and per weight row (its products are zero whatever the scale).  Row part: thread r < BMT walks
     // the blocks of row r into Dt.  Column part: a lane's result columns are fixed (co[j] + l31), their exponents are read from the
     // weight image at the borders (the next border's one block ahead, into registers).
-    if (tid < BMT) {
-        int prev_a = 0, prev = 0, b = 0;
-        for (int i = 0; i < A.nseg; ++i) {
-            const HSeg sg = hseg_at(A, i);
-            const int* ex = sg.exps + (long long)ctile * sg.kbs * 128 + crow0 + tid;
-            for (int k = 0; k < sg.kbs; ++k, ++b) {
-                const int ea = ex[k * 128];
-                prev_a = ea == HI_EZERO ? prev_a : ea;
-                Dt[b][tid] = (short)(prev_a - prev);
-                prev = prev_a;
-            }
-        }
-        Dt[A.tblocks][tid] = (short)(-prev);
-        // (the first block's "delta" Dt[0] = ea(0) is never applied: the accumulators start at zero)
-    }
+    // ONE global round trip: every load of the prologue -- the weight exponents of the first two blocks, all (at most MAX_TB) row
+    // exponents of thread r's row, the epilogue's operands -- is issued before the first value is used; the walk then runs on registers.
+    // (Load, wait, store block after block -- the compiler's remainder loop for fewer than 8 blocks -- was one exposed round trip per
+    // 128-column block, and one more for the weight exponents behind it, in every workgroup of the launch at the same moment.)
     const int* __restrict__ wex = wexps + (long long)tc * a_tblocks * 128 + l31;      // + b * 128 + co[j]: weight row co[j] + l31, block b
     int wcur[TN], wnext[TN];                             // exponent in force of the lane's weight rows; raw exponent of the next block
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
-        const int e0 = wex[co[j]];
-        wcur[j] = e0 == HI_EZERO ? 0 : e0;
+        wcur[j] = wex[co[j]];
         wnext[j] = a_tblocks > 1 ? wex[128 + co[j]] : HI_EZERO;
     }
+    epilogue_operands();
+    if (tid < BMT) {
+        int ev[MAX_TB];
+        {                                                // (uniform) cursor over the blocks of the operand's images: never past an image's kbs blocks
+                                                         // (every image has kbs >= 1: to_operand requires width > 0)
+            int si = 0, k = 0;
+            HSeg sg = hseg_at(A, 0);
+            const int* ex = sg.exps + (long long)ctile * sg.kbs * 128 + crow0 + tid;
+#pragma unroll
+            for (int b = 0; b < MAX_TB; ++b) {
+                ev[b] = HI_EZERO;
+                if (b >= a_tblocks) break;
+                ev[b] = ex[k * 128];
+                ++k;
+                if (MULTI && k == sg.kbs && si + 1 < a_nseg) {
+                    sg = hseg_at(A, ++si);
+                    ex = sg.exps + (long long)ctile * sg.kbs * 128 + crow0 + tid;
+                    k = 0;
+                }
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        int prev_a = 0, prev = 0;
+#pragma unroll
+        for (int b = 0; b < MAX_TB; ++b) {
+            if (b >= a_tblocks) break;
+            prev_a = ev[b] == HI_EZERO ? prev_a : ev[b];
+            Dt[b][tid] = (short)(prev_a - prev);
+            prev = prev_a;
+        }
+        Dt[a_tblocks][tid] = (short)(-prev);
+        // (the first block's "delta" Dt[0] = ea(0) is never applied: the accumulators start at zero)
+    }
+#pragma unroll
+    for (int j = 0; j < TN; ++j) wcur[j] = wcur[j] == HI_EZERO ? 0 : wcur[j];
 
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -661,10 +722,21 @@ __device__ __forceinline__ void h2i_tile(CTileArgs& L, const MseEpiH& mse, const
     };
     __syncthreads();
     if constexpr (SELF) read_self(S0{});
-    for (int trip = (a_total + 2) / 3; trip > 0; --trip) {
+    // Exactly a_total stages, stage s on buffer s % 3: whole trips, then a peeled tail of a_total % 3 stages.  (Trips rounded up ran up to
+    // two stages past the end -- transfers, fragment reads, 12 MFMAs and a barrier each on all-zero operands, which add +0 to sums that
+    // started at +0 and change no bit: 1 of 33 stages at a reduction of 512, 2 of 18 at 256, 2 of 3 at 12.  The loader still runs two
+    // stages ahead, so the last two real stages request pieces past the end -- out-of-range lanes, zeros land -- and a stage's vmcnt
+    // count means what it meant.  `if (done == a_total) break;` between the stages of a trip instead of the tail: 430-500 bytes of
+    // scratch in the 128-row kernels.)  Measured with the prologue's two changes: step 47.3-47.5 -> 46.5-46.6 ms, forward launch
+    // 51.5 -> 49.7 us (profiles/h2i_kloop_kernels.md).
+    for (int trip = a_total / 3; trip > 0; --trip) {
         stage(S0{});
         stage(S1{});
         stage(std::integral_constant<int, 2>{});
+    }
+    if (done < a_total) {
+        stage(S0{});
+        if (done < a_total) stage(S1{});
     }
     __syncthreads();                                     // (the transfers past the last stage -- zeros -- have landed too)
     {                                                    // back to the values themselves (2^-e of the last block, exact)
@@ -679,7 +751,6 @@ __device__ __forceinline__ void h2i_tile(CTileArgs& L, const MseEpiH& mse, const
     if (trace && tid == 0) trace[4 * slot + 1] = __builtin_amdgcn_s_memrealtime();
     // every wave is past its last fragment read and every LDS-DMA has landed (the barrier's wait): LDS becomes the patches
     float* patch = reinterpret_cast<float*>(wave < 2 ? &Xs0[0][0] : &Xs1[0][0]) + (wave & 1) * (32 * LDW);
-    const bool full = (m0 + BMT <= M) && (n0 + BN <= N);
 
     double sq = 0.0;
     if constexpr (EPI == EPI_MSE) {
@@ -690,7 +761,7 @@ __device__ __forceinline__ void h2i_tile(CTileArgs& L, const MseEpiH& mse, const
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             const int col = n0 + co[j] + l31;
-            const float bv = (bias && col < N) ? bias[col] : 0.f;
+            const float bv = bias_pre[j];
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] += bv;
             if (wmask && col < N) {                         // sign record of a ReLU layer (see linear_fwd_kernel), any M (h2i_core.hpp: tail rows)
@@ -722,10 +793,7 @@ __device__ __forceinline__ void h2i_tile(CTileArgs& L, const MseEpiH& mse, const
             for (int i = 0; i < TM; ++i)
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
-                const int mcol = n0 + co[j] + l31;
-                // (uniform) a group behind M has no record words: its rows are zeros; a group that straddles M holds 0 bits for its rows >= M
-                const bool grp = full || m0 + ro[i] < M;
-                const unsigned bits = (grp && mcol < N) ? dg.rmask[((long long)((m0 + ro[i]) >> 5) * 2 + half) * dg.ldm + mcol] : 0u;
+                const unsigned bits = rmask_pre[i][j];
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[i][j][r] = (bits >> r) & 1u ? acc[i][j][r] : 0.f;
             }
@@ -733,7 +801,6 @@ __device__ __forceinline__ void h2i_tile(CTileArgs& L, const MseEpiH& mse, const
     }
 
     // ---- through the patch: lane -> rows r16 + 16 q of the 32 x 32 tile, the 8 columns 8 c8 .. + 7; final values, fp32 stores, row maxima
-    const int r16 = lane >> 2, c8 = lane & 3;
     f32x4 T[TM][TN][2][2];
     u32 mrow[TM][2];
 #pragma unroll
@@ -758,7 +825,7 @@ __device__ __forceinline__ void h2i_tile(CTileArgs& L, const MseEpiH& mse, const
             if constexpr (EPI == EPI_MSE) {
                 // e = (acc + bias) - target[tidx[row], tcol0 + col];  dY = e * scale;  partial = sum e^2 (double)
                 const rsrc_t tres = make_rsrc_bytes(mse.target, mse.target_bytes), bres = make_rsrc_bytes(bias, bias ? (long long)N * 4 : 0);
-                const long long src = mse.tidx[row < M ? row : 0];
+                const long long src = tidx_pre[i][q];
                 f32x4 tg[2];
                 if constexpr (WIDE_T) {
                     // target of 2 GiB or more (WIDE of h2i_pack_kernel): 64-bit lane address; nothing is read behind the row tail, the
